@@ -23,9 +23,15 @@ the product's partitioner (midas_amd.dist.shard_items, the weights of midas_amd/
 collective, one RCCL all-gather of the summary rows, 400 M sites / the slowest rank (`--configs3` adds the block at N = 1,
 `--config c4` makes configs[3] the line's own workload).
 
-Secondary figures in the same JSON line: the step over a resident PACKED batch (`value_resident_packed`: the tile-ordered
-records + one byte per base of pack_reads.hip, built once, outside the region), the device copy rate of this box, the CPU
-baselines, and -- when rocprofv3 is on PATH -- the HBM traffic of the step's kernels measured on this box.
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` (one timed step), the roofline of
+the step's kernels from HIP events recorded in those same steps.  `--dump-outputs DIR` also writes what the last timed step
+computed as DIR/<name>.npy (float32 / float64; a fixed, seeded sample of the sites).  The inputs are seeded: the same arguments
+give the same inputs on every run.
+
+`--full` adds the secondary figures to the same JSON line: the step over a resident PACKED batch (`value_resident_packed`:
+the tile-ordered records + one byte per base of pack_reads.hip, built once, outside the region), the stream rates of this
+box, the CPU baselines and the parity with the C oracle, the merge50 / stage_e2e / bam_decode blocks, and -- when rocprofv3
+is on PATH -- the HBM traffic of the step's kernels measured on this box; with N > 1, the product's own RCCL exchange.
 """
 import argparse
 import json
@@ -70,6 +76,27 @@ def load_pmc_traffic(key, workload):
         return float(e["hbm_bytes_per_launch"]), "committed profile: %s" % e.get("source", "profiles/pmc_traffic.json")
     except Exception:
         return None, None
+
+
+DUMP_SITES = 1 << 20        # per-site outputs: a fixed, seeded sample of at most this many sites (~45 MB of .npy in all)
+DUMP_SEED = 20260927
+
+
+def dump_outputs(path, contigs, counts, allele, stats):
+    """What a caller of the step receives, as .npy: per-site A/C/G/T counts and ref alleles at a fixed, seeded sample of the
+    sites (site_index: positions in the batch's site order), their sums per contig over EVERY site, and the per-species
+    counters.  Integers are stored as float64 (exact) or float32 (the one-byte alleles)."""
+    os.makedirs(path, exist_ok=True)
+    n = counts.shape[0]
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SITES)) if n > DUMP_SITES else np.arange(n)
+    off = contigs.site_offsets()
+    per_contig = np.add.reduceat(counts.astype(np.uint64), off[:-1], axis=0) if n else np.zeros((0, 4), np.uint64)
+    per_contig[off[1:] == off[:-1]] = 0          # (reduceat takes the next site for an empty contig)
+    out = {"site_index": idx.astype(np.float64), "counts": counts[idx].astype(np.float64),
+           "ref_allele": allele[idx].astype(np.float32), "counts_per_contig": per_contig.astype(np.float64),
+           "species_stats": np.asarray(stats).astype(np.float64)}
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def cpu_baseline(thr, contigs, reads, min_seconds):
@@ -254,10 +281,11 @@ def _all_reduce(t, op):
         dist.all_reduce(t, op=op)
 
 
-def configs3_strong(ctx, thr, rank, world, collective, steps):
+def configs3_strong(ctx, thr, rank, world, collective, steps, dump=None):
     """BASELINE.json configs[3] as the product deals it: ONE 100-species sample (400 Mb, 80 M aligned reads), its contigs dealt
     to the ranks by midas_amd.dist.shard_items, every rank piling up its share, one all-gather of the summary rows per job.
-    Strong scaling: value = 400 M sites / the slowest rank.  Returns the block rank 0 prints (None elsewhere)."""
+    Strong scaling: value = 400 M sites / the slowest rank.  Returns the block rank 0 prints (None elsewhere).
+    dump: a directory for rank 0's dump_outputs -- its share's per-site results and the folded per-species rows."""
     import torch
     import torch.distributed as dist
     from midas_amd import abi, synth
@@ -301,6 +329,10 @@ def configs3_strong(ctx, thr, rank, world, collective, steps):
         allv[0].copy_(vals)
     allv = allv.cpu().numpy()
     total = gathered.sum(dim=0).cpu().numpy()           # the fold snps_summary does: per-species counters over the ranks
+    if dump and rank == 0:
+        counts, allele, _ = batch.fetch()
+        dump_outputs(dump, contigs, counts, allele, total)
+        del counts, allele
     batch.close()
     if rank != 0:
         return None
@@ -565,6 +597,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", help="workload (default c3 = BASELINE configs[2], the largest single-GPU "
                                                   "configuration; c2 = configs[1]; c4 = configs[3] sharded over the ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (packed path, stream rates, PMC traffic, "
+                         "CPU baselines and oracle parity, merge50, stage_e2e, bam_decode; the native RCCL exchange at N > 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline budget (rank 0, N=1 only)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 traffic measurement")
@@ -579,13 +616,13 @@ def main():
     ap.add_argument("--no-bam-decode", action="store_true", help="skip the bam_decode block (the workload as a BAM, decoded on the device and by the host; rank 0 at N = 1)")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    t_start = time.perf_counter()
     if a.pmc_child:
         pmc_child(a.pmc_child, a.steps)
         return
 
-    import torch
-    import torch.distributed as dist
-    from midas_amd import abi, synth
+    import threading
+    from midas_amd import abi, synth, utility
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -594,6 +631,21 @@ def main():
         if world == 1 and a.gpus > 1:
             sys.exit("bench.py --gpus %d must be launched with torch.distributed.run --nproc-per-node %d" % (a.gpus, a.gpus))
         sys.exit("--gpus (%d) != WORLD_SIZE (%d)" % (a.gpus, world))
+    inputs = {}
+    if a.config != "c4":        # the seeded inputs are generated (by threads: the serial loop's arrays) while torch and the device come up
+        cfg = dict(synth.CONFIGS[a.config])
+        cfg["seed"] = cfg["seed"] + 1000 * rank       # every rank owns different species (weak scaling)
+
+        def generate():
+            try:
+                inputs["data"] = synth.make_dataset(workers=min(16, utility.cpu_budget()), **cfg)
+            except BaseException as e:      # noqa: BLE001  (raised again below, in the main thread)
+                inputs["error"] = e
+        generator = threading.Thread(target=generate, daemon=True)
+        generator.start()
+
+    import torch
+    import torch.distributed as dist
     if not torch.cuda.is_available():
         sys.exit("bench.py needs an MI355X: torch.cuda.is_available() is False (there is no CPU fallback)")
     if _on_one_gpu():
@@ -616,11 +668,13 @@ def main():
     if a.config == "c4":        # configs[3]: this rank's contigs of the one 400 Mb sample (strong scaling)
         contigs, reads, share = synth.c4_share(rank, world)
     else:
-        cfg = dict(synth.CONFIGS[a.config])
-        cfg["seed"] = cfg["seed"] + 1000 * rank       # every rank owns different species (weak scaling)
-        contigs, reads = synth.make_dataset(**cfg)
+        generator.join()
+        if "error" in inputs:
+            raise inputs["error"]
+        contigs, reads = inputs.pop("data")
     args = dict(abi.DEFAULT_ARGS)
     thr = abi.Thresholds.from_args(args)
+    t_data = time.perf_counter()
 
     ctx = abi.Context(local_rank)
     # The step runs on a stream torch knows as its current one: torch's copies and the RCCL collectives order themselves
@@ -634,6 +688,9 @@ def main():
     batch = ctx.batch(contigs, reads)            # uploads the BAM-native arrays as they are; picks the path
     info = batch.info()
     n_sp = contigs.n_species
+    if rank == 0:
+        print("bench.py: setup %.1f s (inputs %.1f s, context and upload %.1f s)" % (time.perf_counter() - t_start, t_data - t_start,
+                                                                                   time.perf_counter() - t_data), file=sys.stderr, flush=True)
     # N > 1: a rank's K steps are its share of the job; the job's one exchange -- the all-gather of every rank's summary
     # rows, what snps_summary needs to write summary.txt -- follows the last step, inside the timed region, exactly as
     # midas_amd/run/snps.py does it (all of a rank's contigs, then one all-gather).
@@ -675,6 +732,13 @@ def main():
     batch.sync()   # surfaces MIDAS_SNPS_ERR_READ_* of the last run, if any
     if collective and not torch.equal(gathered[rank], rows):      # the gathered table holds this rank's rows where they belong
         sys.exit("bench.py: all-gathered summary rows differ from this rank's rows")
+    strong_headline = world > 1 and a.config != "c4"      # (N > 1: configs3_strong below is the line's own figure)
+    if a.dump_outputs and rank == 0 and not strong_headline:
+        counts, allele, stats = batch.fetch()       # the last timed step's results, as the batch holds them
+        if collective:      # what the job's caller receives: every rank's per-species rows of that step, folded
+            stats = gathered[:, a.steps - 1].sum(dim=0).cpu().numpy()
+        dump_outputs(a.dump_outputs, contigs, counts, allele, stats)
+        del counts, allele
 
     el = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
     sites = torch.tensor([float(info.n_sites)], dtype=torch.float64, device="cuda")
@@ -695,7 +759,7 @@ def main():
 
     # ---- secondary region: the step over a resident PACKED batch (the layout is built once, outside the region) ----------
     packed = None
-    if world == 1:
+    if world == 1 and a.full:
         try:
             batch.select_path(abi.PATH_PACKED)
             kp = max(1, a.steps)
@@ -722,9 +786,10 @@ def main():
             batch.select_path(abi.PATH_AUTO)
 
     strong = None
-    if (world > 1 or a.configs3) and a.config != "c4":
+    if strong_headline or (a.configs3 and a.config != "c4"):
         # (N > 1: the block becomes the line's own figure below, so it runs exactly the K steps the line reports)
-        strong = configs3_strong(ctx, thr, rank, world, collective, a.steps if world > 1 else max(1, min(a.steps, 50)))
+        strong = configs3_strong(ctx, thr, rank, world, collective, a.steps if world > 1 else max(1, min(a.steps, 50)),
+                                 dump=a.dump_outputs if strong_headline else None)
 
     out = None
     if rank == 0:
@@ -812,7 +877,7 @@ def main():
         if packed is not None:
             out["value_resident_packed"] = packed["value"]
             out["resident_packed"] = packed
-        if world == 1:
+        if world == 1 and a.full:
             try:      # what this box streams right now: kernels built to saturate (4 workgroups per CU, 16 B per lane, 4 GiB buffers)
                 rates = ctx.stream_rates(1 << 32, 3)
                 ceil = max(rates.values())
@@ -842,7 +907,7 @@ def main():
                                 t_mix = rd / (rates["read_GBps"] * 1e9) + wr / (rates["write_GBps"] * 1e9)
                                 out["roofline"]["mixed_traffic_floor_ms_this_box"] = t_mix * 1e3
                                 out["roofline"]["frac_of_mixed_traffic_floor_this_box"] = t_mix * 1e3 / step_kernels_ms
-        if world == 1 and not a.no_cpu:
+        if world == 1 and a.full and not a.no_cpu:
             cb, cb_all, cb_species, ref = cpu_baseline(thr, contigs, reads, a.cpu_seconds)
             out["cpu_baseline"] = cb
             out["cpu_baseline_all_cores"] = cb_all
@@ -874,7 +939,7 @@ def main():
             except Exception as e:  # the estimate is a courtesy number; never fail the bench on it
                 out["cpu_python_shaped_estimate"] = {"error": str(e)}
     native = None
-    if collective and not _on_one_gpu():       # (every rank: the product's own RCCL binding beside the harness's process group)
+    if collective and a.full and not _on_one_gpu():       # (every rank: the product's own RCCL binding beside the harness's process group)
         native = native_rccl(ctx, rank, world)
         if rank == 0:
             out["native_rccl"] = native
