@@ -656,6 +656,67 @@ int32_t midas_genes_terms(midas_snps_ctx* ctx, const midas_snps_thresholds* thr,
 int32_t midas_genes_sum(midas_snps_ctx* ctx, int64_t n_pairs, const int32_t* gene, const double* term, int64_t n_genes,
                         int64_t* out_aligned, int64_t* out_mapped, double* out_depth, float* out_kernel_ms);
 
+/* ---- merge_midas.py genes: cross-sample gene matrices ----------------------------------------------------------------------
+ * Both readers parse as utility.parse_file does under Python 3 (midas/utility.py:208-216): universal newlines, '\t'-split
+ * header and rows, a row whose field count differs from the header's skipped, a field taken from the LAST header column of
+ * its name.  Numbers: float() / int() of the field, ASCII whitespace trimmed, plain decimal / nan / inf / infinity spellings
+ * only (anything else is MIDAS_SNPS_ERR_BAD_LAYOUT naming file and line).  err1024 (nullable, 1024 bytes) receives the message.
+ *
+ * midas_genes_merge_map_*: read_cluster_map (midas/merge/genes.py:91-98) -- gene_info.txt[.gz] -> centroid_99 ->
+ *   <cluster_column> (e.g. "centroid_95"), row by row, the last row of an id winning.  columns: out5[0..4] = the distinct
+ *   clusters in sorted byte order back to back (char) and their offsets (int64, n_clusters + 1), the distinct centroid_99 ids
+ *   in first-appearance order (char) and their offsets (int64, n_genes + 1), each id's cluster index (uint32, n_genes);
+ *   sizes2 = bytes of the two id pools.  They belong to the handle.                                                         */
+typedef struct midas_genes_merge_map midas_genes_merge_map;
+int32_t midas_genes_merge_map_open(const char* path, const char* cluster_column, midas_genes_merge_map** out, char* err1024);
+int64_t midas_genes_merge_map_n_clusters(const midas_genes_merge_map* m);
+int64_t midas_genes_merge_map_n_genes(const midas_genes_merge_map* m);
+int32_t midas_genes_merge_map_columns(const midas_genes_merge_map* m, const void** out5, int64_t* sizes2);
+void midas_genes_merge_map_close(midas_genes_merge_map* m);
+
+/* midas_genes_merge_tables_*: the per-sample parse of build_gene_matrices (midas/merge/genes.py:18-26) for n_tables
+ *   genes.gz files, `threads` files at a time (0: all cores).  Per kept row: gene_id (ref_id when that column exists),
+ *   copy_number (normalized_coverage when it exists) and coverage (raw_coverage) as f64, count_reads as i64 (0 without the
+ *   column).  resolve: every row's gene id -> cluster index through the map (sp.map[...], genes.py:22; an id the map lacks is
+ *   MIDAS_SNPS_ERR_BAD_LAYOUT); with reuse != 0 a table whose ids and offsets are byte-equal to an earlier table's takes
+ *   that table's cluster vector (*out_same_as = its index, else -1).  columns: out6[0..5] = ids (char), id offsets (int64,
+ *   rows + 1), copy (f64), depth (f64), reads (i64), clusters (uint32, after resolve).  They belong to the handle.         */
+typedef struct midas_genes_merge_tables midas_genes_merge_tables;
+int32_t midas_genes_merge_tables_open(int32_t n_tables, const char* const* paths, int32_t threads, midas_genes_merge_tables** out,
+                                      char* err1024);
+int64_t midas_genes_merge_tables_rows(const midas_genes_merge_tables* ts, int32_t table);
+int32_t midas_genes_merge_tables_resolve(midas_genes_merge_tables* ts, const midas_genes_merge_map* m, int32_t reuse, int32_t threads,
+                                         char* err1024);
+int32_t midas_genes_merge_tables_columns(const midas_genes_merge_tables* ts, int32_t table, const void** out6, int64_t* out_id_bytes,
+                                         int32_t* out_same_as);
+void midas_genes_merge_tables_close(midas_genes_merge_tables* ts);
+
+/* The arithmetic of build_gene_matrices (midas/merge/genes.py:12-30) on the device for n_samples tables of one species:
+ * sample s has n_rows[s] rows with cluster[s][i] in [0, n_clusters) and copy / depth / reads columns (host memory).  Output
+ * rows are the clusters sample 0's table mentions (sorted(sp.samples[0].genes['depth']), genes.py:40), in index order:
+ * out_row_cluster[r]; per (row r, sample s) at r * n_samples + s: the fp64 sums of copy and depth over the sample's rows of
+ * the cluster IN TABLE ORDER (starting from 0.0), the i64 sum of reads, and out_state = 0 (the cluster is not in the sample's
+ * table: the defaultdict's 0.0 in presabs), 1 (present, copy < min_copy), 2 (present, copy >= min_copy).  out_capacity: rows
+ * the outputs hold (min(n_clusters, n_rows[0]) always suffices); *out_n_rows: rows written.  group_samples: samples on the
+ * device at a time (0: as many as a quarter of the free device memory holds); the bytes do not depend on it.
+ * out_kernel_ms (nullable): device time of the kernels (sort, bounds, row list, transposes, merge), copies not counted.     */
+int32_t midas_genes_merge(midas_snps_ctx* ctx, int32_t n_samples, const int64_t* n_rows, const uint32_t* const* cluster,
+                          const double* const* copy, const double* const* depth, const int64_t* const* reads, int64_t n_clusters,
+                          double min_copy, int32_t group_samples, int64_t out_capacity, int64_t* out_n_rows,
+                          uint32_t* out_row_cluster, double* out_copy, double* out_depth, int64_t* out_reads, uint8_t* out_state,
+                          float* out_kernel_ms);
+
+/* genes_{presabs,copynum,depth,reads}.txt (write_gene_matrices, midas/merge/genes.py:32-48): header_line, then per row r
+ * the cluster id of row_cluster[r] (ids / offsets as midas_genes_merge_map_columns gives them) and one cell per sample, str()
+ * of the value.  kind 0 presabs: state 2 -> "1", 1 -> "0", 0 -> "0.0" (values unused); kind 1: values are f64, Python's repr;
+ * kind 2: values are i64.  values / state: [n_rows * n_samples] as midas_genes_merge writes them.  Host only, row blocks
+ * formatted by `threads` workers (0: all cores).
+ * midas_genes_merge_format_f64: repr() of n doubles, each followed by '\n' (capacity >= 33 n bytes) -- the formatter alone. */
+int32_t midas_genes_merge_write_matrix(const char* path, const char* header_line, int32_t kind, int64_t n_rows, const uint32_t* row_cluster,
+                                       const char* cluster_ids, const int64_t* cluster_off, int32_t n_samples, const void* values,
+                                       const uint8_t* state, int32_t threads, char* err1024);
+int32_t midas_genes_merge_format_f64(int64_t n, const double* v, char* out, int64_t capacity, int64_t* out_len);
+
 /* ---- the exchange between ranks (comm.cpp): RCCL itself, no process group ------------------------------------------------
  * One process per GPU; the only thing ranks exchange on this path is the per-species summary rows -- the reference's pool
  * workers return (species_id, aln_stats) through a pipe, midas/run/snps.py:225-241, midas/utility.py:81-107 -- plus, on the

@@ -331,6 +331,20 @@ def load_library(build_if_missing: bool = True):
         'midas_comm_destroy': (None, [vp]),
         'midas_comm_all_gather': (i32, [vp, vp, vp, i64, C.c_char_p]),
         'midas_comm_all_to_all_v': (i32, [vp, vp, vp, vp, vp, C.c_char_p]),
+        'midas_genes_merge_map_open': (i32, [C.c_char_p, C.c_char_p, C.POINTER(vp), C.c_char_p]),
+        'midas_genes_merge_map_n_clusters': (i64, [vp]),
+        'midas_genes_merge_map_n_genes': (i64, [vp]),
+        'midas_genes_merge_map_columns': (i32, [vp, vp, vp]),
+        'midas_genes_merge_map_close': (None, [vp]),
+        'midas_genes_merge_tables_open': (i32, [i32, vp, i32, C.POINTER(vp), C.c_char_p]),
+        'midas_genes_merge_tables_rows': (i64, [vp, i32]),
+        'midas_genes_merge_tables_resolve': (i32, [vp, vp, i32, i32, C.c_char_p]),
+        'midas_genes_merge_tables_columns': (i32, [vp, i32, vp, C.POINTER(i64), C.POINTER(i32)]),
+        'midas_genes_merge_tables_close': (None, [vp]),
+        'midas_genes_merge': (i32, [vp, i32, vp, vp, vp, vp, vp, i64, C.c_double, i32, i64, C.POINTER(i64)] + [vp] * 5
+                              + [C.POINTER(C.c_float)]),
+        'midas_genes_merge_write_matrix': (i32, [C.c_char_p, C.c_char_p, i32, i64, vp, vp, vp, i32, vp, vp, i32, C.c_char_p]),
+        'midas_genes_merge_format_f64': (i32, [i64, vp, vp, i64, C.POINTER(i64)]),
     })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing: fail loudly
@@ -367,6 +381,10 @@ EXPORTED_SYMBOLS = [
     'midas_merge_write_matrix',
     'midas_bam_open_share',
     'midas_comm_device_key', 'midas_comm_probe', 'midas_comm_unique_id', 'midas_comm_create', 'midas_comm_destroy', 'midas_comm_all_gather', 'midas_comm_all_to_all_v',
+    'midas_genes_merge_map_open', 'midas_genes_merge_map_n_clusters', 'midas_genes_merge_map_n_genes', 'midas_genes_merge_map_columns',
+    'midas_genes_merge_map_close', 'midas_genes_merge_tables_open', 'midas_genes_merge_tables_rows', 'midas_genes_merge_tables_resolve',
+    'midas_genes_merge_tables_columns', 'midas_genes_merge_tables_close', 'midas_genes_merge', 'midas_genes_merge_write_matrix',
+    'midas_genes_merge_format_f64',
 ]
 
 
@@ -669,6 +687,129 @@ def read_fasta_files(paths, threads: int = 0):
     io = np.asarray(_Column(owner, ptrs[5] or 0, nrec + 1, np.int64))
     recs = [(ids[int(io[k]):int(io[k + 1])].decode('latin-1'), int(fi[k]), int(off[k]), int(ln[k])) for k in range(nrec)]
     return pool, recs
+
+
+class _GenesOwner:
+    def __init__(self, lib, h, close):
+        self._lib, self._h, self._close = lib, h, close
+
+    def __del__(self):
+        if self._h:
+            getattr(self._lib, self._close)(self._h)
+            self._h = None
+
+
+class GeneClusterMap:
+    """read_cluster_map (midas/merge/genes.py:91-98) read natively (midas_genes_merge_map_*): gene_info.txt[.gz] ->
+    centroid_99 -> `cluster_column`.  .cluster_ids / .cluster_off: the distinct clusters in sorted byte order (index = output
+    row order); .gene_ids / .gene_off / .gene_cluster: the distinct centroid_99 ids in first-appearance order and their
+    clusters.  Read-only views owned by the handle."""
+
+    def __init__(self, path: str, cluster_column: str):
+        lib = load_library()
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        st = lib.midas_genes_merge_map_open(path.encode(), cluster_column.encode(), C.byref(h), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_merge_map_open failed")
+        self._owner = _GenesOwner(lib, h, 'midas_genes_merge_map_close')
+        self.path = path
+        self.n_clusters = int(lib.midas_genes_merge_map_n_clusters(h))
+        self.n_genes = int(lib.midas_genes_merge_map_n_genes(h))
+        ptrs, sizes = (C.c_void_p * 5)(), (C.c_int64 * 2)()
+        lib.midas_genes_merge_map_columns(h, ptrs, sizes)
+        col = lambda k, n, dt: np.asarray(_Column(self._owner, ptrs[k] or 0, n, dt))
+        self.cluster_ids = col(0, int(sizes[0]), np.uint8)
+        self.cluster_off = col(1, self.n_clusters + 1, np.int64)
+        self.gene_ids = col(2, int(sizes[1]), np.uint8)
+        self.gene_off = col(3, self.n_genes + 1, np.int64)
+        self.gene_cluster = col(4, self.n_genes, np.uint32)
+
+    @property
+    def handle(self):
+        return self._owner._h
+
+    def cluster(self, k: int) -> bytes:
+        return bytes(self.cluster_ids[int(self.cluster_off[k]):int(self.cluster_off[k + 1])])
+
+
+class GeneTables:
+    """The samples' genes/output/<species>.genes.gz tables read natively, one worker per file (midas_genes_merge_tables_*):
+    per sample .ids / .id_off (kept rows' gene ids), .copy / .depth (f64), .reads (i64); after resolve(), .cluster (uint32)
+    and .same_as (the earlier sample whose cluster vector it shares, or -1).  Read-only views owned by the handle."""
+
+    def __init__(self, paths, threads: int = 0):
+        lib = load_library()
+        n = len(paths)
+        c_paths = (C.c_char_p * max(n, 1))(*[p.encode() for p in paths])
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        st = lib.midas_genes_merge_tables_open(n, c_paths, int(threads), C.byref(h), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_merge_tables_open failed")
+        self._lib = lib
+        self._owner = _GenesOwner(lib, h, 'midas_genes_merge_tables_close')
+        self.paths = list(paths)
+        self.rows = [int(lib.midas_genes_merge_tables_rows(h, k)) for k in range(n)]
+        self.resolved = False
+        self._columns()
+
+    def _columns(self):
+        lib, h = self._lib, self._owner._h
+        self.ids, self.id_off, self.copy, self.depth, self.reads, self.cluster, self.same_as = [], [], [], [], [], [], []
+        for k, n in enumerate(self.rows):
+            ptrs, nb, same = (C.c_void_p * 6)(), C.c_int64(0), C.c_int32(-1)
+            lib.midas_genes_merge_tables_columns(h, k, ptrs, C.byref(nb), C.byref(same))
+            col = lambda j, m, dt: np.asarray(_Column(self._owner, ptrs[j] or 0, m, dt))
+            self.ids.append(col(0, int(nb.value), np.uint8))
+            self.id_off.append(col(1, n + 1, np.int64))
+            self.copy.append(col(2, n, np.float64))
+            self.depth.append(col(3, n, np.float64))
+            self.reads.append(col(4, n, np.int64))
+            self.cluster.append(col(5, n, np.uint32) if self.resolved else None)
+            self.same_as.append(int(same.value))
+
+    def resolve(self, cmap: "GeneClusterMap", reuse: bool = True, threads: int = 0):
+        err = C.create_string_buffer(1024)
+        st = self._lib.midas_genes_merge_tables_resolve(self._owner._h, cmap.handle, 1 if reuse else 0, int(threads), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_merge_tables_resolve failed")
+        self.resolved = True
+        self._columns()     # (a sample that shares an earlier one's vector views the same memory: one class on the device)
+
+
+GENES_MATRIX_KINDS = {'presabs': 0, 'copynum': 1, 'depth': 1, 'reads': 2}
+
+
+def write_genes_matrix(path: str, header_line: str, kind: str, row_cluster, cmap: "GeneClusterMap", values, state, threads: int = 0):
+    """genes_<kind>.txt of merge_midas.py genes (midas_genes_merge_write_matrix): row_cluster [R] uint32, values / state
+    [R, S] as Context.genes_merge returns them (presabs reads state only)."""
+    lib = load_library()
+    rc = np.ascontiguousarray(row_cluster, dtype=np.uint32)
+    st_ = np.ascontiguousarray(state, dtype=np.uint8)
+    k = GENES_MATRIX_KINDS[kind]
+    vals = None if k == 0 else np.ascontiguousarray(values, dtype=np.float64 if k == 1 else np.int64)
+    R = rc.shape[0]
+    S = st_.shape[1] if st_.ndim == 2 else 0
+    p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+    err = C.create_string_buffer(1024)
+    st = lib.midas_genes_merge_write_matrix(path.encode(), header_line.encode(), k, R, p(rc), p(cmap.cluster_ids),
+                                            p(cmap.cluster_off), S, p(vals), p(st_), int(threads), err)
+    if st != 0:
+        raise MidasSnpsError(st, err.value.decode(errors='replace'))
+
+
+def format_repr_f64(values) -> list:
+    """Python's repr() of every double, by the matrix writer's formatter (midas_genes_merge_format_f64)."""
+    lib = load_library()
+    v = np.ascontiguousarray(values, dtype=np.float64)
+    out = np.empty(33 * v.shape[0] + 1, np.uint8)
+    n = C.c_int64(0)
+    st = lib.midas_genes_merge_format_f64(v.shape[0], v.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), out.shape[0],
+                                          C.byref(n))
+    if st != 0:
+        raise MidasSnpsError(st, "midas_genes_merge_format_f64 failed")
+    return out[:n.value].tobytes().decode().split('\n')[:-1]
 
 
 def write_bam(path, ref_names, ref_lengths, refid, reads, level=6, threads=0):
@@ -1066,6 +1207,35 @@ class Context:
         self._check(st)
         out['kernel_ms'] = float(ms.value)
         return out
+
+    def genes_merge(self, cluster, copy, depth, reads, n_clusters: int, min_copy: float, group_samples: int = 0):
+        """midas_genes_merge(): per sample s the cluster index [n_s] uint32 and copy / depth f64 / reads i64 columns of its
+        table rows (lists of arrays; samples may share one cluster array).  -> dict(rows [R] uint32 = the clusters sample 0
+        mentions, in index order; copy, depth [R, S] f64; reads [R, S] i64; state [R, S] uint8 (0 absent, 1 present below
+        min_copy, 2 present at or above); kernel_ms)."""
+        S = len(cluster)
+        cl = [np.ascontiguousarray(a, dtype=np.uint32) for a in cluster]
+        cp = [np.ascontiguousarray(a, dtype=np.float64) for a in copy]
+        dp = [np.ascontiguousarray(a, dtype=np.float64) for a in depth]
+        rd = [np.ascontiguousarray(a, dtype=np.int64) for a in reads]
+        n = np.array([a.shape[0] for a in cl], np.int64)
+        assert all(cp[k].shape[0] == n[k] and dp[k].shape[0] == n[k] and rd[k].shape[0] == n[k] for k in range(S))
+        ptrs = lambda arrs: (C.c_void_p * S)(*[a.ctypes.data if a.size else None for a in arrs])
+        cap = int(min(int(n_clusters), int(n[0]))) if S else 0
+        out = dict(rows=np.empty(cap, np.uint32), copy=np.empty((cap, S), np.float64), depth=np.empty((cap, S), np.float64),
+                   reads=np.empty((cap, S), np.int64), state=np.empty((cap, S), np.uint8))
+        R, ms = C.c_int64(0), C.c_float(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        keep = (cl, cp, dp, rd)     # (alive during the call)
+        st = self._lib.midas_genes_merge(self._h, S, p(n), ptrs(cl), ptrs(cp), ptrs(dp), ptrs(rd), int(n_clusters), float(min_copy),
+                                         int(group_samples), cap, C.byref(R), p(out['rows']), p(out['copy']), p(out['depth']),
+                                         p(out['reads']), p(out['state']), C.byref(ms))
+        del keep
+        self._check(st)
+        r = int(R.value)
+        res = {k: v[:r] for k, v in out.items()}
+        res['kernel_ms'] = float(ms.value)
+        return res
 
     def batch(self, contigs: ContigTable, reads: ReadsSoA) -> "Batch":
         return Batch(self, contigs, reads)

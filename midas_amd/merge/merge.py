@@ -1,10 +1,10 @@
 """Which (species, sample) pairs a merge works on -- the selection rules of /root/reference/midas/merge/merge.py,
-restricted to what `merge_midas.py snps` needs.  Pure host logic, no device work.
+restricted to what `merge_midas.py snps` and `merge_midas.py genes` need.  Pure host logic, no device work.
 
 Rules kept (reference line numbers in brackets):
-  * a sample directory counts only if <dir>/snps/summary.txt exists [59-86];
+  * a sample directory counts only if <dir>/<snps|genes>/summary.txt exists [59-86];
   * a pair is dropped when --species_id excludes it, when the species already has --max_samples samples, when the
-    sample's mean_coverage < --sample_depth or its fraction_covered < --fract_cov [104-119];
+    sample's mean_coverage < --sample_depth or (snps only) its fraction_covered < --fract_cov [104-119];
   * species are ranked by number of retained samples (stable), those under --min_samples are dropped and at most
     --max_species are kept [121-156];
   * species_info.txt must carry species_id + rep_genome and genome_info.txt genome_id [10-16, 88-102].
@@ -15,6 +15,8 @@ import os
 
 SUMMARY_FIELDS = ('genome_length', 'covered_bases', 'fraction_covered', 'mean_coverage', 'aligned_reads',
                   'mapped_reads')
+GENES_SUMMARY_FIELDS = ('pangenome_size', 'covered_genes', 'fraction_covered', 'mean_coverage', 'marker_coverage',
+                        'aligned_reads', 'mapped_reads')
 
 
 def _keyed_table(path, key):
@@ -54,12 +56,14 @@ class Species:
         self.sample_depth = [float(s.info[self.id]['mean_coverage']) for s in self.samples]
 
     def write_sample_info(self, dtype, outdir):
-        """<outdir>/<species>/<dtype>_summary.txt: the per-sample summary rows, copied through as text."""
+        """<outdir>/<species>/<dtype>_summary.txt: the per-sample summary rows, copied through as text (the field list
+        of the data type, merge.py:23-37)."""
+        fields = SUMMARY_FIELDS if dtype == 'snps' else GENES_SUMMARY_FIELDS
         with open(os.path.join(outdir, self.id, '%s_summary.txt' % dtype), 'w') as out:
-            out.write('\t'.join(('sample_id',) + SUMMARY_FIELDS) + '\n')
+            out.write('\t'.join(('sample_id',) + fields) + '\n')
             for s in self.samples:
                 row = s.info[self.id]
-                out.write('\t'.join([s.id] + [str(row[f]) for f in SUMMARY_FIELDS]) + '\n')
+                out.write('\t'.join([s.id] + [str(row[f]) for f in fields]) + '\n')
 
 
 def init_samples(indirs, data_type):

@@ -1,10 +1,11 @@
 #!/usr/bin/env python
-"""merge_midas.py snps -- multi-sample SNP calling with the per-site arithmetic on MI355X.
+"""merge_midas.py snps | genes -- multi-sample merges with the per-site / per-gene-cluster arithmetic on MI355X.
 
-Drop-in for the `snps` command of the reference's scripts/merge_midas.py: same positional arguments, option names,
-defaults, presets and output files (<outdir>/<species>/snps_{info,freq,depth,summary}.txt, readme.txt).  The option
-semantics are the reference's (scripts/merge_midas.py:148-281); `species` and `genes` merges are not part of this
-build.  Under torch.distributed.run the species are dealt to the ranks (one GPU each).
+Drop-in for the `snps` and `genes` commands of the reference's scripts/merge_midas.py: same positional arguments, option
+names, defaults, presets and output files (<outdir>/<species>/snps_{info,freq,depth,summary}.txt, readme.txt;
+<outdir>/<species>/genes_{presabs,copynum,depth,reads,summary}.txt, readme.txt).  The option semantics are the
+reference's (scripts/merge_midas.py:84-146, 148-281); the `species` merge is not part of this build.  Under
+torch.distributed.run the species are dealt to the ranks (one GPU each).
 """
 
 import argparse
@@ -68,12 +69,14 @@ def get_program():
     if word in ('-h', '--help'):
         print("merge_midas.py <command> [options]\n\n"
               "  snps   pool the per-sample allele counts of a species, call alleles and SNP types, write the\n"
-              "         freq/depth/info matrices (site arithmetic on the MI355X); `merge_midas.py snps -h` for options\n\n"
-              "species and genes merges are not part of this build.")
+              "         freq/depth/info matrices (site arithmetic on the MI355X); `merge_midas.py snps -h` for options\n"
+              "  genes  merge the per-sample gene tables of a species over its gene clusters, write the presence/absence,\n"
+              "         copy-number, depth and read matrices (cluster sums on the MI355X); `merge_midas.py genes -h` for options\n\n"
+              "the species merge is not part of this build.")
         sys.exit(0)
-    if word in ('species', 'genes'):
-        die("'%s' is not part of this build (only the snps path is)" % word)
-    if word != 'snps':
+    if word == 'species':
+        die("'%s' is not part of this build (only the snps and genes paths are)" % word)
+    if word not in ('snps', 'genes'):
         die("Unrecognized command: '%s'" % word)
     return word
 
@@ -105,8 +108,42 @@ def snps_arguments():
     return add_snp_presets(vars(parser.parse_args()))
 
 
+GENES_OPTION_GROUPS = [
+    ("Samples", OPTION_GROUPS[0][1]),
+    ("Species", OPTION_GROUPS[2][1]),
+    ("Sample filters, per species", [
+        (['--sample_depth'], dict(type=float, default=1.0, metavar='FLOAT',
+                                  help="minimum mean_coverage (read depth over the genes with reads) of the sample (1.0)")),
+        (['--max_samples'], dict(type=int, metavar='INT', help="use at most this many samples")),
+    ]),
+    ("Quantification", [
+        (['--cluster_pid'], dict(type=str, dest='cluster_pid', default='95', choices=['75', '80', '85', '90', '95', '99'],
+                                 help="the pangenome's gene clusters at this %% identity: 75 80 85 90 95 99 (95)")),
+        (['--min_copy'], dict(type=float, default=0.35, metavar='FLOAT',
+                              help="a cluster is present (1) at or above this copy number, absent (0) below (0.35)")),
+    ]),
+]
+
+
+def genes_arguments():
+    parser = argparse.ArgumentParser(
+        prog='merge_midas.py genes', formatter_class=argparse.RawTextHelpFormatter,
+        description="Gene-cluster presence/absence, copy-number, depth and read matrices over the samples of each species.",
+        epilog="examples:\n"
+               "  merge_midas.py genes OUT -i sample_1,sample_2 -t list\n"
+               "  merge_midas.py genes OUT -i /path/to/samples -t dir --sample_depth 5.0 --min_copy 0.1")
+    parser.add_argument('program', help=argparse.SUPPRESS)
+    parser.add_argument('outdir', help="output directory; one sub-directory per species")
+    parser.add_argument('--threads', type=int, default=1, metavar='INT', help="CPU threads for reading and writing tables (1)")
+    for title, options in GENES_OPTION_GROUPS:
+        group = parser.add_argument_group(title)
+        for flags, kw in options:
+            group.add_argument(*flags, **kw)
+    return vars(parser.parse_args())
+
+
 def check_arguments(args):
-    """scripts/merge_midas.py:283-332, the parts that apply to snps."""
+    """scripts/merge_midas.py:283-332, the parts that apply to snps and genes."""
     os.makedirs(args['outdir'], exist_ok=True)
     if args['db'] is None:
         die("No reference database specified\nUse the flag -d to specify a database,\n"
@@ -132,6 +169,11 @@ def check_arguments(args):
         for d in args['indirs']:      # only listed directories are checked (scripts/merge_midas.py:320-331)
             if not os.path.isdir(d):
                 die("Specified input directory '%s' does not exist" % d)
+    if args.get('program') == 'genes':
+        for name in ('min_copy', 'sample_depth', 'max_samples'):       # scripts/merge_midas.py:295-298
+            if args.get(name) and args[name] < 0:
+                die("--%s cannot be a negative value" % name)
+        return
     if args['site_depth'] < 0:
         die("--site_depth must be >=0")
     for name in ('allele_freq', 'fract_cov', 'site_prev'):      # scripts/merge_midas.py:291-293
@@ -142,8 +184,12 @@ def check_arguments(args):
 
 
 if __name__ == '__main__':
-    get_program()
-    args = snps_arguments()
+    program = get_program()
+    args = snps_arguments() if program == 'snps' else genes_arguments()
     check_arguments(args)
-    from midas_amd.merge import snps
-    snps.run_pipeline(args)
+    if program == 'snps':
+        from midas_amd.merge import snps
+        snps.run_pipeline(args)
+    else:
+        from midas_amd.merge import genes
+        genes.run_pipeline(args)
