@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "dense_bases.h"
 
 namespace midas {
 
@@ -189,7 +190,7 @@ __global__ __launch_bounds__(256) void bam_columns_kernel(BamColumnsParams p) {
   p.cigar_off[i + 1] = n_cig;
   p.seq_off[i + 1] = (l + 1u) / 2u;
   p.qual_off[i + 1] = l;
-  if (p.unit_off) p.unit_off[i + 1] = (4ll * n_cig + (l + 1u) / 2u + (long long)l + 7ll) >> 3;     // (layout.h direct_payload_units, any l)
+  if (p.unit_off) p.unit_off[i + 1] = (4ll * n_cig + 4ll + (long long)l + 7ll) >> 3;     // (layout.h direct_payload_units, any l)
   int32_t nm = -1;
   // (a chained walk checks block_size only: a record whose refID names no reference is caught here, as the host walk's
   // plausible_record() catches it -- the host folds per-reference tables by it)
@@ -269,11 +270,12 @@ __global__ __launch_bounds__(kScanBlock) void bam_scan_apply_kernel(long long* a
 }
 
 // ---- the records in the pileup kernel's own layout (layout.h DirectRec + payload), straight from the inflated stream ----------
-// A record's CIGAR ops, 4-bit SEQ and QUAL are ONE run of its bytes (SAM spec 4.2: ... read_name, cigar, seq, qual, aux) -- and
-// that run, in that order, is the direct layout's payload of a read.  HALF a wavefront per record copies it ONCE to the 8-byte
-// unit the scan gave it (eight bytes a lane and load, any alignment; the tail to the next unit zeroed) and writes the read's
-// 16-byte record.  What pysam.AlignmentFile + the iteration of midas/run/snps.py:186-199 hand to count_coverage, as the kernel
-// that replaces count_coverage reads it: nothing is cut into columns and gathered back.
+// A record's CIGAR ops, 4-bit SEQ and QUAL follow each other (SAM spec 4.2: ... read_name, cigar, seq, qual, aux).  HALF a
+// wavefront per record copies the ops to the 8-byte unit the scan gave the read, turns SEQ + QUAL into the sum word and one
+// byte a base behind them (dense_bases.h: eight bases a lane, the tail to the next unit zeroed) and writes the read's 16-byte
+// record; a read the bytes cannot give back exactly is copied raw into the side buffer when the caller keeps no inflated
+// stream (side_copy).  What pysam.AlignmentFile + the iteration of midas/run/snps.py:186-199 hand to count_coverage, as the
+// kernel that replaces count_coverage reads it: nothing is cut into columns and gathered back.
 typedef unsigned long long u64_a1 __attribute__((aligned(1)));
 __global__ __launch_bounds__(256) void bam_direct_kernel(BamDirectParams p) {
   const uint32_t lane = threadIdx.x & 63u, sub = lane >> 5, sl = lane & 31u;
@@ -284,12 +286,15 @@ __global__ __launch_bounds__(256) void bam_direct_kernel(BamDirectParams p) {
     const uint32_t n_cig = rd16(r + 16);
     const uint32_t l = rd32(r + 20);
     const uint8_t* src = r + 36 + l_name;
-    const unsigned long long used = 4ull * n_cig + (l + 1u) / 2u + (unsigned long long)l;
     const unsigned long long u0 = (unsigned long long)p.unit_off[i], room = ((unsigned long long)p.unit_off[i + 1] - u0) << 3;
     uint8_t* dst = p.payload + (u0 << 3);
-    const unsigned long long whole = used & ~7ull;
-    for (unsigned long long k = (unsigned long long)sl * 8ull; k < whole; k += 256ull) *reinterpret_cast<u64_a1*>(dst + k) = *reinterpret_cast<const u64_a1*>(src + k);
-    if (sl < 8u && whole + sl < room) dst[whole + sl] = whole + sl < used ? src[whole + sl] : (uint8_t)0;      // the last unit: bytes, then zeros
+    const uint32_t nc4 = 4u * n_cig;
+    for (uint32_t k = sl * 8u; k + 8u <= nc4; k += 256u) *reinterpret_cast<u64_a1*>(dst + k) = *reinterpret_cast<const u64_a1*>(src + k);
+    if (sl == 0u && (n_cig & 1u)) *reinterpret_cast<uint32_t*>(dst + nc4 - 4u) = rd32(src + nc4 - 4u);
+    const uint8_t* seq = src + nc4;
+    const uint8_t* qual = seq + (l + 1u) / 2u;
+    const bool exc = dense::encode<32>(dst + nc4, (uint32_t)(room - nc4), seq, qual, l, (int)sl, p.side);
+    if (exc && p.side_copy) dense::side_copy<32>(p.side, (unsigned long long)(p.read_base + i), seq, qual, l, (int)sl);
     if (sl == 0u) {
       const int32_t nm = p.nm[i];
       DirectRec rec;

@@ -34,6 +34,7 @@
 
 #include "kernels.h"
 #include "crc32.h"
+#include "dense_bases.h"
 
 namespace midas {
 namespace {
@@ -814,25 +815,45 @@ __global__ __launch_bounds__(256) void bam_payload_kernel(PayloadParams p) {
   const uint32_t lane = threadIdx.x & 63u, sub = lane >> 5, sl = lane & 31u;
   const long long slot = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + sub, n_slots = (long long)gridDim.x * 8;
   for (long long i = slot; i < p.n_records; i += n_slots) {
-    uint32_t n_cig, l;
-    const uint8_t* q;
-    if (p.drec) {        // out of the direct layout: the same run of bytes, found by the read's record
-      n_cig = (uint32_t)(p.cigar_off[i + 1] - p.cigar_off[i]);
-      l = (uint32_t)(p.qual_off[i + 1] - p.qual_off[i]);
-      q = p.stream + ((unsigned long long)p.drec[i].off8 << 3);
-    } else {
-      const uint8_t* r = p.stream + p.rec_off[i];
-      const uint32_t l_name = r[12];
-      n_cig = (uint32_t)r[16] | ((uint32_t)r[17] << 8);
-      l = (uint32_t)r[20] | ((uint32_t)r[21] << 8) | ((uint32_t)r[22] << 16) | ((uint32_t)r[23] << 24);
-      q = r + 36 + l_name;
+    if (p.drec) {        // out of the direct layout: the ops as they are, SEQ / QUAL decoded from the base bytes behind the sum word
+      const uint32_t n_cig = (uint32_t)(p.cigar_off[i + 1] - p.cigar_off[i]);
+      const uint32_t l = (uint32_t)(p.qual_off[i + 1] - p.qual_off[i]);
+      const uint8_t* q = p.stream + ((unsigned long long)p.drec[i].off8 << 3);
+      copy_run32(reinterpret_cast<uint8_t*>(p.cigar + p.cigar_off[i]), q, 4u * n_cig, sl);
+      dense::decode<32>(p.seq4 + p.seq_off[i], p.qual + p.qual_off[i], q + 4ull * n_cig + 4ull, l, (int)sl);
+      continue;
     }
+    const uint8_t* r = p.stream + p.rec_off[i];
+    const uint32_t l_name = r[12];
+    const uint32_t n_cig = (uint32_t)r[16] | ((uint32_t)r[17] << 8);
+    const uint32_t l = (uint32_t)r[20] | ((uint32_t)r[21] << 8) | ((uint32_t)r[22] << 16) | ((uint32_t)r[23] << 24);
+    const uint8_t* q = r + 36 + l_name;
     copy_run32(reinterpret_cast<uint8_t*>(p.cigar + p.cigar_off[i]), q, 4u * n_cig, sl);
     q += 4ull * n_cig;
     const uint32_t ns = (l + 1u) / 2u;
     copy_run32(p.seq4 + p.seq_off[i], q, ns, sl);
     q += ns;
     copy_run32(p.qual + p.qual_off[i], q, l, sl);
+  }
+}
+
+// behind the decode of a direct layout's base bytes: the side buffer's raw SEQ / QUAL of the exceptional reads over what the
+// decode wrote for them (half a wavefront per entry; entries of reads outside [side_first, side_first + n_records) are not this cut's)
+__global__ __launch_bounds__(256) void dense_side_apply_kernel(PayloadParams p) {
+  const uint32_t lane = threadIdx.x & 63u, sub = lane >> 5, sl = lane & 31u;
+  const long long slot = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + sub, n_slots = (long long)gridDim.x * 8;
+  const DenseSide* side = p.side;
+  const unsigned long long used = side->bump >> kDenseSideEntryShift;
+  const long long n_ent = (long long)(used < side->cap_entries ? used : side->cap_entries);
+  const DenseSideEntry* ent = reinterpret_cast<const DenseSideEntry*>(side + 1);
+  const uint8_t* data = reinterpret_cast<const uint8_t*>(ent + side->cap_entries);
+  for (long long e = slot; e < n_ent; e += n_slots) {
+    const DenseSideEntry x = ent[e];
+    const long long i = (long long)x.read - p.side_first;
+    if (i < 0 || i >= p.n_records) continue;
+    const uint32_t l = (uint32_t)(p.qual_off[i + 1] - p.qual_off[i]), ns = (l + 1u) / 2u;
+    copy_run32(p.seq4 + p.seq_off[i], data + x.off, ns, sl);
+    copy_run32(p.qual + p.qual_off[i], data + x.off + ns, l, sl);
   }
 }
 
@@ -871,6 +892,7 @@ hipError_t launch_bam_payload(const PayloadParams& p, int grid_blocks, hipStream
   const long long cap = (long long)grid_blocks * 16;
   if (g > cap) g = cap;
   hipLaunchKernelGGL(bam_payload_kernel, dim3((unsigned)g), dim3(256), 0, s, p);
+  if (p.drec && p.side) hipLaunchKernelGGL(dense_side_apply_kernel, dim3((unsigned)(grid_blocks > 0 ? grid_blocks : 1)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

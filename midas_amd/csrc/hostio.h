@@ -71,6 +71,8 @@ struct ResidentReads {
   int64_t *seq_off = nullptr, *qual_off = nullptr, *cigar_off = nullptr, *unit_off = nullptr;
   const uint8_t* stream = nullptr; const uint64_t* rec_off = nullptr;
   int64_t payload_units = 0;
+  const void* side = nullptr;   // (a streamed decode) layout.h DenseSide: the raw SEQ / QUAL of the reads the base bytes cannot give back
+  uint32_t dense_flags = 0;     // layout.h kDense* flags the producer raised (kDenseClampedQual)
 };
 struct DeviceDecodeResult {
   int64_t n_records = 0, seq_bytes = 0, qual_bytes = 0, n_cigar = 0;

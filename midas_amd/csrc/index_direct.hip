@@ -18,6 +18,7 @@
 //                          and how many reads are not of the one- or two-segment forms the pileup kernel settles in registers.
 // No sort, no payload, no per-read record: the pileup kernel reads pos / l_seq / NM / mapq / the CSR offsets / SEQ / QUAL / CIGAR
 // where they are.
+#include "dense_bases.h"
 #include "direct_common.h"
 
 namespace midas {
@@ -291,8 +292,8 @@ __global__ __launch_bounds__(kIdxBlock) void direct_facts_kernel(DirectIndexPara
 }
 
 // ---- once per batch: the direct layout (layout.h DirectRec + payload) ------------------------------------------------------
-// A read's 41 bytes of columns in seven arrays become ONE 16-byte record and its CIGAR / SEQ / QUAL bytes ONE run of the
-// payload (BAM's own order), so that the pileup kernel finds everything a lane needs behind one dwordx4 load.  Every read was
+// A read's 41 bytes of columns in seven arrays become ONE 16-byte record and its CIGAR, quality sum and base bytes ONE run
+// of the payload (layout.h), so that the pileup kernel finds everything a lane needs behind one dwordx4 load.  Every read was
 // validated by the facts pass before this runs.  Three launches: payload units per workgroup's reads, their scan (one
 // workgroup), records + gather.
 __device__ __forceinline__ uint32_t read_units(const DirectLayoutParams& p, long long i) {
@@ -397,14 +398,11 @@ __global__ __launch_bounds__(kIdxBlock) void direct_layout_fill_kernel(DirectLay
   for (long long i = lo + grp; i < hi; i += kIdxBlock / 16) {
     const uint32_t l = (uint32_t)p.l_seq[i];
     const long long co = p.cigar_off[i];
-    const uint32_t nc4 = 4u * (uint32_t)(p.cigar_off[i + 1] - co), sl = (l + 1u) >> 1;
+    const uint32_t nc = (uint32_t)(p.cigar_off[i + 1] - co);
     uint8_t* dst = p.payload + 8ull * (base + s_off[(int)(i - lo)]);
-    group_copy(dst, reinterpret_cast<const uint8_t*>(p.cigar + co), nc4, gl);
-    group_copy(dst + nc4, p.seq4 + p.seq_off[i], sl, gl);
-    group_copy(dst + nc4 + sl, p.qual + p.qual_off[i], l, gl);
-    const uint32_t used = nc4 + sl + l, room = (used + 7u) & ~7u;
-    if (gl == 0)
-      for (uint32_t j = used; j < room; ++j) dst[j] = 0;
+    group_copy(dst, reinterpret_cast<const uint8_t*>(p.cigar + co), 4u * nc, gl);
+    // (the caller's columns stay on the device beside the layout: no side copy of an exceptional read is needed here)
+    (void)dense::encode<16>(dst + 4u * nc, 8u * direct_payload_units(l, nc) - 4u * nc, p.seq4 + p.seq_off[i], p.qual + p.qual_off[i], l, gl, p.side);
   }
 }
 

@@ -232,11 +232,12 @@ struct DirectLayoutParams {
   unsigned long long* block_units;                // [direct_index_blocks(n_reads) + 1] payload units per workgroup's reads, then their exclusive scan
   DirectRec* rec;                                 // [n_reads + 1] (the last one a sentinel: off8 = all units)
   uint8_t* payload;
+  DenseSide* side;                                // its flags (kDenseClampedQual); no side copies
 };
 
 struct DirectParams {
   const DirectRec* rec;                           // [n_reads + 1]
-  const uint8_t* payload;                         // per read [cigar][seq][qual], 8-byte aligned (64 bytes of slack behind the last)
+  const uint8_t* payload;                         // per read [cigar][sum q][base bytes], 8-byte aligned (64 bytes of slack behind the last)
   // (the caller's arrays: read by developer variants of the kernel only)
   const int32_t* pos; const uint8_t* mapq; const int32_t* nm; const int32_t* l_seq;
   const int64_t* seq_off; const int64_t* qual_off; const int64_t* cigar_off;
@@ -313,6 +314,10 @@ struct PayloadParams {
   // (a streamed decode keeps no inflated stream: the records' runs are cut out of the DIRECT layout then -- `stream` is its payload,
   // drec[i].off8 where record i's [cigar][seq][qual] run starts in it, the lengths from the offset columns)
   const DirectRec* drec = nullptr;
+  // (with drec: the exact copies of the exceptional reads, applied behind the decode of the base bytes -- layout.h DenseSide;
+  // an entry's read index less side_first is the record's index here)
+  const DenseSide* side = nullptr;
+  long long side_first = 0;
 };
 hipError_t launch_bam_payload(const PayloadParams& p, int grid_blocks, hipStream_t s);    // 1: decode, 2: resolve the matches
 
@@ -353,6 +358,9 @@ struct BamDirectParams {
   const uint8_t* stream; const unsigned long long* rec_off; long long n_records;
   const int32_t* pos; const int32_t* nm; const long long* unit_off;
   DirectRec* rec; uint8_t* payload;
+  DenseSide* side;                                  // flags; with side_copy the exceptional reads' raw SEQ / QUAL too
+  long long read_base;                              // index of record 0 in the layout (the side entries' read numbers)
+  int side_copy;
 };
 hipError_t launch_bam_direct(const BamDirectParams& p, int grid_blocks, hipStream_t s);
 hipError_t launch_bam_walk(const BamWalkParams& p, const long long* list, long long n_list, hipStream_t s);

@@ -111,10 +111,12 @@ __host__ __device__ inline uint32_t blob_bytes(uint32_t l_seq, uint32_t n_cigar_
 }
 
 // ---- direct path (index_direct.hip + pileup_direct.hip) ------------------------------------------------------------------
-// One 16-byte record per read -- the 16 fixed bytes SURVEY 8(d) counts per read -- and the read's variable part in BAM order,
-// `[cigar 4 * n_cigar][seq ceil(l / 2)][qual l]`, padded to 8 bytes, reads back to back in input order: ONE dwordx4 load
-// gives a lane everything it needs to find its bases.  Built once per batch from the caller's arrays (direct_layout_kernel);
-// a re-encoding of columns and a gather of bytes, nothing is decided in it (no CIGAR shape, no filter outcome).
+// One 16-byte record per read -- the 16 fixed bytes SURVEY 8(d) counts per read -- and the read's variable part,
+// `[cigar 4 * n_cigar][sum q 4][base byte l]`, padded to 8 bytes, reads back to back in input order: ONE dwordx4 load gives a
+// lane everything it needs to find its bases.  The CIGAR is BAM's own; SEQ + QUAL (1.5 bytes a base) become ONE byte a base
+// (dense_byte) and the sum of the read's true qualities (the readq filter's whole input).  Built once per batch from the
+// caller's arrays (direct_layout_fill_kernel) or from the inflated BAM (bam_direct_kernel); nothing is decided in it (no CIGAR
+// shape, no filter outcome, no threshold).
 struct DirectRec {          // 16 bytes, 16-byte aligned
   int32_t pos;              // BAM pos (0-based leftmost)
   uint32_t l_nc;            // l_seq (bits 0-15) | n_cigar << 16
@@ -123,9 +125,70 @@ struct DirectRec {          // 16 bytes, 16-byte aligned
 };
 static_assert(sizeof(DirectRec) == 16, "DirectRec must be 16 bytes");
 __host__ __device__ inline uint32_t direct_payload_units(uint32_t l_seq, uint32_t n_cigar) {     // 8-byte units of one read
-  return (4u * n_cigar + ((l_seq + 1u) >> 1) + l_seq + 7u) >> 3;
+  return (4u * n_cigar + 4u + l_seq + 7u) >> 3;
 }
 constexpr unsigned long long kMaxDirectPayloadUnits = 0xFFFFFFFFull;    // 32 GiB per batch
+
+// The base byte: A, C, G, T (SEQ nibbles 1, 2, 4, 8) -> ((min(q, 50) + 13) << 2) | code with code A=0 C=1 G=2 T=3 (>= 52);
+// any other nibble (N, IUPAC, '=') -> min(q, 51) (<= 51: never counts).  Zero is "no base" (what the kernel's masks write).
+// A base counts iff byte >= dense_threshold(baseq): exact (q >= baseq on A/C/G/T only) for every baseq <= 50, and for a
+// larger baseq on a batch none of whose A/C/G/T qualities was clamped (kDenseClampedQual; else midas_snps_batch_run sends
+// that run to the long path).  The counter offset of a counted base is (byte & 3) << 2.
+constexpr uint32_t kDenseMaxQual = 50;
+constexpr uint32_t kDenseMaxOtherQual = 51;
+__host__ __device__ inline uint32_t dense_code(uint32_t nib) {       // 0..3 for A, C, G, T; 4 for anything else
+  return nib == 1u ? 0u : (nib == 2u ? 1u : (nib == 4u ? 2u : (nib == 8u ? 3u : 4u)));
+}
+__host__ __device__ inline uint8_t dense_byte(uint32_t nib, uint32_t q) {
+  const uint32_t c = dense_code(nib);
+  if (c < 4u) return (uint8_t)(((q > kDenseMaxQual ? kDenseMaxQual : q) + 13u) << 2 | c);
+  return (uint8_t)(q > kDenseMaxOtherQual ? kDenseMaxOtherQual : q);
+}
+__host__ __device__ inline uint32_t dense_threshold(int32_t baseq) {
+  return baseq > (int32_t)kDenseMaxQual ? 256u : ((uint32_t)(baseq < 0 ? 0 : baseq) + 13u) << 2;
+}
+// decode of a byte: what a read that is not exceptional (dense_exact) held there
+__host__ __device__ inline uint32_t dense_nibble(uint32_t b) { return b >= 52u ? 1u << (b & 3u) : 15u; }
+__host__ __device__ inline uint32_t dense_qual(uint32_t b) { return b >= 52u ? (b >> 2) - 13u : b; }
+// the byte gives the base back exactly; a read with a base for which it does not, or with a nonzero pad nibble (odd l_seq), is
+// EXCEPTIONAL: a producer that must keep the read lossless copies its raw SEQ + QUAL into the side buffer (DenseSide)
+__host__ __device__ inline bool dense_exact(uint32_t nib, uint32_t q) {
+  return dense_code(nib) < 4u ? q <= kDenseMaxQual : (nib == 15u && q <= kDenseMaxOtherQual);
+}
+// the sum word behind the CIGAR: the sum of the read's true qualities (< 2^24 for l_seq < 2^16), bit 31 = QUAL absent (qual[0] == 0xFF)
+constexpr uint32_t kDenseQualAbsent = 0x80000000u;
+
+// The side buffer of the producers: a 32-byte header, `cap_entries` entries, `cap_bytes` of data.  An exceptional read reserves
+// an entry and up8(ceil(l / 2) + l) data bytes with ONE atomicAdd on `bump` ((entries << 32) | 8-byte units) and stores its raw
+// [seq][qual] there; a reservation beyond either capacity raises kDenseSideOverflow and stores nothing (the host retries with
+// room for the whole group).  Whatever turns the layout back into columns decodes the bytes, then applies the entries.  The
+// pileup kernel never reads it.  The producers also raise kDenseClampedQual (no side copy needed for that).
+struct DenseSide {
+  unsigned long long bump;
+  uint32_t flags;
+  uint32_t cap_entries;
+  unsigned long long cap_bytes;
+  unsigned long long pad;
+};
+static_assert(sizeof(DenseSide) == 32, "DenseSide must be 32 bytes");
+struct DenseSideEntry { unsigned long long read, off; };       // the read's index in the layout, its data's offset
+constexpr uint32_t kDenseClampedQual = 1;      // an A/C/G/T quality above kDenseMaxQual (0xFF of an absent QUAL included)
+constexpr uint32_t kDenseSideOverflow = 2;     // an exceptional read found no room
+constexpr int kDenseSideEntryShift = 32;
+// Both fields of `bump` are 32 bits: a launch may only run when neither can pass 2^32 - 1 even if every one of its reads
+// reserves (the host checks dense_side_fits in front of it), so no reservation ever carries out of its field.
+constexpr unsigned long long kDenseSideMaxField = 0xFFFFFFFFull;
+__host__ __device__ inline bool dense_side_fits(unsigned long long entries, unsigned long long units) {
+  return entries <= kDenseSideMaxField && units <= kDenseSideMaxField;
+}
+__host__ __device__ inline DenseSideEntry* dense_side_entries(DenseSide* s) { return reinterpret_cast<DenseSideEntry*>(s + 1); }
+__host__ __device__ inline uint8_t* dense_side_data(DenseSide* s) {
+  return reinterpret_cast<uint8_t*>(dense_side_entries(s) + s->cap_entries);
+}
+__host__ __device__ inline unsigned long long dense_side_bytes(uint32_t cap_entries, unsigned long long cap_bytes) {
+  return sizeof(DenseSide) + (unsigned long long)cap_entries * sizeof(DenseSideEntry) + cap_bytes;
+}
+__host__ __device__ inline unsigned long long dense_side_room(uint32_t l_seq) { return ((l_seq + 1ull) / 2ull + l_seq + 7ull) & ~7ull; }
 
 // Error word written by the kernels: (read_index << 8) | kind, reduced with atomicMin.
 constexpr unsigned long long kNoError = ~0ull;

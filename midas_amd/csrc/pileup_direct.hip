@@ -1,6 +1,7 @@
-// gfx950 (CDNA4) pileup kernel of the MIDAS SNP path that reads the BAM's own bytes: per read ONE 16-byte record (pos, l_seq,
-// n_cigar, NM, mapq, payload offset -- layout.h DirectRec) and its CIGAR / 4-bit SEQ / QUAL bytes as BAM lays them out, one
-// run per read -- nothing decoded, sorted or decided beforehand, ONE visit per read.  Integer counting: no MFMA.
+// gfx950 (CDNA4) pileup kernel of the MIDAS SNP path that reads the reads in input order: per read ONE 16-byte record (pos,
+// l_seq, n_cigar, NM, mapq, payload offset -- layout.h DirectRec) and its payload -- BAM's CIGAR, the sum of its qualities and
+// ONE byte a base (layout.h dense_byte) -- one run per read: nothing sorted or decided beforehand, ONE visit per read.
+// Integer counting: no MFMA.
 //
 // Reference semantics implemented here (citations into /root/reference):
 //   keep_read                       midas/run/snps.py:141-162  (query_alignment_sequence :145, np.mean(query_qualities) :151)
@@ -17,27 +18,22 @@
 // can touch the tile -- the input is position-sorted, so that is a contiguous run of the read arrays.  It is dealt to the
 // workgroup's waves as wave-iterations of floor(64 / lanes per read) reads.
 //
-// Lane mapping.  A lane owns LB (30 or 32) consecutive bases of a read's STORED query: two 16-byte loads of QUAL, one of
-// 4-bit SEQ (LB is even, so a lane's bases start on a byte).  A read of l_seq bases takes ceil(l_seq / LB) adjacent lanes
+// Lane mapping.  A lane owns LB (30 or 32) consecutive bases of a read's STORED query: two 16-byte loads of base bytes.  A read of l_seq bases takes ceil(l_seq / LB) adjacent lanes
 // (5 for 150 bp).  Loads are issued two iterations (the read's record: one dwordx4) and one iteration (bases + the first four
-// CIGAR ops: four dwordx4 off ONE scalar base per wave-iteration -- the payload of the iteration's first read -- plus a 32-bit
-// lane offset) ahead of their use; none of them sits in a branch.
+// CIGAR ops + the quality sum: three dwordx4 and a dword off ONE scalar base per wave-iteration -- the payload of the
+// iteration's first read -- plus a 32-bit lane offset) ahead of their use; none of them sits in a branch.
 //
 // Per read.  The lanes of a read decide in registers what its CIGAR is: ONE or TWO gap-free match runs (direct_common.h
 // ReadShape: clips, at most one insertion / deletion / skip -- what an aligner writes for nearly every read) are tallied
 // straight from the shape, the lane that holds the indel in a second masked pass; anything else (several indels, pads, odd
 // clips, no NM / SEQ, a start off the contig) is walked op by op where it lies, the slow path.
 //
-// Per base, from the raw bytes:  the 4-bit codes of eight bases (one dword) are split into their even and odd nibbles
-// (two masks), mapped to v_perm_b32 selectors by `(n + 7) ^ 8` -- A, C, G, T (1, 2, 4, 8) land on table slots 0, 1, 3, 7,
-// every other code on a slot or a selector constant that yields 0xFF -- and looked up twice: a THRESHOLD byte (baseq - 1
-// for A/C/G/T, 0xFF for anything else) and the byte offset of the base's counter.  Then per base one SDWA compare
-// `qual.byte > threshold.byte` into a lane mask (the byte selects of the two operands are independent, so the even / odd
-// order of the looked-up bytes costs nothing), one SDWA OR forming the LDS address, one returnless ds_add under the mask.
-// Clipping (soft clips, segment borders, tile edges, the read's tail) zeroes the 4-bit codes of the bases outside (code 0 is
-// no base: its threshold byte is 0xFF): two rows of a nibble-mask table from LDS per partial pass.
-// The read's mean quality is v_sad_u8 over the lane's bytes and a sum over the read's lanes; sum(q) < readq * l_seq is the
-// reference's np.mean(q) < readq exactly.
+// Per base: the counter offsets of four bases are `(word << 2) & 0x0C0C0C0C` (two ALU ops a word); then per base one SDWA OR
+// forming the LDS address, one SDWA compare `byte >= thr` (thr = layout.h dense_threshold(baseq), wave-uniform) into a lane
+// mask, one returnless ds_add under the mask.  N and the other non-A/C/G/T codes have bytes below every threshold.
+// Clipping (soft clips, segment borders, tile edges, the read's tail) zeroes the bytes outside: two rows of a byte-mask
+// table from LDS per group of a partial pass.
+// The read's mean quality: the sum stored behind its CIGAR; sum(q) < readq * l_seq is the reference's np.mean(q) < readq exactly.
 #include "direct_common.h"
 #include "pileup_common.h"
 
@@ -60,32 +56,33 @@ namespace {
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// Eight bases of one lane: q0 / q1 two words of four quality bytes (bases in order), the / tho threshold bytes and cde / cdo
-// counter offsets of the even / odd bases (byte i of an `e` word: base 2i, of an `o` word: base 2i + 1).
+// Eight bases of one lane: b0 / b1 two words of four base bytes (layout.h dense_byte, bases in order), thr the byte threshold
+// (dense_threshold, wave-uniform).  Per base one SDWA OR forming the LDS address of its counter ((byte & 3) << 2, two ALU ops a
+// word), one SDWA compare `byte >= thr` into a lane mask, one returnless ds_add under it.
 template <int OFF, int NB>
-__device__ __forceinline__ void tally_group(uint32_t q0, uint32_t q1, uint32_t the, uint32_t tho, uint32_t cde, uint32_t cdo,
-                                            uint32_t abase, uint32_t one) {
+__device__ __forceinline__ void tally_group(uint32_t b0, uint32_t b1, uint32_t thr, uint32_t abase, uint32_t one) {
   static_assert(NB == 8 || NB == 6, "a group holds 8 bases, or 6 at the end of a 30-base lane");
+  const uint32_t c0 = (b0 << 2) & 0x0C0C0C0Cu, c1 = (b1 << 2) & 0x0C0C0C0Cu;
   uint32_t t0, t1, t2, t3, t4, t5, t6, t7;
   unsigned long long m0, m1, m2, m3, m4, m5, m6, m7, save;
   if (NB == 8) {
     asm volatile(
-        "v_or_b32_sdwa %[t0], %[ab], %[ce] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-        "v_or_b32_sdwa %[t1], %[ab], %[co] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-        "v_or_b32_sdwa %[t2], %[ab], %[ce] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
-        "v_or_b32_sdwa %[t3], %[ab], %[co] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
-        "v_or_b32_sdwa %[t4], %[ab], %[ce] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-        "v_or_b32_sdwa %[t5], %[ab], %[co] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-        "v_or_b32_sdwa %[t6], %[ab], %[ce] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3\n\t"
-        "v_or_b32_sdwa %[t7], %[ab], %[co] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3\n\t"
-        "v_cmp_gt_u32_sdwa %[m0], %[q0], %[te] src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
-        "v_cmp_gt_u32_sdwa %[m1], %[q0], %[to] src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
-        "v_cmp_gt_u32_sdwa %[m2], %[q0], %[te] src0_sel:BYTE_2 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %[m3], %[q0], %[to] src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %[m4], %[q1], %[te] src0_sel:BYTE_0 src1_sel:BYTE_2\n\t"
-        "v_cmp_gt_u32_sdwa %[m5], %[q1], %[to] src0_sel:BYTE_1 src1_sel:BYTE_2\n\t"
-        "v_cmp_gt_u32_sdwa %[m6], %[q1], %[te] src0_sel:BYTE_2 src1_sel:BYTE_3\n\t"
-        "v_cmp_gt_u32_sdwa %[m7], %[q1], %[to] src0_sel:BYTE_3 src1_sel:BYTE_3\n\t"
+        "v_or_b32_sdwa %[t0], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
+        "v_or_b32_sdwa %[t1], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
+        "v_or_b32_sdwa %[t2], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
+        "v_or_b32_sdwa %[t3], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3\n\t"
+        "v_or_b32_sdwa %[t4], %[ab], %[c1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
+        "v_or_b32_sdwa %[t5], %[ab], %[c1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
+        "v_or_b32_sdwa %[t6], %[ab], %[c1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
+        "v_or_b32_sdwa %[t7], %[ab], %[c1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3\n\t"
+        "v_cmp_ge_u32_sdwa %[m0], %[b0], %[th] src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m1], %[b0], %[th] src0_sel:BYTE_1 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m2], %[b0], %[th] src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m3], %[b0], %[th] src0_sel:BYTE_3 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m4], %[b1], %[th] src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m5], %[b1], %[th] src0_sel:BYTE_1 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m6], %[b1], %[th] src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m7], %[b1], %[th] src0_sel:BYTE_3 src1_sel:DWORD\n\t"
         "s_mov_b64 %[sv], exec\n\t"
         "s_mov_b64 exec, %[m0]\n\t"
         "ds_add_u32 %[t0], %[one] offset:%[off]\n\t"
@@ -107,23 +104,22 @@ __device__ __forceinline__ void tally_group(uint32_t q0, uint32_t q1, uint32_t t
         : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [t6] "=&v"(t6),
           [t7] "=&v"(t7), [m0] "=&s"(m0), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3), [m4] "=&s"(m4), [m5] "=&s"(m5),
           [m6] "=&s"(m6), [m7] "=&s"(m7), [sv] "=&s"(save)
-        : [q0] "v"(q0), [q1] "v"(q1), [te] "v"(the), [to] "v"(tho), [ce] "v"(cde), [co] "v"(cdo), [ab] "v"(abase), [one] "v"(one),
-          [off] "n"(OFF)
+        : [b0] "v"(b0), [b1] "v"(b1), [th] "v"(thr), [c0] "v"(c0), [c1] "v"(c1), [ab] "v"(abase), [one] "v"(one), [off] "n"(OFF)
         : "memory");
   } else {
     asm volatile(
-        "v_or_b32_sdwa %[t0], %[ab], %[ce] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-        "v_or_b32_sdwa %[t1], %[ab], %[co] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
-        "v_or_b32_sdwa %[t2], %[ab], %[ce] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
-        "v_or_b32_sdwa %[t3], %[ab], %[co] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
-        "v_or_b32_sdwa %[t4], %[ab], %[ce] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-        "v_or_b32_sdwa %[t5], %[ab], %[co] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
-        "v_cmp_gt_u32_sdwa %[m0], %[q0], %[te] src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"
-        "v_cmp_gt_u32_sdwa %[m1], %[q0], %[to] src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"
-        "v_cmp_gt_u32_sdwa %[m2], %[q0], %[te] src0_sel:BYTE_2 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %[m3], %[q0], %[to] src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %[m4], %[q1], %[te] src0_sel:BYTE_0 src1_sel:BYTE_2\n\t"
-        "v_cmp_gt_u32_sdwa %[m5], %[q1], %[to] src0_sel:BYTE_1 src1_sel:BYTE_2\n\t"
+        "v_or_b32_sdwa %[t0], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
+        "v_or_b32_sdwa %[t1], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
+        "v_or_b32_sdwa %[t2], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2\n\t"
+        "v_or_b32_sdwa %[t3], %[ab], %[c0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3\n\t"
+        "v_or_b32_sdwa %[t4], %[ab], %[c1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n\t"
+        "v_or_b32_sdwa %[t5], %[ab], %[c1] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1\n\t"
+        "v_cmp_ge_u32_sdwa %[m0], %[b0], %[th] src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m1], %[b0], %[th] src0_sel:BYTE_1 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m2], %[b0], %[th] src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m3], %[b0], %[th] src0_sel:BYTE_3 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m4], %[b1], %[th] src0_sel:BYTE_0 src1_sel:DWORD\n\t"
+        "v_cmp_ge_u32_sdwa %[m5], %[b1], %[th] src0_sel:BYTE_1 src1_sel:DWORD\n\t"
         "s_mov_b64 %[sv], exec\n\t"
         "s_mov_b64 exec, %[m0]\n\t"
         "ds_add_u32 %[t0], %[one] offset:%[off]\n\t"
@@ -140,8 +136,7 @@ __device__ __forceinline__ void tally_group(uint32_t q0, uint32_t q1, uint32_t t
         "s_mov_b64 exec, %[sv]"
         : [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [t5] "=&v"(t5), [m0] "=&s"(m0),
           [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3), [m4] "=&s"(m4), [m5] "=&s"(m5), [sv] "=&s"(save)
-        : [q0] "v"(q0), [q1] "v"(q1), [te] "v"(the), [to] "v"(tho), [ce] "v"(cde), [co] "v"(cdo), [ab] "v"(abase), [one] "v"(one),
-          [off] "n"(OFF)
+        : [b0] "v"(b0), [b1] "v"(b1), [th] "v"(thr), [c0] "v"(c0), [c1] "v"(c1), [ab] "v"(abase), [one] "v"(one), [off] "n"(OFF)
         : "memory");
   }
 }
@@ -166,9 +161,7 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
   // OV: sites behind the tile's last that the tallies also hold (see "chunks" below); kDirectOverhangLong for batches of longer reads
   static_assert(OV <= TILE, "the overhang is moved by the write-out's first rounds");
   __shared__ __attribute__((aligned(16))) uint32_t lds[4 * (TILE + OV)];
-  __shared__ __attribute__((aligned(16))) uint32_t s_khi[33 * 4];   // [h][w]: 0xF in the nibbles of the bases j <  h of a lane's four SEQ words
-  __shared__ __attribute__((aligned(16))) uint32_t s_klo[33 * 4];   // [l][w]: 0xF in the nibbles of the bases j >= l
-  __shared__ uint32_t s_qsum[NWAVES * 64];                           // per wave and read slot: sum of a read's quality bytes
+  __shared__ __attribute__((aligned(16))) uint32_t s_kb[33 * 8];    // [h][w]: 0xFF in the bytes of the bases j < h of a lane's eight words
   __shared__ unsigned long long s_stats[MIDAS_STATS];
   __shared__ uint32_t s_next_ticket;
   // [min_match table_len][min_align table_len]; 16-bit entries in the long-overhang instantiation (its reads are <= 288 bases, the
@@ -219,19 +212,13 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
       s_tables[i] = (table_t)p.filt->min_match[i];
       s_tables[p.table_len + i] = (table_t)p.filt->min_align[i];
     }
-    for (int i = tid; i < 33 * 4; i += kDirectBlock) {
-      const int h = i >> 2, wd = i & 3;
-      uint32_t kh = 0, kl = 0;
-      for (int k = 0; k < 8; ++k) {
-        const int j = 8 * wd + k;                              // base k of word wd: byte k / 2, the HIGH nibble when k is even
-        const uint32_t nib = 0xFu << (8 * (k >> 1) + ((k & 1) ? 0 : 4));
-        if (j < h) kh |= nib;
-        if (j >= h) kl |= nib;
-      }
-      s_khi[i] = kh;
-      s_klo[i] = kl;
+    for (int i = tid; i < 33 * 8; i += kDirectBlock) {
+      const int h = i >> 3, wd = i & 7;
+      uint32_t kb = 0;
+      for (int k = 0; k < 4; ++k)
+        if (4 * wd + k < h) kb |= 0xFFu << (8 * k);
+      s_kb[i] = kb;
     }
-    s_qsum[tid] = 0u;
     if (tid < MIDAS_STATS) s_stats[tid] = 0ull;
   }
 
@@ -241,11 +228,8 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
   const int c = lane - g * lpr;
   const int q0 = c * LB;                           // first base of the lane in the read's stored query
   const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)lds;
-  const uint32_t qsum_addr = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)(s_qsum + wave * 64 + g);
-  // v_perm_b32 tables (slots 0, 1, 3, 7 = A, C, G, T): threshold bytes and counter offsets
-  const uint32_t thr = BQ0 ? 0u : (uint32_t)(p.baseq > 256 ? 255 : p.baseq - 1);
-  const uint32_t th_lo = thr | (thr << 8) | 0x00FF0000u | (thr << 24), th_hi = 0x00FFFFFFu | (thr << 24);
-  const uint32_t cd_lo = 0x08000400u, cd_hi = 0x0C000000u;
+  // a base counts iff its byte >= thr (layout.h dense_threshold: 52 for every baseq <= 0 -- every A/C/G/T base, no N, no masked slot)
+  const uint32_t thr = BQ0 ? dense_threshold(0) : dense_threshold(p.baseq);
   const int rq = p.readq < 0 ? 0 : (p.readq > 256 ? 256 : p.readq);   // sum(q) < rq * l  <=>  np.mean(q) < readq (q <= 255)
   const uint32_t one = 1u;
 
@@ -267,60 +251,31 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     return left <= 0 ? 0 : (left < rpw ? (int)left : rpw);
   };
 
-  // Sum of a read's quality bytes over its lanes (np.mean(aln.query_qualities), midas/run/snps.py:151): every lane adds its
-  // part to the read's LDS slot, reads the slot back and clears it -- three LDS operations of one wave, executed in
-  // order, instead of a shuffle per lane of the read.  Bit 31: QUAL absent.
-  auto read_sum = [&](uint32_t part) -> uint32_t {
-    uint32_t tot;
-    asm volatile("ds_add_u32 %1, %2\n\tds_read_b32 %0, %1\n\tds_write_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&v"(tot) : "v"(qsum_addr), "v"(part), "v"(0u) : "memory");
-    return tot;
-  };
-  auto lane_qsum = [&](const uint32_t (&q)[8], int nb) -> uint32_t {
-    uint32_t part = 0;
-    if (nb == LB) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) part = __builtin_amdgcn_sad_u8(q[k], 0u, part);
-      part = __builtin_amdgcn_sad_u8(LB == 32 ? q[7] : (q[7] & 0x0000FFFFu), 0u, part);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) part = __builtin_amdgcn_sad_u8(q[k] & low_bytes_mask(nb - 4 * k), 0u, part);
-    }
-    if (c == 0) part |= ((q[0] & 0xFFu) == 0xFFu) ? 0x80000000u : 0u;   // QUAL absent (BAM: first byte 0xFF)
-    return part;
-  };
-  // Threshold bytes and counter offsets of eight bases from their 4-bit codes (one dword of SEQ): the even and the odd
-  // nibbles become v_perm_b32 selectors by (n + 7) ^ 8 -- A, C, G, T (1, 2, 4, 8) select table slots 0, 1, 3, 7, every
-  // other code a slot or a selector constant that reads 0xFF.
-  // The lanes `go` tally bases [lo, hi) of their 30 / 32, the first of the lane at tile-relative site loc0.  Group by group
-  // (decode eight bases, tally them), so that only one group's looked-up bytes are alive at a time.
+  // The lanes `go` tally bases [lo, hi) of their 30 / 32, the first of the lane at tile-relative site loc0, group by group of
+  // eight.  Partial lanes zero the bytes outside [lo, hi) (a zero byte never counts): two rows of the byte-mask table (LDS).
   // (sparse: a pass with few lanes, e.g. the one lane of a read that holds its indel -- a group of eight bases none of the
   // wave's lanes has a base in is skipped)
-  auto tally_range = [&](bool go, int lo, int hi, int loc0, const uint32_t (&qv)[8], const uint32_t (&sq)[4], auto sparse_tag) {
+  auto tally_range = [&](bool go, int lo, int hi, int loc0, const uint32_t (&bv)[8], auto sparse_tag) {
     constexpr bool SPARSE = decltype(sparse_tag)::value;
     const uint32_t abase = ((uint32_t)loc0 << 4) + lds_base;
-    const bool masked = !(kDebug & 32) && __ballot(go && (lo > 0 || hi < LB)) != 0ull;   // partial lanes: the codes outside become 0
+    const bool masked = !(kDebug & 32) && __ballot(go && (lo > 0 || hi < LB)) != 0ull;   // partial lanes: the bytes outside become 0
     unsigned long long gmask[4];
     if (SPARSE) {
 #pragma unroll
       for (int S = 0; S < 4; ++S) gmask[S] = __ballot(go && lo < 8 * S + 8 && hi > 8 * S);
     }
-    if (!go) return;                                                    // outside [lo, hi) (a row of each table, LDS)
-    uint4 keep = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-    if (masked) {
-      const uint4 kh = *reinterpret_cast<const uint4*>(s_khi + 4 * (hi > 32 ? 32 : hi));
-      const uint4 kl = *reinterpret_cast<const uint4*>(s_klo + 4 * (lo < 0 ? 0 : lo));
-      keep.x = kh.x & kl.x; keep.y = kh.y & kl.y; keep.z = kh.z & kl.z; keep.w = kh.w & kl.w;
-    }
+    if (!go) return;
     auto group = [&](auto sidx, auto off, auto nbases) {
       constexpr int S = decltype(sidx)::value;
       if (SPARSE && gmask[S] == 0ull) return;
-      const uint32_t x = masked ? (sq[S] & (S == 0 ? keep.x : (S == 1 ? keep.y : (S == 2 ? keep.z : keep.w)))) : sq[S];
-      const uint32_t se = (((x >> 4) & 0x0F0F0F0Fu) + 0x07070707u) ^ 0x08080808u;   // even bases (high nibbles)
-      const uint32_t so = ((x & 0x0F0F0F0Fu) + 0x07070707u) ^ 0x08080808u;          // odd bases
-      const uint32_t te = __builtin_amdgcn_perm(th_hi, th_lo, se), to = __builtin_amdgcn_perm(th_hi, th_lo, so);
-      const uint32_t ce = __builtin_amdgcn_perm(cd_hi, cd_lo, se), co = __builtin_amdgcn_perm(cd_hi, cd_lo, so);
-      tally_group<decltype(off)::value, decltype(nbases)::value>(qv[2 * S], qv[2 * S + 1], te, to, ce, co, abase, one);
+      uint32_t x0 = bv[2 * S], x1 = bv[2 * S + 1];
+      if (masked) {        // bytes [lo, hi): row hi less row lo
+        const uint2 kh = *reinterpret_cast<const uint2*>(s_kb + 8 * (hi > 32 ? 32 : hi) + 2 * S);
+        const uint2 kl = *reinterpret_cast<const uint2*>(s_kb + 8 * (lo < 0 ? 0 : lo) + 2 * S);
+        x0 &= kh.x & ~kl.x;
+        x1 &= kh.y & ~kl.y;
+      }
+      tally_group<decltype(off)::value, decltype(nbases)::value>(x0, x1, thr, abase, one);
     };
     using std::integral_constant;
     group(integral_constant<int, 0>{}, integral_constant<int, 0>{}, integral_constant<int, 8>{});
@@ -344,13 +299,13 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     f.pos = x.x; f.l_nc = x.y; f.nmq = x.z; f.off = x.w;
     return f;
   };
-  // ---- stage D: what the read's processing needs of its record, and the lane's bases (two 16-byte loads of QUAL, one of
-  // SEQ) + the read's first four CIGAR ops (one 16-byte load; the payload has slack behind its last read).  The four loads go
-  // off ONE scalar base -- the payload of the iteration's first read (lane 0's) -- plus a 32-bit lane offset: the reads of an
-  // iteration are neighbours in the payload.
+  // ---- stage D: what the read's processing needs of its record, and the lane's bases (two 16-byte loads of base bytes) + the
+  // read's first four CIGAR ops (one 16-byte load; the payload has slack behind its last read) + its quality sum (one dword).
+  // The four loads go off ONE scalar base -- the payload of the iteration's first read (lane 0's) -- plus a 32-bit lane offset:
+  // the reads of an iteration are neighbours in the payload.
   //   nmq: NM (16 bits, 0xFFFF = no NM tag) | mapq << 16 | kGenIdle << 24 (a lane without a read)      l_nc: l_seq | n_cigar << 16
   struct Rd { uint32_t pos, nmq, l_nc; };
-  struct Dat { uint32_t q[8]; uint32_t s[4]; uint32_t cg[4]; };
+  struct Dat { uint32_t b[8]; uint32_t cg[4]; uint32_t qs; };
   auto settle = [&](const Raw& f, int n_reads_it, Rd& r, Dat& d) {
     const bool act = g < n_reads_it;
     const uint32_t l_nc = act ? f.l_nc : 0u;
@@ -363,16 +318,16 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     const uint32_t rel = (f.off - off0) << 3;                          // (an iteration's reads lie within a few hundred KB)
     const bool has = (uint32_t)q0 < l && !(kDebug & 128);
     const uint32_t vc = act && !(kDebug & 128) ? rel : 0u;
-    const uint32_t vs = has ? rel + nc4 + (uint32_t)(q0 >> 1) : 0u;
-    const uint32_t vq = has ? rel + nc4 + ((l + 1u) >> 1) + (uint32_t)q0 : 0u;
-    const u32x4_a1 qa = *reinterpret_cast<const u32x4_a1*>(base + (size_t)vq);
-    const u32x4_a1 qb = *reinterpret_cast<const u32x4_a1*>(base + (size_t)vq + 16);
-    const u32x4_a1 sv = *reinterpret_cast<const u32x4_a1*>(base + (size_t)vs);
+    const uint32_t vq = act && !(kDebug & 128) ? rel + nc4 : 0u;
+    const uint32_t vb = has ? rel + nc4 + 4u + (uint32_t)q0 : 0u;
+    const u32x4_a1 ba = *reinterpret_cast<const u32x4_a1*>(base + (size_t)vb);
+    const u32x4_a1 bb = *reinterpret_cast<const u32x4_a1*>(base + (size_t)vb + 16);
     const u32x4_a4 cv = *reinterpret_cast<const u32x4_a4*>(base + (size_t)vc);
-    d.q[0] = qa.x; d.q[1] = qa.y; d.q[2] = qa.z; d.q[3] = qa.w;
-    d.q[4] = qb.x; d.q[5] = qb.y; d.q[6] = qb.z; d.q[7] = qb.w;
-    d.s[0] = sv.x; d.s[1] = sv.y; d.s[2] = sv.z; d.s[3] = sv.w;
+    const uint32_t qs = *reinterpret_cast<const uint32_t*>(base + (size_t)vq);
+    d.b[0] = ba.x; d.b[1] = ba.y; d.b[2] = ba.z; d.b[3] = ba.w;
+    d.b[4] = bb.x; d.b[5] = bb.y; d.b[6] = bb.z; d.b[7] = bb.w;
     d.cg[0] = cv.x; d.cg[1] = cv.y; d.cg[2] = cv.z; d.cg[3] = cv.w;
+    d.qs = qs;
   };
 
   Tile tile = load_tile(c_tiles, c_first);
@@ -439,13 +394,13 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
 #if MIDAS_SNPS_DEBUG_BITS & 256
       asm volatile("" :: "v"(rd_n.pos), "v"(rd_n.l_nc));
       const unsigned long long pt1 = PROBE_NOW();
-      asm volatile("" :: "v"(dat_cur.q[0]), "v"(dat_cur.q[7]), "v"(dat_cur.s[3]), "v"(dat_cur.cg[3]));
+      asm volatile("" :: "v"(dat_cur.b[0]), "v"(dat_cur.b[7]), "v"(dat_cur.qs), "v"(dat_cur.cg[3]));
       const unsigned long long pt2 = PROBE_NOW();
       pr_cols += pt1 - pt0; pr_bases += pt2 - pt1; pr_iters += 1;
 #endif
 
       if (kDebug & 4) {          // (developer timing variant: the stream of loads only)
-        asm volatile("" :: "v"(dat_cur.q[0]), "v"(dat_cur.q[7]), "v"(dat_cur.s[0]), "v"(dat_cur.s[3]), "v"(dat_cur.cg[0]), "v"(rd_cur.pos));
+        asm volatile("" :: "v"(dat_cur.b[0]), "v"(dat_cur.b[7]), "v"(dat_cur.qs), "v"(dat_cur.cg[0]), "v"(rd_cur.pos));
         return;
       }
       MIDAS_MARK("qsum");
@@ -457,15 +412,13 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
       // (developer timing variant, bit 512: ALL per-read work off -- no quality sum, no CIGAR shape, no filter tables: every read is
       // one match run of its length and kept; the tallies and the stream stay.  What a scheme that does the per-read work once
       // per read instead of on each of its lanes could save AT MOST: profiles/r06_kernel_experiments.txt section 3)
-      uint32_t qsum = (kDebug & (64 | 512)) ? 0x00FFFFFFu : read_sum(has ? lane_qsum(dat_cur.q, nb) : 0u);
-      const bool t_noqual = (qsum >> 31) != 0u;
-      qsum &= 0x7FFFFFFFu;
+      // The read's quality sum travels with it (layout.h: bit 31 QUAL absent); sum(q) < readq * l_seq is np.mean(q) < readq exactly.
+      uint32_t qsum = (kDebug & (64 | 512)) ? 0x00FFFFFFu : dat_cur.qs;
+      const bool t_noqual = (qsum & kDenseQualAbsent) != 0u;
+      qsum &= ~kDenseQualAbsent;
       const uint32_t nm16 = rd_cur.nmq & 0xFFFFu;
       const int nm = (int)nm16, mapq = (int)((rd_cur.nmq >> 16) & 0xFFu);
       const bool act = !((rd_cur.nmq >> 24) & kGenIdle);
-      uint32_t qv[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) qv[k] = BQ0 ? 0x01010101u : dat_cur.q[k];
 
       // ---- the read's shape, in registers: one match op of the read's length settles most reads; anything else takes the
       // four-op grammar (wave-uniform branch) ------------------------------------------------------------------------------
@@ -518,10 +471,10 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         const bool go1 = go_a | go_b;
         MIDAS_MARK("pass1");
         if (!(kDebug & 1) && __ballot(go1) != 0ull)
-          tally_range(go1, go_a ? lo_a : lo_b, go_a ? hi_a : hi_b, go_a ? loc_a : loc_b, qv, dat_cur.s, std::false_type{});
+          tally_range(go1, go_a ? lo_a : lo_b, go_a ? hi_a : hi_b, go_a ? loc_a : loc_b, dat_cur.b, std::false_type{});
         const bool go2 = go_a & go_b;
         MIDAS_MARK("pass2");
-        if (!(kDebug & (1 | 16)) && __ballot(go2) != 0ull) tally_range(go2, lo_b, hi_b, loc_b, qv, dat_cur.s, std::true_type{});
+        if (!(kDebug & (1 | 16)) && __ballot(go2) != 0ull) tally_range(go2, lo_b, hi_b, loc_b, dat_cur.b, std::true_type{});
       }
       // ======================= slow: walked op by op ============================================================================
       MIDAS_MARK("slowgate");
@@ -617,7 +570,7 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         while (__ballot(walking) != 0ull) {
           const int lo = jlo > -loc0 ? jlo : -loc0;
           const int hi = jhi < ext_len - loc0 ? jhi : ext_len - loc0;
-          if (!(kDebug & 1)) tally_range(walking && lo < hi, lo, hi, loc0, qv, dat_cur.s, std::true_type{});
+          if (!(kDebug & 1)) tally_range(walking && lo < hi, lo, hi, loc0, dat_cur.b, std::true_type{});
           walking = (walking && k < nc) ? next_segment() : false;
         }
       }

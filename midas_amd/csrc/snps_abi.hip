@@ -92,6 +92,7 @@ struct midas_snps_batch {
   std::vector<uint8_t> h_tile_split;
   bool any_split = false;
   bool has_high_qual = false;   // the payload holds a quality above kMaxPackedQual: a baseq above it cannot be served
+  bool dense_clamped = false;   // the direct layout clamped an A/C/G/T quality above kDenseMaxQual (layout.h): a baseq above it goes the long way
   int64_t n_items = 0, n_whole_items = 0;
   std::vector<std::pair<size_t, size_t>> zero_ranges;   // (first site, sites) of split tiles: counts zeroed before a run
   FilterTables h_filt;
@@ -893,11 +894,14 @@ hipError_t inflate_again(const InflateParams& ip, const std::vector<InflateBlock
 // (PayloadParams::drec).  kStreamFallback: this BAM is not for the streamed decode (a record longer than the blocks a group
 // keeps behind its end) -- the caller decodes it in one arena.
 constexpr int32_t kStreamFallback = -1000;
-struct TwoBuffers { void* a; void* b; };
+constexpr uint32_t kSideFirstEntries = 4096;                 // the side buffer's first room (layout.h DenseSide): grown by the group that needs more
+constexpr unsigned long long kSideFirstBytes = 1ull << 20;
+struct TwoBuffers { void* a; void* b; void* c; };
 void two_buffers_free(void* v) {
   TwoBuffers* t = static_cast<TwoBuffers*>(v);
   if (t->a) (void)hipFree(t->a);
   if (t->b) (void)hipFree(t->b);
+  if (t->c) (void)hipFree(t->c);
   delete t;
 }
 struct StreamColumns {       // the result's record arrays in ONE allocation, for `cap` records (+ 2: the offsets' last entry, the sentinel record)
@@ -1094,7 +1098,34 @@ int32_t device_decode_stream(midas_snps_ctx* ctx, const uint8_t* comp_base, cons
   // ---- the result's arrays ----------------------------------------------------------------------------------------------------------
   StreamColumns cols;
   struct Pay { uint8_t* p = nullptr; size_t cap_units = 0; } pay;
-  struct Owned { StreamColumns& c; Pay& y; bool keep = false; ~Owned() { if (!keep) { if (c.p) (void)hipFree(c.p); if (y.p) (void)hipFree(y.p); } } } owned{cols, pay};
+  // the side buffer (layout.h DenseSide): the raw SEQ / QUAL of the reads the base bytes cannot give back -- none in most files;
+  // a group that finds no room is written again behind a buffer with room for all of its SEQ / QUAL
+  struct Side { DenseSide* p = nullptr; DenseSide h{}; } side;
+  struct Owned { StreamColumns& c; Pay& y; Side& z; bool keep = false; ~Owned() { if (!keep) { if (c.p) (void)hipFree(c.p); if (y.p) (void)hipFree(y.p); if (z.p) (void)hipFree(z.p); } } } owned{cols, pay, side};
+  auto grow_side = [&](uint32_t cap_entries, unsigned long long cap_bytes) -> int32_t {     // (what the groups so far kept moves along)
+    DenseSide* q = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), (size_t)dense_side_bytes(cap_entries, cap_bytes));
+    if (e != hipSuccess) return hip_err(e, "the side buffer");
+    DenseSide h = side.h;
+    h.flags &= ~kDenseSideOverflow;
+    h.cap_entries = cap_entries; h.cap_bytes = cap_bytes;
+    const unsigned long long n_ent = side.h.bump >> kDenseSideEntryShift, n_bytes = (side.h.bump & kDenseSideMaxField) << 3;
+    e = hipMemcpyAsync(q, &h, sizeof h, hipMemcpyHostToDevice, s);
+    if (side.p && n_ent > 0) {
+      if (e == hipSuccess) e = hipMemcpyAsync(dense_side_entries(q), dense_side_entries(side.p), n_ent * sizeof(DenseSideEntry), hipMemcpyDeviceToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(reinterpret_cast<uint8_t*>(dense_side_entries(q) + cap_entries),
+                                              reinterpret_cast<uint8_t*>(dense_side_entries(side.p) + side.h.cap_entries), n_bytes, hipMemcpyDeviceToDevice, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (side.p) (void)hipFree(side.p);
+    side.p = q;
+    side.h = h;
+    return e == hipSuccess ? MIDAS_SNPS_OK : hip_err(e, "the side buffer moved");
+  };
+  {
+    const int32_t gs = grow_side(kSideFirstEntries, kSideFirstBytes);
+    if (gs != MIDAS_SNPS_OK) return gs;
+  }
   long long N = 0;                                  // records so far
   long long base[4] = {0, 0, 0, 0};                 // what the offset columns came to so far: SEQ bytes, QUAL bytes, CIGAR ops, payload units
   const double span_total = (double)(seg_stop > sg.from ? seg_stop - sg.from : 1);
@@ -1342,8 +1373,35 @@ int32_t device_decode_stream(midas_snps_ctx* ctx, const uint8_t* comp_base, cons
       dp.stream = slot; dp.rec_off = d_rec; dp.n_records = n;
       dp.pos = cp.pos; dp.nm = cp.nm; dp.unit_off = cp.unit_off;
       dp.rec = reinterpret_cast<DirectRec*>(cols.colp(0)) + N; dp.payload = pay.p;
-      DS_TRY(launch_bam_direct(dp, ctx->prop.multiProcessorCount, s));
-      DS_TRY(hipStreamSynchronize(s));
+      dp.read_base = N; dp.side_copy = 1;
+      // the most this group can reserve: every read an entry, its SEQ + QUAL (8-byte aligned) in data
+      const unsigned long long g_ent = (unsigned long long)n, g_bytes = (unsigned long long)(ends[0] - base[0]) + (unsigned long long)(ends[1] - base[1]) + 8ull * (unsigned long long)n;
+      for (int attempt = 0;; ++attempt) {
+        const unsigned long long n_ent = side.h.bump >> kDenseSideEntryShift, n_bytes = (side.h.bump & kDenseSideMaxField) << 3;
+        if (!dense_side_fits(n_ent + g_ent, (n_bytes + g_bytes) >> 3)) {       // (the bump's fields could carry: refuse, never lose a read)
+          if (err256) snprintf(err256, 256, "device decode (streamed): the exact copies of the reads the layout cannot hold exceed the side buffer's limits (%llu reads, %llu bytes)",
+                               n_ent + g_ent, n_bytes + g_bytes);
+          return MIDAS_SNPS_ERR_UNSUPPORTED;
+        }
+        dp.side = side.p;
+        DS_TRY(launch_bam_direct(dp, ctx->prop.multiProcessorCount, s));
+        DenseSide h{};
+        DS_TRY(hipMemcpyAsync(&h, side.p, sizeof h, hipMemcpyDeviceToHost, s));
+        DS_TRY(hipStreamSynchronize(s));
+        if (!(h.flags & kDenseSideOverflow)) { side.h = h; break; }
+        // no room for the group's exceptional reads: at least room for ALL of its reads' SEQ / QUAL behind what the groups before
+        // kept (twice the old room when that is more: a file of exceptional reads grows it a few times, not every group), and the
+        // group written again (the bump and the flags as they were in front of it)
+        if (attempt > 0) {
+          if (err256) snprintf(err256, 256, "device decode (streamed): group %zu found no room in a side buffer sized for all of its reads", g);
+          return MIDAS_SNPS_ERR_HIP;
+        }
+        const unsigned long long want_e = std::min(kDenseSideMaxField, std::max(n_ent + g_ent, 2ull * side.h.cap_entries));
+        const unsigned long long want_b = std::min(kDenseSideMaxField << 3, std::max(n_bytes + g_bytes, 2ull * side.h.cap_bytes));
+        const int32_t gs = grow_side((uint32_t)want_e, want_b);
+        if (gs != MIDAS_SNPS_OK) return gs;
+        if (trace) fprintf(stderr, "[device decode] streamed: group %zu: the side buffer grown to %llu reads, %llu bytes\n", g, want_e, want_b);
+      }
       lap(5);
       N += n;
       for (int k = 0; k < 4; ++k) base[k] = ends[k];
@@ -1394,7 +1452,9 @@ int32_t device_decode_stream(midas_snps_ctx* ctx, const uint8_t* comp_base, cons
   rr.seq_off = reinterpret_cast<int64_t*>(cols.colp(7)); rr.qual_off = reinterpret_cast<int64_t*>(cols.colp(8)); rr.cigar_off = reinterpret_cast<int64_t*>(cols.colp(9)); rr.unit_off = reinterpret_cast<int64_t*>(cols.colp(10));
   rr.stream = nullptr; rr.rec_off = nullptr;       // (no inflated stream is kept: raw columns come out of the direct layout)
   rr.payload_units = base[3];
-  res->dev_owner = new TwoBuffers{cols.p, pay.p};
+  rr.side = side.p;
+  rr.dense_flags = side.h.flags;
+  res->dev_owner = new TwoBuffers{cols.p, pay.p, side.p};
   res->dev_free = two_buffers_free;
   owned.keep = true;
 #undef DS_TRY
@@ -1701,11 +1761,18 @@ int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob
     uint8_t* d_pay = take((size_t)units * 8 + 64);
     if (!d_pay) { if (err256) snprintf(err256, 256, "device decode: the arena is too small for the direct layout"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
     DEC_TRY(hipMemsetAsync(d_pay + (size_t)units * 8, 0, 64, s));       // (a lane's 16-byte loads may overhang the last read)
+    // (the inflated stream stays: raw columns are cut out of it, the side buffer only collects the producer's flags)
+    DenseSide* d_side = reinterpret_cast<DenseSide*>(take(sizeof(DenseSide)));
+    if (!d_side) { if (err256) snprintf(err256, 256, "device decode: the arena is too small for the direct layout"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
+    DEC_TRY(hipMemsetAsync(d_side, 0, sizeof(DenseSide), s));
     BamDirectParams dp;
     dp.stream = base; dp.rec_off = d_rec; dp.n_records = n;
     dp.pos = cp.pos; dp.nm = cp.nm; dp.unit_off = cp.unit_off;
     dp.rec = d_drec; dp.payload = d_pay;
+    dp.side = d_side; dp.read_base = 0; dp.side_copy = 0;
     DEC_TRY(launch_bam_direct(dp, ctx->prop.multiProcessorCount, s));
+    DenseSide h_side{};
+    DEC_TRY(hipMemcpyAsync(&h_side, d_side, sizeof h_side, hipMemcpyDeviceToHost, s));
     const HostColumns hc = alloc(sink, n);
     if (!hc.refid) { DEC_TRY(hipStreamSynchronize(s)); return MIDAS_SNPS_OK; }      // (the caller reports its own out-of-memory)
     if (n > 0) {
@@ -1721,6 +1788,7 @@ int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob
     rr.cigar_off = reinterpret_cast<int64_t*>(cp.cigar_off); rr.unit_off = reinterpret_cast<int64_t*>(cp.unit_off);
     rr.stream = base; rr.rec_off = reinterpret_cast<const uint64_t*>(d_rec);
     rr.payload_units = (int64_t)units;
+    rr.dense_flags = h_side.flags;
     res->dev_owner = new ArenaLoan{loan.pool, loan.p};       // everything lives in the arena: it stays lent until the handle is closed
     res->dev_free = arena_loan_free;
     loan.p = nullptr;
@@ -1848,7 +1916,10 @@ int32_t midas_bam_resident_to_columns(midas_bam* bam, midas_snps_ctx* ctx, int64
   PayloadParams pp;
   pp.stream = rr->stream;
   pp.rec_off = reinterpret_cast<const unsigned long long*>(rr->rec_off);
-  if (!rr->stream) { pp.stream = rr->payload; pp.drec = static_cast<const DirectRec*>(rr->rec); }      // (a streamed decode: out of the direct layout)
+  if (!rr->stream) {      // (a streamed decode: out of the direct layout, the side buffer's exact copies over the decoded bytes)
+    pp.stream = rr->payload; pp.drec = static_cast<const DirectRec*>(rr->rec);
+    pp.side = static_cast<const DenseSide*>(rr->side); pp.side_first = 0;
+  }
   pp.n_records = n;
   pp.seq_off = reinterpret_cast<const long long*>(rr->seq_off); pp.qual_off = reinterpret_cast<const long long*>(rr->qual_off);
   pp.cigar_off = reinterpret_cast<const long long*>(rr->cigar_off);
@@ -2118,7 +2189,10 @@ int32_t ensure_raw_payload(midas_snps_batch* b) {
   PayloadParams pp;
   pp.stream = b->rr.stream;
   pp.rec_off = reinterpret_cast<const unsigned long long*>(b->rr.rec_off) + b->rr_first;
-  if (!b->rr.stream) { pp.stream = b->rr.payload; pp.rec_off = nullptr; pp.drec = b->d_drec; }      // (a streamed decode: out of the direct layout)
+  if (!b->rr.stream) {    // (a streamed decode: out of the direct layout, the side buffer's exact copies over the decoded bytes)
+    pp.stream = b->rr.payload; pp.rec_off = nullptr; pp.drec = b->d_drec;
+    pp.side = static_cast<const DenseSide*>(b->rr.side); pp.side_first = b->rr_first;
+  }
   pp.n_records = b->n_reads;
   pp.seq_off = reinterpret_cast<const long long*>(b->d_seq_off); pp.qual_off = reinterpret_cast<const long long*>(b->d_qual_off);
   pp.cigar_off = reinterpret_cast<const long long*>(b->d_cigar_off);
@@ -2267,7 +2341,9 @@ int32_t direct_prepare(midas_snps_batch* b) {
     const int nb = direct_index_blocks(b->n_reads);
     HIP_TRY(ctx, hipMalloc(&b->d_drec, (n1 + 1) * sizeof(DirectRec)));
     HIP_TRY(ctx, hipMemsetAsync(b->d_drec, 0, (n1 + 1) * sizeof(DirectRec), s));
-    HIP_TRY(ctx, hipMalloc(&b->d_dunits, ((size_t)nb + 1) * 8));
+    HIP_TRY(ctx, hipMalloc(&b->d_dunits, ((size_t)nb + 1) * 8 + sizeof(DenseSide)));      // (+ the layout's flags: the caller's columns stay, no side copies)
+    DenseSide* const d_side = reinterpret_cast<DenseSide*>(b->d_dunits + nb + 1);
+    HIP_TRY(ctx, hipMemsetAsync(d_side, 0, sizeof(DenseSide), s));
     DirectLayoutParams lp;
     lp.pos = b->d_pos; lp.mapq = b->d_mapq; lp.nm = b->d_nm; lp.l_seq = b->d_lseq;
     lp.seq_off = b->d_seq_off; lp.qual_off = b->d_qual_off; lp.cigar_off = b->d_cigar_off;
@@ -2276,6 +2352,7 @@ int32_t direct_prepare(midas_snps_batch* b) {
     lp.block_units = b->d_dunits;
     lp.rec = b->d_drec;
     lp.payload = nullptr;
+    lp.side = d_side;
     unsigned long long units = 0;
     hipEvent_t lev[2] = {nullptr, nullptr};       // (how long the layout takes on the device: reported beside the step it feeds)
     struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int k = 0; k < 2; ++k) if (e[k]) (void)hipEventDestroy(e[k]); } } ev_guard{lev};
@@ -2299,12 +2376,19 @@ int32_t direct_prepare(midas_snps_batch* b) {
     lp.payload = b->d_dpay;
     if (b->n_reads > 0) HIP_TRY(ctx, launch_direct_layout_fill(lp, s));
     HIP_TRY(ctx, hipEventRecord(lev[1], s));
+    DenseSide h_side{};
+    HIP_TRY(ctx, hipMemcpyAsync(&h_side, d_side, sizeof h_side, hipMemcpyDeviceToHost, s));
     HIP_TRY(ctx, hipEventSynchronize(lev[1]));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    b->dense_clamped = (h_side.flags & kDenseClampedQual) != 0u;
     float lms = 0.f;
     if (hipEventElapsedTime(&lms, lev[0], lev[1]) == hipSuccess) b->layout_build_us = (int32_t)(lms * 1000.f + 0.5f);
     (void)hipGetLastError();
   }
-  if (b->resident) b->direct_payload_bytes = b->rr.payload_units * 8;
+  if (b->resident) {
+    b->direct_payload_bytes = b->rr.payload_units * 8;
+    b->dense_clamped = (b->rr.dense_flags & kDenseClampedQual) != 0u;      // (the handle's flag: the whole file's reads, not just this batch's)
+  }
   // the tile ranges once, to see how well the reads are ordered: a tile's stream holds every read between the first and the
   // last that can touch it
   fill_direct_index(b, &ip);
@@ -2795,6 +2879,10 @@ int32_t midas_snps_batch_run(midas_snps_batch* b, const midas_snps_thresholds* t
     if (pst != MIDAS_SNPS_OK) return pst;
     if (b->has_high_qual) run_path = MIDAS_SNPS_PATH_DIRECT;
   }
+  // The direct layout keeps an A/C/G/T quality in its base byte up to kDenseMaxQual (layout.h dense_byte): exact for every
+  // baseq <= 50, and above that unless the batch holds a larger A/C/G/T quality (an absent QUAL's 0xFF included) -- that one
+  // case is served by the long path over the raw columns, this run only.
+  if (run_path == MIDAS_SNPS_PATH_DIRECT && thr->baseq > (int32_t)kDenseMaxQual && b->dense_clamped) run_path = MIDAS_SNPS_PATH_LONG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   hipEvent_t* ev = b->timing_slots > 0 ? &b->ev[(size_t)(b->timed_runs % b->timing_slots) * 3] : nullptr;
