@@ -717,6 +717,57 @@ int32_t midas_genes_merge_write_matrix(const char* path, const char* header_line
                                        const uint8_t* state, int32_t threads, char* err1024);
 int32_t midas_genes_merge_format_f64(int64_t n, const double* v, char* out, int64_t capacity, int64_t* out_len);
 
+/* ---- snp_diversity.py / call_consensus.py: the analysis of one merged species directory ------------------------------------
+ * midas_sites_tables_*: one output directory of `merge_midas.py snps`, read as csv.DictReader(delimiter='\t') reads it
+ *   (midas/analyze/parse_snps.py:27-58, 181-194): snps_summary.txt and snps_info.txt parsed into columns, snps_freq.txt and
+ *   snps_depth.txt mapped and left as text.  counts: out8[0..6] = summary rows, info rows, distinct gene ids, sample columns
+ *   of the depth header, bytes of the freq and depth rows after their header lines, sample columns of the freq header.
+ *   columns: out25[2k], out25[2k + 1] for k = 0..8 = the strings back to back (char) and their offsets (int64, n + 1) of
+ *   sample_id, site_id, ref_allele, major_allele, minor_allele, locus_type, site_type, the gene ids in order of first
+ *   appearance, the depth header's sample ids; sizes10[k] = bytes of pool k; out25[18..22] = mean_coverage (f64),
+ *   fraction_covered (f64), the sites' gene index (int32, -1: no gene id), the freq rows, the depth rows (char).  They belong
+ *   to the handle.  A file that cannot be read, or a row that lacks a field in use, is an error naming file and line.
+ * midas_sites_parse_cell: float() (kind 0, out8 is a double) or int() (kind 1, an int64) of one cell by the host's exact
+ *   parser -- the one the scan uses for the cells its device parser passes on.                                             */
+typedef struct midas_sites_tables midas_sites_tables;
+int32_t midas_sites_tables_open(const char* dir, midas_sites_tables** out, char* err1024);
+int32_t midas_sites_tables_counts(const midas_sites_tables* t, int64_t* out8);
+int32_t midas_sites_tables_columns(const midas_sites_tables* t, const void** out25, int64_t* sizes10);
+void midas_sites_tables_close(midas_sites_tables* t);
+int32_t midas_sites_parse_cell(int32_t kind, const char* text, int64_t n, void* out8);
+
+/* The per-site loop of snp_diversity.py (:182-258) and call_consensus.py (:183-213) on the device.  freq / depth: the text
+ * rows of the two matrices after their header lines (host memory); row i of both belongs to site i, and the sites end with
+ * the shorter of the two or at n_sites_max.  Per site i: site_mask[i] (what the info table and the options decide: ref_allele,
+ * locus / site type, --site_list, --rand_sites), site_gene[i] (MIDAS_SITES_PER_GENE), minor[i] / major[i] (MIDAS_SITES_SEQ).
+ * Sample s of n_samples reads matrix column sample_col[s] (0 = the first after the site id) and has mean_depth[s]; the order
+ * of the samples is the order of every sum over samples.  fparams5 = site_ratio, allele_support, site_prev, site_maf, snp_maf;
+ * iparams8 = site_depth, max_sites (-1: all), flags, number of genes, group_rows, chunk_bytes (0: from the free device
+ * memory; the outputs do not depend on either), sequence capacity, 0.
+ * A cell is float() / int() of its text; the device converts plain decimals itself and hands every other cell to the host's
+ * exact parser.  A row with too few columns or a cell that is no number, among the rows the reference would read, is
+ * MIDAS_SNPS_ERR_BAD_LAYOUT with out_stats16[4..6] = matrix (1 freq, 2 depth), 0-based data row, sample (-1: short row).
+ * MIDAS_SITES_SUMS: per chain (sample s, or the pool under MIDAS_SITES_POOLED) and gene (MIDAS_SITES_PER_GENE; else one) at
+ *   chain * genes + gene: out_pi = the sum of 2 f (1 - f) in site order exactly as `+=` forms it, out_snps, out_sites,
+ *   out_depth.  MIDAS_SITES_SEQ: out_seq[s * capacity + k] = '-', minor or major allele of the k-th retained site.
+ * dump_* (nullable, tests): the parsed cells [n_samples][n_sites_max], the sites' final keep flag and pooled frequency.
+ * out_stats16: [0] sites read, [1] sites kept, [2] / [3] freq / depth cells converted by the host, [7] row groups, [8] kept
+ * sites without a gene under MIDAS_SITES_PER_GENE, [9] group_rows and [10] chunk_bytes in use.  out_ms8 (nullable): upload +
+ * index (host clock), index, parse, site, order, sums, sequences, download (device events).                               */
+#define MIDAS_SITES_WEIGHT 1
+#define MIDAS_SITES_ROUND 2
+#define MIDAS_SITES_POOLED 4
+#define MIDAS_SITES_PER_GENE 8
+#define MIDAS_SITES_MASK_ONLY 16
+#define MIDAS_SITES_SEQ 32
+#define MIDAS_SITES_SUMS 64
+int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                         int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor, const char* major,
+                         int32_t n_samples, const int32_t* sample_col, const double* mean_depth, const double* fparams5,
+                         const int64_t* iparams8, double* out_pi, int64_t* out_snps, int64_t* out_sites, int64_t* out_depth,
+                         uint8_t* out_seq, double* dump_freq, int64_t* dump_depth, uint8_t* dump_keep, double* dump_pooled,
+                         int64_t* out_stats16, float* out_ms8);
+
 /* ---- the exchange between ranks (comm.cpp): RCCL itself, no process group ------------------------------------------------
  * One process per GPU; the only thing ranks exchange on this path is the per-species summary rows -- the reference's pool
  * workers return (species_id, aln_stats) through a pipe, midas/run/snps.py:225-241, midas/utility.py:81-107 -- plus, on the

@@ -345,6 +345,12 @@ def load_library(build_if_missing: bool = True):
                               + [C.POINTER(C.c_float)]),
         'midas_genes_merge_write_matrix': (i32, [C.c_char_p, C.c_char_p, i32, i64, vp, vp, vp, i32, vp, vp, i32, C.c_char_p]),
         'midas_genes_merge_format_f64': (i32, [i64, vp, vp, i64, C.POINTER(i64)]),
+        'midas_sites_tables_open': (i32, [C.c_char_p, C.POINTER(vp), C.c_char_p]),
+        'midas_sites_tables_counts': (i32, [vp, vp]),
+        'midas_sites_tables_columns': (i32, [vp, vp, vp]),
+        'midas_sites_tables_close': (None, [vp]),
+        'midas_sites_parse_cell': (i32, [i32, C.c_char_p, i64, vp]),
+        'midas_sites_scan': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15),
     })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing: fail loudly
@@ -386,6 +392,9 @@ EXPORTED_SYMBOLS = [
     'midas_genes_merge_tables_columns', 'midas_genes_merge_tables_close', 'midas_genes_merge', 'midas_genes_merge_write_matrix',
     'midas_genes_merge_format_f64',
 ]
+# the analysis entry points (snp_diversity.py, call_consensus.py): bound above like the rest, listed by themselves
+SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
+                 'midas_sites_parse_cell', 'midas_sites_scan']
 
 
 def deflate_rows(text: bytes, row_begin, tail_begin) -> bytes:
@@ -812,6 +821,88 @@ def format_repr_f64(values) -> list:
     return out[:n.value].tobytes().decode().split('\n')[:-1]
 
 
+SITES_WEIGHT, SITES_ROUND, SITES_POOLED, SITES_PER_GENE, SITES_MASK_ONLY, SITES_SEQ, SITES_SUMS = 1, 2, 4, 8, 16, 32, 64
+
+
+class SitesTables:
+    """One species directory of `merge_midas.py snps` (midas_sites_tables_*): snps_summary.txt and snps_info.txt as columns,
+    snps_freq.txt / snps_depth.txt mapped as text.  String columns are (.x_pool uint8, .x_off int64) pairs read through
+    .strings(name); .freq_text / .depth_text are the matrices' rows after the header line.  Views owned by the handle."""
+
+    STRING_COLUMNS = ('sample_id', 'site_id', 'ref_allele', 'major_allele', 'minor_allele', 'locus_type', 'site_type', 'gene_id',
+                      'matrix_sample_id')
+
+    def __init__(self, indir: str):
+        lib = load_library()
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        st = lib.midas_sites_tables_open(indir.encode(), C.byref(h), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_sites_tables_open failed")
+        self._owner = _GenesOwner(lib, h, 'midas_sites_tables_close')
+        self.dir = indir
+        counts = (C.c_int64 * 8)()
+        lib.midas_sites_tables_counts(h, counts)
+        self.n_samples, self.n_sites, self.n_genes, self.n_columns = (int(counts[k]) for k in range(4))
+        self.freq_columns = int(counts[6])
+        ptrs, sizes = (C.c_void_p * 25)(), (C.c_int64 * 10)()
+        lib.midas_sites_tables_columns(h, ptrs, sizes)
+        col = lambda k, n, dt: np.asarray(_Column(self._owner, ptrs[k] or 0, n, dt))
+        rows = (self.n_samples, self.n_sites, self.n_sites, self.n_sites, self.n_sites, self.n_sites, self.n_sites, self.n_genes,
+                self.n_columns)
+        self._str = {}
+        for k, name in enumerate(self.STRING_COLUMNS):
+            self._str[name] = (col(2 * k, int(sizes[k]), np.uint8), col(2 * k + 1, rows[k] + 1, np.int64))
+        self.mean_coverage = col(18, self.n_samples, np.float64)
+        self.fraction_covered = col(19, self.n_samples, np.float64)
+        self.gene = col(20, self.n_sites, np.int32)
+        self.freq_text = col(21, int(counts[4]), np.uint8)
+        self.depth_text = col(22, int(counts[5]), np.uint8)
+
+    def column(self, name: str):
+        """(pool uint8, offsets int64) of a string column."""
+        return self._str[name]
+
+    def strings(self, name: str) -> list:
+        pool, off = self._str[name]
+        text = pool.tobytes().decode('utf-8', errors='surrogateescape')
+        if len(text) == pool.shape[0]:
+            return [text[int(off[k]):int(off[k + 1])] for k in range(off.shape[0] - 1)]
+        raw = pool.tobytes()
+        return [raw[int(off[k]):int(off[k + 1])].decode('utf-8', errors='surrogateescape') for k in range(off.shape[0] - 1)]
+
+    def equals(self, name: str, value: str) -> np.ndarray:
+        """Per row: the string column equals value (bool), without building Python strings."""
+        pool, off = self._str[name]
+        v = np.frombuffer(value.encode(), np.uint8)
+        n = off.shape[0] - 1
+        hit = (off[1:] - off[:-1]) == v.shape[0]
+        for k in range(v.shape[0]):
+            idx = np.minimum(off[:-1] + k, max(pool.shape[0] - 1, 0))
+            hit &= (pool[idx] == v[k]) if pool.shape[0] else np.zeros(n, bool)
+        return hit
+
+    def first_bytes(self, name: str):
+        """(first byte of every string, or 0 for an empty one; the lengths)."""
+        pool, off = self._str[name]
+        ln = off[1:] - off[:-1]
+        if pool.shape[0] == 0:
+            return np.zeros(ln.shape[0], np.uint8), ln
+        first = pool[np.minimum(off[:-1], pool.shape[0] - 1)].copy()
+        first[ln == 0] = 0
+        return first, ln
+
+
+def parse_cell(text: bytes, kind: str):
+    """float() ('freq') or int() ('depth') of a matrix cell by the library's exact host parser; None when it is no number."""
+    lib = load_library()
+    if kind == 'freq':
+        out = C.c_double(0)
+        return float(out.value) if lib.midas_sites_parse_cell(0, text, len(text), C.byref(out)) == 0 else None
+    out = C.c_int64(0)
+    return int(out.value) if lib.midas_sites_parse_cell(1, text, len(text), C.byref(out)) == 0 else None
+
+
 def write_bam(path, ref_names, ref_lengths, refid, reads, level=6, threads=0):
     """The native BAM writer (midas_bam_write): records in the given order, names "r<i>", aux NM + YT:Z:UU -- the bytes of
     midas_amd/bam.py's pure-Python writer, made by all cores."""
@@ -1236,6 +1327,67 @@ class Context:
         res = {k: v[:r] for k, v in out.items()}
         res['kernel_ms'] = float(ms.value)
         return res
+
+    def sites_scan(self, freq_text, depth_text, site_mask, sample_col, mean_depth, site_depth: int, site_ratio: float,
+                   allele_support: float, site_prev: float, site_maf: float, snp_maf: float = 0.01, max_sites: int = -1,
+                   flags: int = 0, site_gene=None, n_genes: int = 0, minor=None, major=None, group_rows: int = 0,
+                   chunk_bytes: int = 0, dump: bool = False, dump_keep: bool = False):
+        """midas_sites_scan(): the per-site loop of snp_diversity.py / call_consensus.py over the text rows of snps_freq.txt
+        and snps_depth.txt (uint8 arrays, header line excluded).  site_mask [N] uint8; sample_col / mean_depth [S].  -> dict
+        (n_sites, n_kept, side_freq, side_depth, groups, no_gene, ms [8]; with SITES_SUMS pi f64, snps / sites / depth i64
+        [chains, genes]; with SITES_SEQ seq uint8 [S, n_kept]; with dump: freq f64 / depthv i64 [S, n_sites], keep uint8 and
+        pooled f64 [n_sites]; with dump_keep: keep alone).  A malformed row raises MidasSnpsError with .bad = (matrix 1|2, data row, sample or -1)."""
+        ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
+        dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
+        mask = np.ascontiguousarray(site_mask, dtype=np.uint8)
+        N = int(mask.shape[0])
+        cols = np.ascontiguousarray(sample_col, dtype=np.int32)
+        mean = np.ascontiguousarray(mean_depth, dtype=np.float64)
+        S = int(cols.shape[0])
+        assert mean.shape[0] == S and S >= 1
+        pooled, per_gene = bool(flags & SITES_POOLED), bool(flags & SITES_PER_GENE)
+        gene = np.ascontiguousarray(site_gene, dtype=np.int32) if per_gene else None
+        assert gene is None or gene.shape[0] == N
+        G = int(n_genes) if per_gene else 1
+        chains = 1 if pooled else S
+        cap = N if max_sites < 0 else min(N, int(max_sites))
+        mi = np.ascontiguousarray(minor, dtype=np.uint8) if flags & SITES_SEQ else None
+        ma = np.ascontiguousarray(major, dtype=np.uint8) if flags & SITES_SEQ else None
+        assert mi is None or (mi.shape[0] == N and ma.shape[0] == N)
+        fp = np.array([site_ratio, allele_support, site_prev, site_maf, snp_maf], np.float64)
+        ip = np.array([site_depth, max_sites, flags, G if per_gene else 0, group_rows, chunk_bytes, cap, 0], np.int64)
+        out = {}
+        if flags & SITES_SUMS:
+            out.update(pi=np.zeros((chains, G), np.float64), snps=np.zeros((chains, G), np.int64), sites=np.zeros((chains, G), np.int64),
+                       depth=np.zeros((chains, G), np.int64))
+        seq = np.empty((S, cap), np.uint8) if flags & SITES_SEQ else None
+        if dump:
+            out.update(freq=np.zeros((S, N), np.float64), depthv=np.zeros((S, N), np.int64), keep=np.zeros(N, np.uint8),
+                       pooled=np.zeros(N, np.float64))
+        elif dump_keep:
+            out.update(keep=np.zeros(N, np.uint8))
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_sites_scan(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], N, p(mask), p(gene), p(mi), p(ma), S, p(cols),
+                                        p(mean), p(fp), p(ip), p(out.get('pi')), p(out.get('snps')), p(out.get('sites')),
+                                        p(out.get('depth')), p(seq), p(out.get('freq')), p(out.get('depthv')), p(out.get('keep')),
+                                        p(out.get('pooled')), p(stats), p(ms))
+        if st != 0:
+            try:
+                self._check(st)
+            except MidasSnpsError as e:
+                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
+                raise
+        n = int(stats[0])
+        out.update(n_sites=n, n_kept=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]), groups=int(stats[7]),
+                   no_gene=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), ms=ms.tolist())
+        if seq is not None:
+            out['seq'] = seq[:, :out['n_kept']]
+        if dump:
+            out.update(freq=out['freq'][:, :n], depthv=out['depthv'][:, :n], keep=out['keep'][:n], pooled=out['pooled'][:n])
+        elif dump_keep:
+            out['keep'] = out['keep'][:n]
+        return out
 
     def batch(self, contigs: ContigTable, reads: ReadsSoA) -> "Batch":
         return Batch(self, contigs, reads)

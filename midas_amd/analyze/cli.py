@@ -1,0 +1,163 @@
+"""The command lines of snp_diversity.py and call_consensus.py: the reference's option names, defaults, check_args messages
+and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146), shared where they agree."""
+import argparse
+import os
+import sys
+
+INF = float('Inf')
+
+SAMPLE_OPTIONS = [
+    (['--sample_depth'], dict(dest='sample_depth', type=float, default=0.0, metavar='FLOAT', help="samples with at least this mean_coverage (0.0)")),
+    (['--sample_cov'], dict(dest='fract_cov', type=float, default=0.0, metavar='FLOAT',
+                            help="samples with at least this fraction of the reference covered by a read (0.0)")),
+    (['--max_samples'], dict(type=int, default=INF, metavar='INT', help="use at most this many samples, in snps_summary.txt order (all)")),
+    (['--keep_samples'], dict(type=str, metavar='STR', help="comma-separated sample ids to use; the other sample filters still apply")),
+    (['--exclude_samples'], dict(type=str, metavar='STR', help="comma-separated sample ids to leave out")),
+]
+
+SITE_OPTIONS = [
+    (['--site_list'], dict(metavar='PATH', type=str, help="file with one site id per line: only these sites")),
+    (['--site_depth'], dict(type=int, default=2, metavar='INT', help="a sample counts at a site with at least this many reads (2)")),
+    (['--site_prev'], dict(type=float, default=0.0, metavar='FLOAT',
+                           help="keep sites where at least this fraction of the samples counts (0.0: every site;\n1.0: sites covered in all samples)")),
+    (['--site_maf'], dict(type=float, default=0.0, metavar='FLOAT',
+                          help="keep sites whose pooled minor allele frequency is at least this (0.0: invariant sites too)")),
+    (['--site_ratio'], dict(type=float, default=INF, metavar='FLOAT',
+                            help="a sample counts at a site with at most this depth / mean_coverage (no limit)")),
+    (['--allele_support'], dict(type=float, default=0.5, metavar='FLOAT',
+                                help="a sample counts at a site when its commoner allele has at least this share of the reads (0.5)")),
+    (['--locus_type'], dict(choices=['CDS', 'RNA', 'IGR'], help="only sites in coding genes (CDS), rRNA / tRNA genes (RNA) or between genes (IGR)")),
+    (['--site_type'], dict(choices=['1D', '2D', '3D', '4D'], help="with --locus_type CDS: only sites of this degeneracy (4D synonymous, 1D not)")),
+    (['--max_sites'], dict(type=int, default=INF, metavar='INT', help="stop after this many retained sites (all)")),
+]
+
+DIVERSITY_OPTIONS = [
+    (['--genomic_type'], dict(choices=['genome-wide', 'per-gene'], default='genome-wide', help="one result for the genome, or one per gene (genome-wide)")),
+    (['--sample_type'], dict(choices=['per-sample', 'pooled-samples'], default='per-sample',
+                             help="one result per sample, or one for the samples pooled (per-sample)")),
+    (['--weight_by_depth'], dict(action='store_true', default=False, help="pooled-samples: weight each sample by its depth at the site")),
+    (['--rand_reads'], dict(type=int, metavar='INT', help="(resampling N reads per site and sample is not part of this build)")),
+    (['--replace_reads'], dict(action='store_true', default=False, help="(not part of this build)")),
+    (['--rand_samples'], dict(type=int, metavar='INT', help="use a random subset of N samples (numpy's global random stream)")),
+    (['--rand_sites'], dict(type=float, metavar='FLOAT', help="use a random share X of the sites (Python's global random stream)")),
+    (['--snp_maf'], dict(type=float, metavar='FLOAT', default=0.01, help="a site is a SNP at or above this minor allele frequency (0.01)")),
+    (['--consensus'], dict(action='store_true', default=False, help="round every frequency to 0 or 1 before anything is computed from it")),
+]
+
+DEVICE_OPTIONS = [
+    (['--group_rows'], dict(type=int, default=0, metavar='INT', help="matrix rows on the device at a time (0: what its memory holds);\nthe output does not depend on it")),
+]
+
+
+def _parser(prog, description, epilog, groups):
+    parser = argparse.ArgumentParser(prog=prog, formatter_class=argparse.RawTextHelpFormatter, description=description, epilog=epilog)
+    parser.add_argument('indir', metavar='PATH', type=str,
+                        help="one species directory written by `merge_midas.py snps` (holds snps_freq.txt, snps_depth.txt,\nsnps_info.txt, snps_summary.txt)")
+    parser.add_argument('--out', metavar='PATH', type=str, default='/dev/stdout', help="output file (/dev/stdout)")
+    for title, options in groups:
+        group = parser.add_argument_group(title)
+        for flags, kw in options:
+            group.add_argument(*flags, **kw)
+    return parser
+
+
+def diversity_arguments(argv=None):
+    parser = _parser('snp_diversity.py',
+                     "Nucleotide diversity (pi) and SNP density of one species from its merged SNP tables:\n"
+                     "genome-wide or per gene, per sample or for the samples pooled.  Run `merge_midas.py snps` first.",
+                     "examples:\n"
+                     "  snp_diversity.py OUT/species_1 --genomic_type genome-wide --sample_type per-sample --out pi.txt\n"
+                     "  snp_diversity.py OUT/species_1 --genomic_type per-gene --sample_type pooled-samples --locus_type CDS --out pi.txt\n"
+                     "  snp_diversity.py OUT/species_1 --sample_type pooled-samples --locus_type CDS --site_type 4D --out pi.txt\n"
+                     "  snp_diversity.py OUT/species_1 --max_sites 10000 --out pi.txt",
+                     [("Diversity options", DIVERSITY_OPTIONS), ("Sample filters", SAMPLE_OPTIONS), ("Site filters", SITE_OPTIONS),
+                      ("Device", DEVICE_OPTIONS)])
+    return vars(parser.parse_args(argv))
+
+
+def consensus_arguments(argv=None):
+    parser = _parser('call_consensus.py',
+                     "One consensus sequence per sample over the retained sites of a species, as a multi-FASTA (for trees).\n"
+                     "Run `merge_midas.py snps` first.",
+                     "examples:\n"
+                     "  call_consensus.py OUT/species_1 --out seqs.fa --site_maf 0.01 --site_depth 5 --site_prev 0.90 \\\n"
+                     "      --sample_depth 10 --sample_cov 0.40 --site_ratio 5.0\n"
+                     "  call_consensus.py OUT/species_1 --out seqs.fa --max_sites 10000",
+                     [("Sample filters", SAMPLE_OPTIONS), ("Site filters", SITE_OPTIONS), ("Device", DEVICE_OPTIONS)])
+    return vars(parser.parse_args(argv))
+
+
+def print_args(args, script):
+    """The reference's argument block, line for line (its last but one line prints locus_type under the name site_type)."""
+    rows = [("Command: %s" % ' '.join(sys.argv)), "Script: %s" % script, "Input directory: %s" % args['indir'], "Output file: %s" % args['out']]
+    blocks = []
+    if script == 'snp_diversity.py':
+        blocks.append(("Diversity options:", ['genomic_type', 'sample_type', 'weight_by_depth', 'rand_reads', 'replace_reads', 'rand_samples',
+                                              'rand_sites', 'snp_maf', 'consensus']))
+    blocks.append(("Sample filters:", ['sample_depth', 'fract_cov', 'max_samples', 'keep_samples', 'exclude_samples']))
+    blocks.append(("Site filters:", ['site_list', 'site_depth', 'site_prev', 'site_maf', 'site_ratio', 'allele_support', 'locus_type', 'site_type',
+                                     'max_sites']))
+    for title, names in blocks:
+        rows.append(title)
+        for name in names:
+            rows.append("  %s: %s" % (name, args['locus_type' if name == 'site_type' else name]))
+    sys.stdout.write('\n'.join(rows) + '\n')
+
+
+def _exit(message):
+    sys.exit("\nError: %s\n" % message)
+
+
+def _common_checks(args):
+    if args['max_sites'] < 1:
+        _exit("--max_sites must be >= 1 to calculate nucleotide variation")
+    if args['max_samples'] < 1:
+        _exit("--max_samples must be >= 1 to calculate nucleotide variation")
+    if args['site_ratio'] < 0:
+        _exit("--site_ratio cannot be a negative number")
+    if args['site_depth'] < 0:
+        _exit("--site_depth cannot be a negative number")
+    if args['sample_depth'] < 0:
+        _exit("--sample_depth cannot be a negative number")
+    if not 0 <= args['site_maf'] <= 1:
+        _exit("--site_maf must be between 0 and 1")
+    if not 0 <= args['site_prev'] <= 1:
+        _exit("--site_prev must be between 0 and 1")
+    if not 0 <= args['fract_cov'] <= 1:
+        _exit("--fract_cov must be between 0 and 1")
+
+
+def check_diversity_args(args):
+    """check_args of snp_diversity.py, in its order.  Its --rand_reads comparison cannot run under Python 3 without the
+    option; here the option itself is out: resampling reads needs numpy's legacy random stream per (site, sample)."""
+    if args['rand_reads'] is not None or args['replace_reads']:
+        _exit("--rand_reads / --replace_reads are not part of this build")
+    if not os.path.isdir(args['indir']):
+        _exit("Specified input directory '%s' does not exist" % args['indir'])
+    if args['site_depth'] < 2:
+        _exit("--site_depth must be >=2 to calculate nucleotide variation")
+    _common_checks(args)
+    if args['rand_sites'] and (args['rand_sites'] < 0 or args['rand_sites'] > 1):
+        _exit("--rand_sites must be between 0 and 1")
+    if args['locus_type'] != 'CDS' and args['genomic_type'] == 'per-gene':
+        _exit("--locus_type must be CDS if --genomic_type is per-gene")
+    if args['locus_type'] != 'CDS' and args['site_type'] is not None:
+        _exit("--locus_type must be CDS if --site_type is specified")
+
+
+def check_consensus_args(args):
+    if not os.path.isdir(args['indir']):
+        _exit("Specified input directory '%s' does not exist" % args['indir'])
+    if args['site_depth'] < 1:
+        _exit("--site_depth must be >=1")
+    _common_checks(args)
+
+
+COPYRIGHT = ["", "MIDAS: Metagenomic Intra-species Diversity Analysis System", "analysis commands on AMD Instinct MI355X (midas_amd %s)",
+             "after github.com/snayfach/MIDAS, Copyright (C) 2015-2016 Stephen Nayfach",
+             "Freely distributed under the GNU General Public License (GPLv3)", ""]
+
+
+def print_copyright():
+    import midas_amd
+    sys.stdout.write('\n'.join(COPYRIGHT) % midas_amd.__version__ + '\n')

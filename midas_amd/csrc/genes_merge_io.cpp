@@ -30,6 +30,7 @@
 #include <zlib.h>
 
 #include "../../include/midas_snps.h"
+#include "text_numbers.h"
 #include "workers.h"
 
 namespace {
@@ -86,57 +87,8 @@ int last_column(const std::vector<std::string_view>& header, const char* name) {
   return -1;
 }
 
-bool py_space(char c) { return c == ' ' || (c >= '\t' && c <= '\r') || (c >= 0x1c && c <= 0x1f); }
-
-std::string_view trim(std::string_view v) {
-  size_t a = 0, b = v.size();
-  while (a < b && py_space(v[a])) ++a;
-  while (b > a && py_space(v[b - 1])) --b;
-  return v.substr(a, b - a);
-}
-
-// float(field): true and *out, or false for a spelling this build does not take
-bool parse_f64(std::string_view v, double* out) {
-  v = trim(v);
-  if (v.empty()) return false;
-  size_t i = 0;
-  if (v[0] == '+' || v[0] == '-') i = 1;
-  if (i >= v.size() || v[i] == '+' || v[i] == '-') return false;
-  for (char c : v)
-    if (c == '(' || c == '_') return false;       // nan(...) / digit separators
-  const std::string_view body = v.substr(i);
-  double x = 0.0;
-  const auto r = std::from_chars(body.data(), body.data() + body.size(), x, std::chars_format::general);
-  if (r.ptr != body.data() + body.size()) return false;
-  if (r.ec == std::errc::result_out_of_range) {    // overflow -> inf, underflow -> 0 (Python's float())
-    const std::string z(body);
-    x = strtod(z.c_str(), nullptr);
-  } else if (r.ec != std::errc()) {
-    return false;
-  }
-  *out = v[0] == '-' ? -x : x;
-  return true;
-}
-
-bool parse_i64(std::string_view v, int64_t* out) {
-  v = trim(v);
-  size_t i = 0;
-  if (!v.empty() && (v[0] == '+' || v[0] == '-')) i = 1;
-  if (i >= v.size()) return false;
-  for (size_t k = i; k < v.size(); ++k)
-    if (v[k] < '0' || v[k] > '9') return false;
-  uint64_t u = 0;
-  const auto r = std::from_chars(v.data() + i, v.data() + v.size(), u);
-  if (r.ec != std::errc() || r.ptr != v.data() + v.size()) return false;
-  if (v[0] == '-') {
-    if (u > (uint64_t)1 << 63) return false;
-    *out = (int64_t)(0 - u);
-  } else {
-    if (u > (uint64_t)INT64_MAX) return false;
-    *out = (int64_t)u;
-  }
-  return true;
-}
+using midas::parse_f64;
+using midas::parse_i64;
 
 template <class F>
 void for_each_index(int64_t n, int threads, F&& fn) {

@@ -1,0 +1,838 @@
+// snp_diversity.py / call_consensus.py on MI355X: the per-site loop of midas/analyze/parse_snps.py and of the
+// two scripts over it, for all rows of snps_freq.txt / snps_depth.txt at once.  The matrices arrive as TEXT; parsing them is
+// most of the work, so it happens here.
+//
+//   chunks   a run of bytes of each matrix is uploaded; its complete rows are the group's candidates
+//   index    newlines counted per 16 bytes, the library's exclusive scan (device_sort.hip), newline k's position -> ends[k]
+//   parse    one thread a row walks its fields; a cell of a selected sample is converted on the spot when it has the shape
+//            [+-]digits[.digits][e[+-]digits] with a mantissa below 2^53 and a power of ten within +-22 (one exact
+//            int -> fp64 conversion, one IEEE multiply or divide: correctly rounded), or [+-]digits up to 18 of them for
+//            the depth; every other cell goes to a side list, which the host converts with its exact parser and patches
+//            in before the site kernel runs.  Values land sample-major, [sample][row]
+//   site     one thread a row: GenomicSite.flag_samples, call_consensus, summary_stats, filter, in snps_summary.txt order.
+//            The unweighted pooled frequency is numpy's pairwise add-reduce (blocks of 128, eight partial sums) over the
+//            kept values, consumed in order; the weighted one is a left-to-right sum
+//   order    --max_sites: exclusive scan of the keep flags, a site stays while fewer than max_sites were kept before it
+//   sums     one wave a chain (a sample, or the pool): 64 rows loaded coalesced, then folded in lane order -- the fp64 sum
+//            is the sequential one, bit for bit; per-gene chains switch accumulators where the gene index changes.
+//            Accumulators live in device memory and carry from group to group
+//   seq      call_consensus.py: one byte per (retained site, sample), sample-major
+// This file is compiled with -ffp-contract=off (build.py): 2*f*(1-f) and d*f round twice, as the interpreter does.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <string_view>
+#include <vector>
+
+#include "../../include/midas_snps.h"
+#include "ctx_internal.h"
+#include "kernels.h"
+#include "text_numbers.h"
+
+namespace midas {
+namespace {
+
+struct SideCell { uint32_t row, slot, off, len; };
+
+constexpr unsigned long long kNoBad = ~0ull;
+
+__device__ __forceinline__ uint32_t newline_bytes(uint32_t w) {     // 0x80 in every byte of w that is '\n'
+  const uint32_t x = w ^ 0x0A0A0A0Au;
+  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+}
+
+// text is padded with zero bytes to n16 * 16
+__global__ __launch_bounds__(256) void ss_count_kernel(const uint4* text, long long n16, uint32_t* counts) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n16) return;
+  const uint4 v = text[i];
+  counts[i] = __popc(newline_bytes(v.x)) + __popc(newline_bytes(v.y)) + __popc(newline_bytes(v.z)) + __popc(newline_bytes(v.w));
+}
+
+// ends[k] = offset of newline k, for k < cap
+__global__ __launch_bounds__(256) void ss_ends_kernel(const uint4* text, long long n16, const uint32_t* prefix, uint32_t cap, uint32_t* ends) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n16) return;
+  const uint4 v = text[i];
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  uint32_t k = prefix[i];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    uint32_t m = newline_bytes(w[q]);
+    while (m) {
+      const int b = __ffs(m) - 1;          // bit 7, 15, 23 or 31
+      if (k < cap) ends[k] = (uint32_t)(16 * i + 4 * q + (b >> 3));
+      ++k;
+      m &= m - 1;
+    }
+  }
+}
+
+__device__ __forceinline__ bool is_digit(char c) { return c >= '0' && c <= '9'; }
+
+// float(cell) for [+-]digits[.digits][e[+-]digits], mantissa < 2^53, |power of ten| <= 22: exact by construction
+__device__ bool fast_f64(const char* s, int n, double* out) {
+  static const double p10[23] = {1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
+                                 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
+  if (n <= 0) return false;
+  int i = 0;
+  bool neg = false;
+  if (s[0] == '+' || s[0] == '-') { neg = s[0] == '-'; i = 1; }
+  unsigned long long m = 0;
+  constexpr unsigned long long lim = (1ull << 53) - 1;
+  int nd = 0, nfrac = 0;
+  for (; i < n && is_digit(s[i]); ++i, ++nd) {
+    const unsigned d = (unsigned)(s[i] - '0');
+    if (m > (lim - d) / 10) return false;
+    m = m * 10 + d;
+  }
+  if (nd == 0) return false;
+  if (i < n && s[i] == '.') {
+    for (++i; i < n && is_digit(s[i]); ++i, ++nfrac) {
+      const unsigned d = (unsigned)(s[i] - '0');
+      if (m > (lim - d) / 10) return false;
+      m = m * 10 + d;
+    }
+    if (nfrac == 0) return false;
+  }
+  int ex = 0;
+  if (i < n && (s[i] == 'e' || s[i] == 'E')) {
+    ++i;
+    bool eneg = false;
+    if (i < n && (s[i] == '+' || s[i] == '-')) { eneg = s[i] == '-'; ++i; }
+    int ne = 0;
+    for (; i < n && is_digit(s[i]); ++i, ++ne) {
+      if (ne == 3) return false;
+      ex = ex * 10 + (s[i] - '0');
+    }
+    if (ne == 0) return false;
+    if (eneg) ex = -ex;
+  }
+  if (i != n) return false;
+  double x = (double)(long long)m;
+  if (m != 0) {
+    const int e10 = ex - nfrac;
+    if (e10 < -22 || e10 > 22) return false;
+    x = e10 < 0 ? __ddiv_rn(x, p10[-e10]) : __dmul_rn(x, p10[e10]);
+  }
+  *out = neg ? -x : x;
+  return true;
+}
+
+// int(cell) for [+-]digits, at most 18 digits
+__device__ bool fast_i64(const char* s, int n, long long* out) {
+  if (n <= 0) return false;
+  int i = 0;
+  bool neg = false;
+  if (s[0] == '+' || s[0] == '-') { neg = s[0] == '-'; i = 1; }
+  if (i == n || n - i > 18) return false;
+  long long m = 0;
+  for (; i < n; ++i) {
+    if (!is_digit(s[i])) return false;
+    m = m * 10 + (s[i] - '0');
+  }
+  *out = neg ? -m : m;
+  return true;
+}
+
+struct ParseP {
+  const char* text;            // the chunk
+  const uint32_t* ends;        // newline offsets of its rows
+  long long g, stride;         // rows to parse; row stride of a sample's values
+  const int32_t* col_slot;     // [n_cols] matrix column -> selected sample, or -1
+  int n_cols;                  // columns a row must have (1 + the largest selected column)
+  void* val;                   // [n_samples][stride] f64 or i64
+  SideCell* side;
+  uint32_t* side_n;
+  uint32_t side_cap;
+  unsigned long long* bad;     // min over (row << 32 | slot + 1); slot + 1 == 0: the row is short
+};
+
+template <bool kInt>
+__global__ __launch_bounds__(256) void ss_parse_kernel(ParseP p) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= p.g) return;
+  const uint32_t b = r == 0 ? 0u : p.ends[r - 1] + 1u;
+  uint32_t e = p.ends[r];
+  const char* t = p.text;
+  if (e > b && t[e - 1] == '\r') --e;
+  uint32_t q = b;
+  while (q < e && t[q] != '\t') ++q;         // the site id
+  for (int c = 0; c < p.n_cols; ++c) {
+    if (q >= e) {                            // no tab left: the row lacks column c
+      atomicMin(p.bad, (unsigned long long)r << 32);
+      return;
+    }
+    const uint32_t fs = ++q;
+    while (q < e && t[q] != '\t') ++q;
+    const int slot = p.col_slot[c];
+    if (slot < 0) continue;
+    const int len = (int)(q - fs);
+    const long long at = (long long)slot * p.stride + r;
+    bool ok;
+    if (kInt) {
+      long long v = 0;
+      ok = fast_i64(t + fs, len, &v);
+      static_cast<long long*>(p.val)[at] = v;
+    } else {
+      double v = 0.0;
+      ok = fast_f64(t + fs, len, &v);
+      static_cast<double*>(p.val)[at] = v;
+    }
+    if (!ok) {
+      const uint32_t k = atomicAdd(p.side_n, 1u);
+      if (k < p.side_cap) p.side[k] = SideCell{(uint32_t)r, (uint32_t)slot, fs, (uint32_t)len};
+    }
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void ss_patch_kernel(T* val, const long long* at, const T* v, long long n) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) val[at[i]] = v[i];
+}
+
+struct SiteP {
+  const double* fv;            // [S][stride]
+  const long long* dv;         // [S][stride]
+  uint8_t* cell;               // [S][stride] bit 0: the sample is kept at the site
+  const double* mean_depth;    // [S]
+  const uint8_t* mask;         // [g] what the info table and the options decide (already offset to the group)
+  long long g, stride;
+  int S;
+  long long site_depth;
+  double site_ratio, allele_support, site_prev, site_maf;
+  int weight, round_freq, mask_only;
+  uint32_t* keep;              // [g] the site's keep decision
+  double* pooled;              // [g]
+};
+
+// the kept frequencies of one site, in sample order
+struct KeptIter {
+  const double* fv;
+  const uint8_t* cell;
+  long long stride;
+  int s, round_freq;
+  __device__ double next() {
+    while (!(cell[(long long)s * stride] & 1)) ++s;
+    const double f = fv[(long long)s * stride];
+    ++s;
+    return round_freq ? rint(f) : f;
+  }
+};
+
+// numpy's pairwise_sum over n <= 128 values (eight partial sums, then the tail)
+__device__ double pairwise_leaf(KeptIter& it, long long n) {
+  if (n < 8) {
+    double res = 0.0;
+    for (long long i = 0; i < n; ++i) res += it.next();
+    return res;
+  }
+  double r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = it.next();
+  long long i = 8;
+  for (; i < n - (n % 8); i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] += it.next();
+  }
+  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += it.next();
+  return res;
+}
+
+// numpy's add.reduce of n values: halves cut at multiples of eight down to blocks of at most 128, left before right
+__device__ double pairwise_sum(KeptIter& it, long long n) {
+  struct Frame { long long n; double left; int st; };
+  Frame stk[40];
+  int sp = 0;
+  stk[sp++] = Frame{n, 0.0, 0};
+  double ret = 0.0;
+  while (sp > 0) {
+    Frame& f = stk[sp - 1];
+    long long n2 = f.n / 2;
+    n2 -= n2 % 8;
+    if (f.st == 0) {
+      if (f.n <= 128) {
+        ret = pairwise_leaf(it, f.n);
+        --sp;
+      } else {
+        f.st = 1;
+        stk[sp++] = Frame{n2, 0.0, 0};
+      }
+    } else if (f.st == 1) {
+      f.left = ret;
+      f.st = 2;
+      stk[sp++] = Frame{f.n - n2, 0.0, 0};
+    } else {
+      ret = f.left + ret;
+      --sp;
+    }
+  }
+  return ret;
+}
+
+__global__ __launch_bounds__(256) void ss_site_kernel(SiteP p) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= p.g) return;
+  long long count = 0, dsum = 0;
+  double msum = 0.0;
+  for (int s = 0; s < p.S; ++s) {
+    const long long at = (long long)s * p.stride + r;
+    const long long d = p.dv[at];
+    const double f = p.fv[at];
+    bool keep = true;
+    if (d < p.site_depth) keep = false;
+    if (__ddiv_rn((double)d, p.mean_depth[s]) > p.site_ratio) keep = false;
+    double m = f;                               // max(f, 1 - f) as Python's max: the first wins unless the second is greater
+    if (1.0 - f > m) m = 1.0 - f;
+    if (m < p.allele_support) keep = false;
+    p.cell[at] = keep ? 1 : 0;
+    if (keep) {
+      ++count;
+      if (p.weight) {
+        const double f2 = p.round_freq ? rint(f) : f;
+        dsum += d;
+        msum += (double)d * f2;
+      }
+    }
+  }
+  double pooled = 0.0;
+  if (count > 0) {
+    if (p.weight) {
+      pooled = __ddiv_rn(msum, (double)dsum);
+    } else {
+      KeptIter it{p.fv + r, p.cell + r, p.stride, 0, p.round_freq};
+      pooled = __ddiv_rn(pairwise_sum(it, count), (double)count);
+    }
+  }
+  bool k = p.mask[r] != 0;
+  if (!p.mask_only) {
+    const double prev = __ddiv_rn((double)count, (double)p.S);
+    if (p.site_prev != 0.0 && prev < (1e-6 > p.site_prev ? 1e-6 : p.site_prev)) k = false;
+    if (p.site_maf != 0.0 && pooled < p.site_maf) k = false;
+  }
+  p.keep[r] = k ? 1u : 0u;
+  p.pooled[r] = pooled;
+}
+
+// keep[r] -> final: still below max_sites; rank[r] = kept sites of the group before r.  The row that fills max_sites is
+// reported: the reference reads one more row after it and stops.
+__global__ __launch_bounds__(256) void ss_order_kernel(const uint32_t* keep, const uint32_t* rank, long long g, long long kept_before,
+                                                       long long max_sites, uint8_t* final_keep, long long* last_row) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= g) return;
+  const long long pos = kept_before + rank[r];
+  const bool k = keep[r] != 0 && (max_sites < 0 || pos < max_sites);
+  final_keep[r] = k ? 1 : 0;
+  if (k && max_sites >= 0 && pos == max_sites - 1) *last_row = r;
+}
+
+struct SumP {
+  const double* fv;            // [S][stride], or the pooled frequency [g] (pooled != 0)
+  const long long* dv;
+  const uint8_t* cell;
+  const uint8_t* final_keep;   // [g]
+  const int32_t* gene;         // [g] (already offset), per_gene only
+  long long g, stride;
+  int pooled, per_gene, round_freq;
+  long long n_genes;           // accumulators per chain (1 genome-wide)
+  double snp_maf;
+  double* pi;                  // [chains][n_genes]
+  long long* snps;
+  long long* sites;
+  long long* depth;
+  unsigned long long* no_gene; // kept sites without a gene id in a per-gene run
+};
+
+// one wave per chain
+__global__ __launch_bounds__(64) void ss_sums_kernel(SumP p) {
+  const int chain = blockIdx.x, lane = threadIdx.x;
+  const long long base = (long long)chain * p.n_genes;
+  long long cur = p.per_gene ? -1 : 0;
+  double pi = 0.0;
+  long long snps = 0, sites = 0, depth = 0;
+  if (!p.per_gene) { pi = p.pi[base]; snps = p.snps[base]; sites = p.sites[base]; depth = p.depth[base]; }
+  for (long long r0 = 0; r0 < p.g; r0 += 64) {
+    const long long r = r0 + lane;
+    bool on = false;
+    double term = 0.0;
+    long long d = 0;
+    int snp = 0, gi = -1;
+    if (r < p.g && p.final_keep[r]) {
+      const long long at = (long long)chain * p.stride + r;
+      on = p.pooled ? true : (p.cell[at] & 1) != 0;
+      if (on) {
+        double f = p.pooled ? p.fv[r] : p.fv[at];
+        if (!p.pooled && p.round_freq) f = rint(f);
+        term = (2.0 * f) * (1.0 - f);
+        double m = f;                           // min(f, 1 - f) as Python's min
+        if (1.0 - f < m) m = 1.0 - f;
+        snp = m >= p.snp_maf ? 1 : 0;
+        d = p.pooled ? 0 : p.dv[at];
+        if (p.per_gene) gi = p.gene[r];
+      }
+    }
+    unsigned long long live = __ballot(on);
+    const int tlo = __double2loint(term), thi = __double2hiint(term);
+    while (live) {
+      const int k = __ffsll((long long)live) - 1;
+      live &= live - 1;
+      const double t = __hiloint2double(__builtin_amdgcn_readlane(thi, k), __builtin_amdgcn_readlane(tlo, k));
+      if (p.per_gene) {
+        const long long gk = __builtin_amdgcn_readlane(gi, k);
+        if (gk != cur) {
+          if (cur >= 0 && lane == 0) { p.pi[base + cur] = pi; p.snps[base + cur] = snps; p.sites[base + cur] = sites; p.depth[base + cur] = depth; }
+          cur = gk;
+          if (cur >= 0) { pi = p.pi[base + cur]; snps = p.snps[base + cur]; sites = p.sites[base + cur]; depth = p.depth[base + cur]; }
+        }
+        if (cur < 0) {
+          if (lane == 0 && chain == 0) atomicAdd(p.no_gene, 1ull);
+          continue;
+        }
+      }
+      pi += t;
+      snps += __builtin_amdgcn_readlane(snp, k);
+      sites += 1;
+      const unsigned dlo = (unsigned)__builtin_amdgcn_readlane((int)(d & 0xFFFFFFFFll), k);
+      const unsigned dhi = (unsigned)__builtin_amdgcn_readlane((int)(d >> 32), k);
+      depth += (long long)(((unsigned long long)dhi << 32) | dlo);
+    }
+  }
+  if (cur >= 0 && lane == 0) { p.pi[base + cur] = pi; p.snps[base + cur] = snps; p.sites[base + cur] = sites; p.depth[base + cur] = depth; }
+}
+
+// fetch_consensus for the retained sites of the group: seq[s][rank] (rank among the group's retained sites)
+__global__ __launch_bounds__(256) void ss_seq_kernel(const double* fv, const long long* dv, const uint8_t* cell, const uint8_t* final_keep,
+                                                     const uint32_t* rank, const char* minor, const char* major, long long g, long long stride,
+                                                     int S, uint8_t* seq) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= g || !final_keep[r]) return;
+  const long long pos = rank[r];
+  const char mi = minor[r], ma = major[r];
+  for (int s = 0; s < S; ++s) {
+    const long long at = (long long)s * stride + r;
+    char c = '-';
+    if ((cell[at] & 1) && dv[at] != 0) c = fv[at] >= 0.5 ? mi : ma;
+    seq[(long long)s * stride + pos] = (uint8_t)c;
+  }
+}
+
+int32_t ss_fail(midas_snps_ctx* ctx, int32_t st, const char* msg) {
+  ctx->set_error(msg);
+  return st;
+}
+
+#define SS_TRY(call)                                                                                             \
+  do {                                                                                                           \
+    hipError_t e__ = (call);                                                                                     \
+    if (e__ != hipSuccess) {                                                                                     \
+      char buf__[384];                                                                                           \
+      snprintf(buf__, sizeof buf__, "%s: %s", #call, hipGetErrorString(e__));                                    \
+      (void)hipGetLastError();                                                                                   \
+      return ss_fail(ctx, e__ == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP, buf__); \
+    }                                                                                                            \
+  } while (0)
+
+struct SsBufs {
+  std::vector<void*> ptrs;
+  ~SsBufs() { for (void* q : ptrs) (void)hipFree(q); }
+  template <class T> hipError_t get(T** out, size_t bytes) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+    if (e == hipSuccess) ptrs.push_back(q);
+    *out = static_cast<T*>(q);
+    return e;
+  }
+};
+
+struct SsEvents {
+  hipEvent_t e[8] = {};
+  ~SsEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+unsigned nblocks(long long n, long long per) { return (unsigned)((n + per - 1) / per); }
+
+// one matrix's chunk on the device: the text, its newline index
+struct Chunk {
+  const char* host = nullptr;
+  long long bytes = 0, at = 0;   // the file's body, where the next group starts
+  char* d_text = nullptr;
+  uint32_t* d_counts = nullptr;
+  uint32_t* d_ends = nullptr;
+  SideCell* d_side = nullptr;
+  uint32_t* d_side_n = nullptr;
+  unsigned long long* d_bad = nullptr;
+  long long n = 0;               // bytes of the chunk on the device (a final line without '\n' got one)
+  long long lines = 0;
+  bool at_eof = false;
+};
+
+}  // namespace
+}  // namespace midas
+
+using namespace midas;
+
+extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                    int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                                    const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                                    const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
+                                    int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
+                                    uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8) {
+  if (!ctx || freq_bytes < 0 || depth_bytes < 0 || (freq_bytes > 0 && !freq) || (depth_bytes > 0 && !depth) || n_sites_max < 0 ||
+      n_samples < 1 || !sample_col || !mean_depth || !fparams5 || !iparams8 || !out_stats16 || (n_sites_max > 0 && !site_mask))
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  const long long site_depth = iparams8[0], max_sites = iparams8[1], flags = iparams8[2], seq_cap = iparams8[6];
+  const long long n_genes_in = iparams8[3];
+  long long G = iparams8[4], chunk_bytes = iparams8[5];
+  const int weight = flags & MIDAS_SITES_WEIGHT ? 1 : 0, round_freq = flags & MIDAS_SITES_ROUND ? 1 : 0,
+            pooled = flags & MIDAS_SITES_POOLED ? 1 : 0, per_gene = flags & MIDAS_SITES_PER_GENE ? 1 : 0,
+            mask_only = flags & MIDAS_SITES_MASK_ONLY ? 1 : 0, want_seq = flags & MIDAS_SITES_SEQ ? 1 : 0,
+            want_sums = flags & MIDAS_SITES_SUMS ? 1 : 0;
+  const int S = n_samples;
+  if ((per_gene && (!site_gene || n_genes_in < 0)) || (want_seq && (!out_seq || !minor || !major || seq_cap < 0)) ||
+      (want_sums && (!out_pi || !out_snps || !out_sites || !out_depth)) || G < 0 || chunk_bytes < 0)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  int n_cols = 0;
+  for (int s = 0; s < S; ++s) {
+    if (sample_col[s] < 0) return MIDAS_SNPS_ERR_INVALID_ARG;
+    n_cols = std::max(n_cols, sample_col[s] + 1);
+  }
+  if (per_gene)
+    for (int64_t i = 0; i < n_sites_max; ++i)
+      if (site_gene[i] >= n_genes_in) return MIDAS_SNPS_ERR_INVALID_ARG;
+  ctx->clear_error();
+  ctx->err_read = -1;
+  for (int k = 0; k < 16; ++k) out_stats16[k] = 0;
+  out_stats16[4] = 0;
+  out_stats16[5] = -1;
+  out_stats16[6] = -1;
+  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = 0.f;
+  const long long n_genes = per_gene ? n_genes_in : 1;
+  const long long chains = pooled ? 1 : S;
+  const size_t n_acc = (size_t)(chains * n_genes);
+  if (want_sums)
+    for (size_t k = 0; k < n_acc; ++k) { out_pi[k] = 0.0; out_snps[k] = 0; out_sites[k] = 0; out_depth[k] = 0; }
+  if (n_sites_max == 0) return MIDAS_SNPS_OK;
+  std::vector<int32_t> col_slot((size_t)n_cols, -1);
+  for (int s = 0; s < S; ++s) {
+    if (col_slot[(size_t)sample_col[s]] >= 0) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "a matrix column is selected twice");
+    col_slot[(size_t)sample_col[s]] = s;
+  }
+  SS_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // ---- sizes: rows a group (G) and bytes a chunk, from the caller or from a quarter of the free device memory ---------------
+  constexpr long long kChunkMax = (1ll << 30);       // newline offsets are 32-bit
+  const long long per_row = (long long)S * (8 + 8 + 1 + 2 * (long long)sizeof(SideCell) + (want_seq ? 1 : 0)) + 4 + 4 + 4 + 8 + 1 + 8 + 8;
+  if (G == 0 || chunk_bytes == 0) {
+    size_t free_b = 0, total_b = 0;
+    SS_TRY(hipMemGetInfo(&free_b, &total_b));
+    const long long budget = (long long)(free_b / 4);
+    if (chunk_bytes == 0) chunk_bytes = std::min<long long>(kChunkMax, std::max<long long>(1 << 20, budget / 8));
+    if (G == 0) G = std::max<long long>(1, (budget - std::min(budget / 2, 5 * chunk_bytes / 2)) / per_row);
+  }
+  chunk_bytes = std::min(std::max<long long>(chunk_bytes, 64), kChunkMax);
+  chunk_bytes = std::min(chunk_bytes, std::max<long long>(64, std::max(freq_bytes, depth_bytes) + 1));
+  G = std::min<long long>(std::min<long long>(G, n_sites_max), chunk_bytes);
+  G = std::max<long long>(G, 1);
+  const size_t cells = (size_t)G * (size_t)S;
+  if (cells > 0xFFFFFFF0ull) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a row group beyond 2^32 cells: lower group_rows");
+  SsBufs dev;
+  SsEvents ev;
+  for (auto& x : ev.e) SS_TRY(hipEventCreate(&x));
+  Chunk ck[2];
+  ck[0].host = freq; ck[0].bytes = freq_bytes;
+  ck[1].host = depth; ck[1].bytes = depth_bytes;
+  auto alloc_chunk = [&](Chunk& c, long long cb) -> int32_t {
+    const size_t padded = ((size_t)cb + 1 + 15) / 16 * 16;
+    SS_TRY(dev.get(&c.d_text, padded));
+    SS_TRY(dev.get(&c.d_counts, padded / 16 * 4));
+    return MIDAS_SNPS_OK;
+  };
+  for (Chunk& c : ck) {
+    int32_t rc = alloc_chunk(c, chunk_bytes);
+    if (rc != MIDAS_SNPS_OK) return rc;
+    SS_TRY(dev.get(&c.d_ends, ((size_t)G + 1) * 4));
+    SS_TRY(dev.get(&c.d_side, cells * sizeof(SideCell)));
+    SS_TRY(dev.get(&c.d_side_n, 4));
+    SS_TRY(dev.get(&c.d_bad, 8));
+  }
+  uint32_t* d_scratch = nullptr;
+  SS_TRY(dev.get(&d_scratch, std::max(scan_scratch_words((kChunkMax + 16) / 16), scan_scratch_words(G)) * 4));
+  double *d_fv = nullptr, *d_pooled = nullptr, *d_mean = nullptr, *d_pi = nullptr;
+  long long *d_dv = nullptr, *d_last = nullptr, *d_snps = nullptr, *d_sites = nullptr, *d_depth = nullptr, *d_patch_at = nullptr;
+  uint8_t *d_cell = nullptr, *d_mask = nullptr, *d_final = nullptr, *d_seq = nullptr;
+  uint32_t *d_keep = nullptr, *d_rank = nullptr;
+  int32_t *d_gene = nullptr, *d_col_slot = nullptr;
+  char *d_minor = nullptr, *d_major = nullptr;
+  unsigned long long* d_no_gene = nullptr;
+  void* d_patch_v = nullptr;
+  size_t patch_cap = 0;
+  SS_TRY(dev.get(&d_fv, cells * 8));
+  SS_TRY(dev.get(&d_dv, cells * 8));
+  SS_TRY(dev.get(&d_cell, cells));
+  SS_TRY(dev.get(&d_mask, (size_t)G));
+  SS_TRY(dev.get(&d_final, (size_t)G));
+  SS_TRY(dev.get(&d_keep, (size_t)G * 4));
+  SS_TRY(dev.get(&d_rank, (size_t)G * 4));
+  SS_TRY(dev.get(&d_pooled, (size_t)G * 8));
+  SS_TRY(dev.get(&d_mean, (size_t)S * 8));
+  SS_TRY(dev.get(&d_col_slot, (size_t)n_cols * 4));
+  SS_TRY(dev.get(&d_last, 8));
+  SS_TRY(dev.get(&d_no_gene, 8));
+  SS_TRY(hipMemsetAsync(d_no_gene, 0, 8, st));
+  if (per_gene) SS_TRY(dev.get(&d_gene, (size_t)G * 4));
+  if (want_seq) {
+    SS_TRY(dev.get(&d_seq, cells));
+    SS_TRY(dev.get(&d_minor, (size_t)G));
+    SS_TRY(dev.get(&d_major, (size_t)G));
+  }
+  if (want_sums) {
+    SS_TRY(dev.get(&d_pi, n_acc * 8));
+    SS_TRY(dev.get(&d_snps, n_acc * 8));
+    SS_TRY(dev.get(&d_sites, n_acc * 8));
+    SS_TRY(dev.get(&d_depth, n_acc * 8));
+    SS_TRY(hipMemsetAsync(d_pi, 0, n_acc * 8, st));
+    SS_TRY(hipMemsetAsync(d_snps, 0, n_acc * 8, st));
+    SS_TRY(hipMemsetAsync(d_sites, 0, n_acc * 8, st));
+    SS_TRY(hipMemsetAsync(d_depth, 0, n_acc * 8, st));
+  }
+  SS_TRY(hipMemcpyAsync(d_mean, mean_depth, (size_t)S * 8, hipMemcpyHostToDevice, st));
+  SS_TRY(hipMemcpyAsync(d_col_slot, col_slot.data(), (size_t)n_cols * 4, hipMemcpyHostToDevice, st));
+  float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, site, order, sums, seq, download
+  auto lap = [&](int a, int b, int slot) -> hipError_t {
+    float t = 0.f;
+    const hipError_t e = hipEventElapsedTime(&t, ev.e[a], ev.e[b]);
+    if (e == hipSuccess) ms[slot] += t;
+    return e;
+  };
+  // upload the next chunk of one matrix and index its lines
+  auto load_chunk = [&](Chunk& c) -> int32_t {
+    const long long left = c.bytes - c.at;
+    long long n = std::min(left, chunk_bytes);
+    c.at_eof = n == left;
+    if (n > 0) SS_TRY(hipMemcpyAsync(c.d_text, c.host + c.at, (size_t)n, hipMemcpyHostToDevice, st));
+    if (c.at_eof && n > 0 && c.host[c.at + n - 1] != '\n') {      // the last line has no terminator: it is a row all the same
+      const char nl = '\n';
+      SS_TRY(hipMemcpyAsync(c.d_text + n, &nl, 1, hipMemcpyHostToDevice, st));
+      ++n;
+    }
+    const long long n16 = (n + 15) / 16;
+    if (n16 * 16 > n) SS_TRY(hipMemsetAsync(c.d_text + n, 0, (size_t)(n16 * 16 - n), st));
+    c.n = n;
+    c.lines = 0;
+    if (n == 0) return MIDAS_SNPS_OK;
+    SS_TRY(hipEventRecord(ev.e[1], st));
+    hipLaunchKernelGGL(ss_count_kernel, dim3(nblocks(n16, 256)), dim3(256), 0, st, (const uint4*)c.d_text, n16, c.d_counts);
+    SS_TRY(hipGetLastError());
+    uint32_t last_count = 0, last_prefix = 0;
+    SS_TRY(hipMemcpyAsync(&last_count, c.d_counts + n16 - 1, 4, hipMemcpyDeviceToHost, st));
+    SS_TRY(launch_scan_u32(c.d_counts, c.d_counts, n16, d_scratch, st));
+    SS_TRY(hipMemcpyAsync(&last_prefix, c.d_counts + n16 - 1, 4, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(ss_ends_kernel, dim3(nblocks(n16, 256)), dim3(256), 0, st, (const uint4*)c.d_text, n16, c.d_counts, (uint32_t)G,
+                       c.d_ends);
+    SS_TRY(hipGetLastError());
+    SS_TRY(hipEventRecord(ev.e[2], st));
+    SS_TRY(hipStreamSynchronize(st));
+    SS_TRY(lap(1, 2, 1));
+    c.lines = (long long)last_count + last_prefix;
+    return MIDAS_SNPS_OK;
+  };
+  static const char* kFile[2] = {"freq", "depth"};
+  std::vector<SideCell> side_h;
+  std::vector<long long> patch_at;
+  std::vector<double> patch_f;
+  std::vector<long long> patch_i;
+  long long base = 0, kept = 0, groups = 0;
+  bool stop = false;
+  while (!stop && base < n_sites_max) {
+    // ---- the group's rows: complete lines of both chunks ----------------------------------------------------------------
+    const auto t_load = std::chrono::steady_clock::now();
+    for (Chunk& c : ck) {
+      int32_t rc = load_chunk(c);
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
+    // (host clock around copies that end in a synchronise: upload + index of both chunks; the index alone is ms[1])
+    ms[0] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_load).count();
+    long long g = std::min(std::min(ck[0].lines, ck[1].lines), std::min(G, n_sites_max - base));
+    if (g == 0) {
+      bool grow = false;
+      for (Chunk& c : ck)
+        if (c.lines == 0 && !c.at_eof) grow = true;
+      if (!grow) break;                    // one of the matrices has no row left: the reference stops here too
+      if (chunk_bytes >= kChunkMax) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a matrix row longer than 1 GiB");
+      chunk_bytes = std::min(kChunkMax, chunk_bytes * 2);
+      for (Chunk& c : ck) {
+        int32_t rc = alloc_chunk(c, chunk_bytes);
+        if (rc != MIDAS_SNPS_OK) return rc;
+      }
+      continue;
+    }
+    ++groups;
+    // ---- parse ---------------------------------------------------------------------------------------------------------
+    SS_TRY(hipEventRecord(ev.e[2], st));
+    for (int m = 0; m < 2; ++m) {
+      Chunk& c = ck[m];
+      SS_TRY(hipMemsetAsync(c.d_side_n, 0, 4, st));
+      SS_TRY(hipMemsetAsync(c.d_bad, 0xFF, 8, st));
+      ParseP pp;
+      pp.text = c.d_text; pp.ends = c.d_ends; pp.g = g; pp.stride = G; pp.col_slot = d_col_slot; pp.n_cols = n_cols;
+      pp.val = m == 0 ? (void*)d_fv : (void*)d_dv; pp.side = c.d_side; pp.side_n = c.d_side_n; pp.side_cap = (uint32_t)cells;
+      pp.bad = c.d_bad;
+      if (m == 0) hipLaunchKernelGGL(ss_parse_kernel<false>, dim3(nblocks(g, 256)), dim3(256), 0, st, pp);
+      else hipLaunchKernelGGL(ss_parse_kernel<true>, dim3(nblocks(g, 256)), dim3(256), 0, st, pp);
+      SS_TRY(hipGetLastError());
+    }
+    SS_TRY(hipEventRecord(ev.e[3], st));
+    uint32_t side_n[2] = {0, 0}, end_at[2] = {0, 0};
+    unsigned long long bad[2] = {kNoBad, kNoBad};
+    for (int m = 0; m < 2; ++m) {
+      SS_TRY(hipMemcpyAsync(&side_n[m], ck[m].d_side_n, 4, hipMemcpyDeviceToHost, st));
+      SS_TRY(hipMemcpyAsync(&bad[m], ck[m].d_bad, 8, hipMemcpyDeviceToHost, st));
+      SS_TRY(hipMemcpyAsync(&end_at[m], ck[m].d_ends + g - 1, 4, hipMemcpyDeviceToHost, st));
+    }
+    SS_TRY(hipStreamSynchronize(st));
+    SS_TRY(lap(2, 3, 2));
+    // ---- the side lists: cells off the fast path, converted by the host's exact parser and patched in ----------------------
+    for (int m = 0; m < 2; ++m) {
+      const uint32_t n = side_n[m];
+      out_stats16[2 + m] += n;
+      if (n == 0) continue;
+      side_h.resize(n);
+      SS_TRY(hipMemcpy(side_h.data(), ck[m].d_side, (size_t)n * sizeof(SideCell), hipMemcpyDeviceToHost));
+      patch_at.clear(); patch_f.clear(); patch_i.clear();
+      const char* text = ck[m].host + ck[m].at;
+      for (const SideCell& sc : side_h) {
+        // (a cell that starts at the appended terminator of an unterminated last line is empty: off + len stays inside)
+        const std::string_view cell(text + sc.off, sc.len);
+        bool ok;
+        double vf = 0.0;
+        int64_t vi = 0;
+        if (m == 0) ok = parse_f64_py(cell, &vf);
+        else ok = parse_i64_py(cell, &vi);
+        if (!ok) {
+          bad[m] = std::min(bad[m], ((unsigned long long)sc.row << 32) | (sc.slot + 1ull));
+          continue;
+        }
+        patch_at.push_back((long long)sc.slot * G + sc.row);
+        if (m == 0) patch_f.push_back(vf); else patch_i.push_back((long long)vi);
+      }
+      const size_t np = patch_at.size();
+      if (np == 0) continue;
+      if (np > patch_cap) {
+        patch_cap = std::max(np, patch_cap * 2);
+        SS_TRY(dev.get(&d_patch_at, patch_cap * 8));
+        SS_TRY(dev.get((char**)&d_patch_v, patch_cap * 8));
+      }
+      SS_TRY(hipMemcpyAsync(d_patch_at, patch_at.data(), np * 8, hipMemcpyHostToDevice, st));
+      SS_TRY(hipMemcpyAsync(d_patch_v, m == 0 ? (const void*)patch_f.data() : (const void*)patch_i.data(), np * 8, hipMemcpyHostToDevice, st));
+      if (m == 0) hipLaunchKernelGGL(ss_patch_kernel<double>, dim3(nblocks((long long)np, 256)), dim3(256), 0, st, d_fv, d_patch_at, (const double*)d_patch_v, (long long)np);
+      else hipLaunchKernelGGL(ss_patch_kernel<long long>, dim3(nblocks((long long)np, 256)), dim3(256), 0, st, d_dv, d_patch_at, (const long long*)d_patch_v, (long long)np);
+      SS_TRY(hipGetLastError());
+      SS_TRY(hipStreamSynchronize(st));       // (the host vectors are reused by the other matrix)
+    }
+    // ---- site kernel, order, sums, sequences ---------------------------------------------------------------------------
+    SS_TRY(hipMemcpyAsync(d_mask, site_mask + base, (size_t)g, hipMemcpyHostToDevice, st));
+    if (per_gene) SS_TRY(hipMemcpyAsync(d_gene, site_gene + base, (size_t)g * 4, hipMemcpyHostToDevice, st));
+    if (want_seq) {
+      SS_TRY(hipMemcpyAsync(d_minor, minor + base, (size_t)g, hipMemcpyHostToDevice, st));
+      SS_TRY(hipMemcpyAsync(d_major, major + base, (size_t)g, hipMemcpyHostToDevice, st));
+    }
+    SS_TRY(hipEventRecord(ev.e[3], st));
+    SiteP sp;
+    sp.fv = d_fv; sp.dv = d_dv; sp.cell = d_cell; sp.mean_depth = d_mean; sp.mask = d_mask; sp.g = g; sp.stride = G; sp.S = S;
+    sp.site_depth = site_depth; sp.site_ratio = fparams5[0]; sp.allele_support = fparams5[1]; sp.site_prev = fparams5[2];
+    sp.site_maf = fparams5[3]; sp.weight = weight; sp.round_freq = round_freq; sp.mask_only = mask_only; sp.keep = d_keep;
+    sp.pooled = d_pooled;
+    hipLaunchKernelGGL(ss_site_kernel, dim3(nblocks(g, 256)), dim3(256), 0, st, sp);
+    SS_TRY(hipGetLastError());
+    SS_TRY(hipEventRecord(ev.e[4], st));
+    uint32_t last_keep = 0, last_rank = 0;
+    long long last_row = -1;
+    SS_TRY(hipMemsetAsync(d_last, 0xFF, 8, st));
+    SS_TRY(launch_scan_u32(d_keep, d_rank, g, d_scratch, st));
+    hipLaunchKernelGGL(ss_order_kernel, dim3(nblocks(g, 256)), dim3(256), 0, st, d_keep, d_rank, g, kept, max_sites, d_final, d_last);
+    SS_TRY(hipGetLastError());
+    SS_TRY(hipEventRecord(ev.e[5], st));
+    SS_TRY(hipMemcpyAsync(&last_keep, d_keep + g - 1, 4, hipMemcpyDeviceToHost, st));
+    SS_TRY(hipMemcpyAsync(&last_rank, d_rank + g - 1, 4, hipMemcpyDeviceToHost, st));
+    SS_TRY(hipMemcpyAsync(&last_row, d_last, 8, hipMemcpyDeviceToHost, st));
+    if (want_sums) {
+      SumP q;
+      q.fv = pooled ? d_pooled : d_fv; q.dv = d_dv; q.cell = d_cell; q.final_keep = d_final; q.gene = d_gene; q.g = g; q.stride = G;
+      q.pooled = pooled; q.per_gene = per_gene; q.round_freq = round_freq; q.n_genes = n_genes; q.snp_maf = fparams5[4];
+      q.pi = d_pi; q.snps = d_snps; q.sites = d_sites; q.depth = d_depth; q.no_gene = d_no_gene;
+      hipLaunchKernelGGL(ss_sums_kernel, dim3((unsigned)chains), dim3(64), 0, st, q);
+      SS_TRY(hipGetLastError());
+    }
+    SS_TRY(hipEventRecord(ev.e[6], st));
+    if (want_seq) {
+      hipLaunchKernelGGL(ss_seq_kernel, dim3(nblocks(g, 256)), dim3(256), 0, st, d_fv, d_dv, d_cell, d_final, d_rank, d_minor, d_major, g, G,
+                         S, d_seq);
+      SS_TRY(hipGetLastError());
+    }
+    SS_TRY(hipEventRecord(ev.e[7], st));
+    SS_TRY(hipStreamSynchronize(st));
+    SS_TRY(lap(3, 4, 3));
+    SS_TRY(lap(4, 5, 4));
+    SS_TRY(lap(5, 6, 5));
+    SS_TRY(lap(6, 7, 6));
+    long long kept_g = (long long)last_rank + last_keep;
+    if (max_sites >= 0) kept_g = std::min(kept_g, max_sites - kept);
+    // the rows the reference reads: all of the group, or up to the one after the row that fills max_sites
+    const long long read_rows = last_row >= 0 ? last_row + 2 : g;
+    for (int m = 0; m < 2; ++m) {
+      if (bad[m] == kNoBad || (long long)(bad[m] >> 32) >= read_rows) continue;
+      const long long row = base + (long long)(bad[m] >> 32);
+      const long long slot = (long long)(bad[m] & 0xFFFFFFFFull) - 1;
+      out_stats16[4] = m + 1;
+      out_stats16[5] = row;
+      out_stats16[6] = slot;
+      out_stats16[0] = base;
+      char buf[160];
+      if (slot < 0) snprintf(buf, sizeof buf, "%s matrix, data row %lld: fewer than %d sample columns", kFile[m], row, n_cols);
+      else snprintf(buf, sizeof buf, "%s matrix, data row %lld, sample %lld: not a number", kFile[m], row, slot);
+      return ss_fail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+    }
+    SS_TRY(hipEventRecord(ev.e[0], st));
+    if (dump_freq || dump_depth)
+      for (int s = 0; s < S; ++s) {
+        if (dump_freq) SS_TRY(hipMemcpyAsync(dump_freq + (size_t)s * n_sites_max + base, d_fv + (size_t)s * G, (size_t)g * 8, hipMemcpyDeviceToHost, st));
+        if (dump_depth) SS_TRY(hipMemcpyAsync(dump_depth + (size_t)s * n_sites_max + base, d_dv + (size_t)s * G, (size_t)g * 8, hipMemcpyDeviceToHost, st));
+      }
+    if (dump_keep) SS_TRY(hipMemcpyAsync(dump_keep + base, d_final, (size_t)g, hipMemcpyDeviceToHost, st));
+    if (dump_pooled) SS_TRY(hipMemcpyAsync(dump_pooled + base, d_pooled, (size_t)g * 8, hipMemcpyDeviceToHost, st));
+    if (want_seq && kept_g > 0) {
+      if (kept + kept_g > seq_cap) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "the retained sites do not fit the sequence capacity");
+      SS_TRY(hipMemcpy2DAsync(out_seq + kept, (size_t)seq_cap, d_seq, (size_t)G, (size_t)kept_g, (size_t)S, hipMemcpyDeviceToHost, st));
+    }
+    SS_TRY(hipEventRecord(ev.e[1], st));
+    SS_TRY(hipStreamSynchronize(st));
+    SS_TRY(lap(0, 1, 7));
+    kept += kept_g;
+    base += g;
+    for (int m = 0; m < 2; ++m) ck[m].at = std::min(ck[m].bytes, ck[m].at + (long long)end_at[m] + 1);
+    if (last_row >= 0) stop = true;
+  }
+  if (want_sums) {
+    SS_TRY(hipMemcpyAsync(out_pi, d_pi, n_acc * 8, hipMemcpyDeviceToHost, st));
+    SS_TRY(hipMemcpyAsync(out_snps, d_snps, n_acc * 8, hipMemcpyDeviceToHost, st));
+    SS_TRY(hipMemcpyAsync(out_sites, d_sites, n_acc * 8, hipMemcpyDeviceToHost, st));
+    SS_TRY(hipMemcpyAsync(out_depth, d_depth, n_acc * 8, hipMemcpyDeviceToHost, st));
+  }
+  unsigned long long no_gene = 0;
+  SS_TRY(hipMemcpyAsync(&no_gene, d_no_gene, 8, hipMemcpyDeviceToHost, st));
+  SS_TRY(hipStreamSynchronize(st));
+  out_stats16[0] = base;
+  out_stats16[1] = kept;
+  out_stats16[7] = groups;
+  out_stats16[8] = (int64_t)no_gene;
+  out_stats16[9] = G;
+  out_stats16[10] = chunk_bytes;
+  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = ms[k];
+  return MIDAS_SNPS_OK;
+}
