@@ -768,6 +768,45 @@ int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_byt
                          uint8_t* out_seq, double* dump_freq, int64_t* dump_depth, uint8_t* dump_keep, double* dump_pooled,
                          int64_t* out_stats16, float* out_ms8);
 
+/* ---- strain_tracking.py: marker alleles (id_markers) and their sharing between all pairs of samples (track_markers) ----------
+ * Both walk the two matrices as midas_sites_scan does (same text, same cell parsers, same row groups, same place of a bad row
+ * in out_stats16[4..6]).  Rows [0, n_parse) are read and checked, rows [0, n_call) are called (n_call <= n_parse: the reference
+ * reads one row more than --max_sites lets it use).  An allele with frequency x (freq for the minor, 1 - freq for the major
+ * allele) is present in a sample of depth d != 0 when x >= min_freq and round(x * d) >= min_reads, round() half to even.
+ * fparams2 = min_freq, 0; iparams8 = min_reads, allele_prev, group_rows, chunk_bytes, capacity (markers), pair_blocks
+ * (track_markers: the workgroups the pair kernel aims at when it cuts the words into runs; 0: 1024; the output does not
+ * depend on it), 0, 0.
+ * id_markers: minor_code / major_code [n_call]: 0..3 = the site's allele is A, T, C, G, anything else another string.  A site
+ *   is a marker when exactly two letters are present in some sample and the rarer (a tie: the earlier of A, T, C, G) is present
+ *   in at most allele_prev samples.  out_rows7 [capacity][7], in site order: site row, allele 0..3, samples with depth != 0,
+ *   samples with A, T, C, G.  out_stats16[1] = markers.
+ * track_markers: site_which [n_call]: 0 the site is no marker, 1 the marker is its major, 2 its minor allele.  The matched
+ *   sites of a row group become a bit matrix [sample][64 sites a word]; out_both [n_samples][n_samples], filled for i <= j:
+ *   sites whose marker is present in samples i and j (the diagonal: in sample i).  The sums are integers held on the device
+ *   across row groups: they do not depend on group_rows.  A workgroup adds up a MIDAS_SITES_PAIR_TILE-square tile of pairs.
+ *   out_stats16[1] = matched sites, [8] = (sample pairs with i <= j) x words of the bit matrices, [11] / [12] = the most word
+ *   runs a launch of the pair kernel had and the most staging steps a run had.
+ * A site that cannot be called is MIDAS_SNPS_ERR_BAD_LAYOUT with out_stats16[4] = 3 (frequency x depth is not finite), 4 / 5
+ * (a sample has the minor / major allele, which is none of A, T, C, G), [5] the data row, [6] the sample.  Of a row that
+ * cannot be read and a site that cannot be called the one in the earlier row is reported (in one row: the cell), as the
+ * reference meets them: which error it is does not depend on group_rows.
+ * out_ms8 (nullable): upload + index (host clock), index, parse, then id_markers: call, compact, -, -, download;
+ * track_markers: matched sites, bit matrix, pairs, -, download (device events).
+ * midas_sites_write_markers / _pairs: the two output tables formatted natively from these arrays and the tables' string columns
+ * (site_id; sample_id of summary rows sample_row[s]); pairs in itertools.combinations order.                                  */
+#define MIDAS_SITES_PAIR_TILE 64
+int32_t midas_sites_id_markers(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                               int64_t n_parse, int64_t n_call, const uint8_t* minor_code, const uint8_t* major_code,
+                               int32_t n_samples, const int32_t* sample_col, const double* fparams2, const int64_t* iparams8,
+                               int32_t* out_rows7, int64_t* out_stats16, float* out_ms8);
+int32_t midas_sites_track_markers(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                  int64_t n_parse, int64_t n_call, const uint8_t* site_which, int32_t n_samples,
+                                  const int32_t* sample_col, const double* fparams2, const int64_t* iparams8, int64_t* out_both,
+                                  int64_t* out_stats16, float* out_ms8);
+int32_t midas_sites_write_markers(const char* path, const midas_sites_tables* t, int64_t n_markers, const int32_t* rows7, char* err1024);
+int32_t midas_sites_write_pairs(const char* path, const midas_sites_tables* t, int32_t n_samples, const int32_t* sample_row,
+                                const int64_t* both, char* err1024);
+
 /* ---- the exchange between ranks (comm.cpp): RCCL itself, no process group ------------------------------------------------
  * One process per GPU; the only thing ranks exchange on this path is the per-species summary rows -- the reference's pool
  * workers return (species_id, aln_stats) through a pipe, midas/run/snps.py:225-241, midas/utility.py:81-107 -- plus, on the

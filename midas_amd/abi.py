@@ -351,6 +351,10 @@ def load_library(build_if_missing: bool = True):
         'midas_sites_tables_close': (None, [vp]),
         'midas_sites_parse_cell': (i32, [i32, C.c_char_p, i64, vp]),
         'midas_sites_scan': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15),
+        'midas_sites_id_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, vp, i32] + [vp] * 6),
+        'midas_sites_track_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, i32] + [vp] * 6),
+        'midas_sites_write_markers': (i32, [C.c_char_p, vp, i64, vp, C.c_char_p]),
+        'midas_sites_write_pairs': (i32, [C.c_char_p, vp, i32, vp, vp, C.c_char_p]),
     })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing: fail loudly
@@ -392,9 +396,10 @@ EXPORTED_SYMBOLS = [
     'midas_genes_merge_tables_columns', 'midas_genes_merge_tables_close', 'midas_genes_merge', 'midas_genes_merge_write_matrix',
     'midas_genes_merge_format_f64',
 ]
-# the analysis entry points (snp_diversity.py, call_consensus.py): bound above like the rest, listed by themselves
+# the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
-                 'midas_sites_parse_cell', 'midas_sites_scan']
+                 'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_id_markers', 'midas_sites_track_markers',
+                 'midas_sites_write_markers', 'midas_sites_write_pairs']
 
 
 def deflate_rows(text: bytes, row_begin, tail_begin) -> bytes:
@@ -822,6 +827,8 @@ def format_repr_f64(values) -> list:
 
 
 SITES_WEIGHT, SITES_ROUND, SITES_POOLED, SITES_PER_GENE, SITES_MASK_ONLY, SITES_SEQ, SITES_SUMS = 1, 2, 4, 8, 16, 32, 64
+SITES_PAIR_TILE = 64         # MIDAS_SITES_PAIR_TILE: samples a side of the pair kernel's tile
+ALLELE_LETTERS = 'ATCG'      # the order of the allele codes and of the count columns of strain_tracking.py id_markers
 
 
 class SitesTables:
@@ -881,6 +888,27 @@ class SitesTables:
             idx = np.minimum(off[:-1] + k, max(pool.shape[0] - 1, 0))
             hit &= (pool[idx] == v[k]) if pool.shape[0] else np.zeros(n, bool)
         return hit
+
+    def write_markers(self, path: str, rows7):
+        """The table of strain_tracking.py id_markers (midas_sites_write_markers): rows7 int32 [n, 7] as Context.sites_id_markers
+        returns them."""
+        rows = np.ascontiguousarray(rows7, dtype=np.int32).reshape(-1, 7)
+        err = C.create_string_buffer(1024)
+        st = self._owner._lib.midas_sites_write_markers(path.encode(), self._owner._h, rows.shape[0], rows.ctypes.data_as(C.c_void_p), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_sites_write_markers failed")
+
+    def write_pairs(self, path: str, sample_rows, both):
+        """The table of strain_tracking.py track_markers (midas_sites_write_pairs): both int64 [S, S] as Context.sites_track_markers
+        returns it, sample_rows [S] = the samples' rows of snps_summary.txt."""
+        rows = np.ascontiguousarray(sample_rows, dtype=np.int32)
+        b = np.ascontiguousarray(both, dtype=np.int64)
+        assert b.shape == (rows.shape[0], rows.shape[0])
+        err = C.create_string_buffer(1024)
+        st = self._owner._lib.midas_sites_write_pairs(path.encode(), self._owner._h, rows.shape[0], rows.ctypes.data_as(C.c_void_p),
+                                                      b.ctypes.data_as(C.c_void_p), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_sites_write_pairs failed")
 
     def first_bytes(self, name: str):
         """(first byte of every string, or 0 for an empty one; the lengths)."""
@@ -1387,6 +1415,59 @@ class Context:
             out.update(freq=out['freq'][:, :n], depthv=out['depthv'][:, :n], keep=out['keep'][:n], pooled=out['pooled'][:n])
         elif dump_keep:
             out['keep'] = out['keep'][:n]
+        return out
+
+    def _strains_call(self, fn, freq_text, depth_text, n_parse, n_call, site_arrays, sample_col, min_freq, iparams, out):
+        ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
+        dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
+        cols = np.ascontiguousarray(sample_col, dtype=np.int32)
+        assert cols.shape[0] >= 1 and 0 <= n_call <= n_parse and all(a.shape[0] >= n_call for a in site_arrays)
+        fp = np.array([min_freq, 0.0], np.float64)
+        ip = np.array(list(iparams) + [0] * (8 - len(iparams)), np.int64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = fn(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], int(n_parse), int(n_call), *[p(a) for a in site_arrays], cols.shape[0],
+                p(cols), p(fp), p(ip), p(out), p(stats), p(ms))
+        if st != 0:
+            try:
+                self._check(st)
+            except MidasSnpsError as e:
+                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
+                raise
+        return dict(n_sites=int(stats[0]), groups=int(stats[7]), side_freq=int(stats[2]), side_depth=int(stats[3]),
+                    group_rows=int(stats[9]), chunk_bytes=int(stats[10]), ms=ms.tolist()), stats
+
+    def sites_id_markers(self, freq_text, depth_text, minor_code, major_code, sample_col, min_freq: float, min_reads: int, allele_prev: int,
+                         n_parse: int = None, group_rows: int = 0, chunk_bytes: int = 0):
+        """midas_sites_id_markers(): strain_tracking.py id_markers over the text rows of the two matrices.  minor_code / major_code
+        uint8 [n_call]: the site's alleles as indices into ALLELE_LETTERS (anything above 3: another string); rows up to n_parse
+        (default n_call) are read and checked.  -> dict(rows int32 [markers, 7] = site row, allele, samples with depth, samples
+        with A, T, C, G; n_sites, groups, side_freq, side_depth, ms [8]).  A row that cannot be read or called raises
+        MidasSnpsError with .bad = (1 freq | 2 depth | 3 not finite | 4 minor letter | 5 major letter, data row, sample or -1)."""
+        mi = np.ascontiguousarray(minor_code, dtype=np.uint8)
+        ma = np.ascontiguousarray(major_code, dtype=np.uint8)
+        n_call = int(mi.shape[0])
+        assert ma.shape[0] == n_call
+        rows = np.zeros((max(n_call, 1), 7), np.int32)
+        out, stats = self._strains_call(self._lib.midas_sites_id_markers, freq_text, depth_text, n_call if n_parse is None else n_parse, n_call,
+                                        [mi, ma], sample_col, float(min_freq), [int(min_reads), int(allele_prev), group_rows, chunk_bytes, n_call], rows)
+        out['rows'] = rows[:int(stats[1])]
+        return out
+
+    def sites_track_markers(self, freq_text, depth_text, site_which, sample_col, min_freq: float, min_reads: int, n_parse: int = None,
+                            group_rows: int = 0, chunk_bytes: int = 0, pair_blocks: int = 0):
+        """midas_sites_track_markers(): strain_tracking.py track_markers.  site_which uint8 [n_call]: 0 no marker, 1 the marker is the
+        site's major, 2 its minor allele.  -> dict(both int64 [S, S], filled for i <= j: sites whose marker both samples have (the
+        diagonal: the sample's own count); n_matched, word_pairs, pair_runs / pair_steps = the most word runs a launch of the pair
+        kernel had and the most staging steps a run had, n_sites, groups, ms [8]); errors as sites_id_markers.  pair_blocks: the
+        workgroups the pair kernel aims at when it cuts the words into runs (0: 1024); the output does not depend on it."""
+        which = np.ascontiguousarray(site_which, dtype=np.uint8)
+        n_call = int(which.shape[0])
+        S = int(np.asarray(sample_col).shape[0])
+        both = np.zeros((S, S), np.int64)
+        out, stats = self._strains_call(self._lib.midas_sites_track_markers, freq_text, depth_text, n_call if n_parse is None else n_parse, n_call,
+                                        [which], sample_col, float(min_freq), [int(min_reads), 0, group_rows, chunk_bytes, 0, int(pair_blocks)], both)
+        out.update(both=both, n_matched=int(stats[1]), word_pairs=int(stats[8]), pair_runs=int(stats[11]), pair_steps=int(stats[12]))
         return out
 
     def batch(self, contigs: ContigTable, reads: ReadsSoA) -> "Batch":

@@ -1,5 +1,6 @@
-"""The command lines of snp_diversity.py and call_consensus.py: the reference's option names, defaults, check_args messages
-and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146), shared where they agree."""
+"""The command lines of snp_diversity.py, call_consensus.py and strain_tracking.py: the reference's option names, defaults,
+check_args messages and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146,
+scripts/strain_tracking.py:10-137), shared where they agree."""
 import argparse
 import os
 import sys
@@ -151,6 +152,83 @@ def check_consensus_args(args):
     if args['site_depth'] < 1:
         _exit("--site_depth must be >=1")
     _common_checks(args)
+
+
+STRAIN_COMMANDS = ['id_markers', 'track_markers']
+STRAIN_USAGE = ['', 'Usage: strain_tracking.py <command> [options]', '',
+                'Note: use strain_tracking.py <command> -h to view usage for a specific command', '', 'Commands:',
+                '\tid_markers      identify rare SNPs that disriminate individual strains',
+                '\ttrack_markers   track rare SNPs between samples and determine transmission']
+
+CALL_OPTIONS = [
+    (['--min_freq'], dict(type=float, metavar='FLOAT', default=0.10, help="an allele counts in a sample from this share of the reads at the site (0.10)")),
+    (['--min_reads'], dict(type=int, metavar='INT', default=3, help="... and from this many reads, round(share x depth) (3)")),
+]
+
+
+def strain_program(argv=None):
+    """get_program: the usage screen without a command or with -h, the exit for a command that is not one."""
+    argv = sys.argv[1:] if argv is None else argv
+    if len(argv) == 0 or argv[0] in ['-h', '--help']:
+        sys.stdout.write('\n'.join(STRAIN_USAGE) + '\n')
+        sys.exit()
+    if argv[0] not in STRAIN_COMMANDS:
+        _exit("Unrecognized command: '%s'" % argv[0])
+    return argv[0]
+
+
+def _strain_parser(command, description, epilog, options):
+    parser = argparse.ArgumentParser(prog='strain_tracking.py %s' % command, formatter_class=argparse.RawTextHelpFormatter,
+                                     usage=argparse.SUPPRESS,
+                                     description="\nDescription: %s\n\nUsage: strain_tracking.py %s [options]\n" % (description, command), epilog=epilog)
+    parser.add_argument('program', help=argparse.SUPPRESS)
+    parser.add_argument('--indir', metavar='PATH', type=str, required=True,
+                        help="one species directory written by `merge_midas.py snps` (holds snps_freq.txt, snps_depth.txt,\nsnps_info.txt, snps_summary.txt)")
+    for flags, kw in options + DEVICE_OPTIONS:
+        parser.add_argument(*flags, **kw)
+    return parser
+
+
+def id_markers_arguments(argv=None):
+    """id_arguments: argv starts with the command.  --samples becomes a list: membership in it is list membership."""
+    parser = _strain_parser('id_markers', "find the rare alleles that tell the strains of one species apart",
+                            "examples:\n"
+                            "  strain_tracking.py id_markers --indir OUT/species_1 --out markers.txt --samples s1,s2,s3\n"
+                            "  strain_tracking.py id_markers --indir OUT/species_1 --out markers.txt --max_sites 10000\n\n"
+                            "output: site_id, allele, count_samples (samples with a read at the site) and count_A, count_T, count_C,\n"
+                            "count_G (samples that have the letter) per marker",
+                            [(['--out'], dict(metavar='PATH', type=str, required=True, help="output file: the list of markers")),
+                             (['--samples'], dict(metavar='STR', type=str, help="comma-separated training samples (all)"))] + CALL_OPTIONS +
+                            [(['--allele_prev'], dict(type=int, metavar='INT', default=1,
+                                                      help="a marker allele is found in at most this many samples (1: in exactly one)")),
+                             (['--max_sites'], dict(type=int, metavar='INT', default=INF, help="stop after this many sites read (all)"))])
+    args = vars(parser.parse_args(argv))
+    if args['samples']:
+        args['samples'] = args['samples'].split(',')
+    return args
+
+
+def track_markers_arguments(argv=None):
+    """track_arguments with its two existence checks; --out or --markers left out is a plain error here."""
+    parser = _strain_parser('track_markers', "count the marker alleles every pair of samples shares",
+                            "examples:\n"
+                            "  strain_tracking.py track_markers --indir OUT/species_1 --markers markers.txt --out allele_sharing.txt\n"
+                            "  strain_tracking.py track_markers --indir OUT/species_1 --markers markers.txt --out allele_sharing.txt --max_sites 1000\n\n"
+                            "output: sample1, sample2, count1, count2 (marker alleles in each), count_both, count_either per pair",
+                            [(['--out'], dict(metavar='PATH', type=str, help="output file: marker sharing of every pair of samples")),
+                             (['--markers'], dict(metavar='PATH', type=str, help="the list `strain_tracking.py id_markers` wrote"))] + CALL_OPTIONS +
+                            [(['--max_sites'], dict(type=int, metavar='INT', default=INF, help="stop after this many sites read (all)")),
+                             (['--max_samples'], dict(type=int, metavar='INT', help="(accepted; as in the reference it is never applied)"))])
+    args = vars(parser.parse_args(argv))
+    if not os.path.isdir(args['indir']):
+        _exit("Specified input directory '%s' does not exist" % args['indir'])
+    if args['markers'] is None:
+        _exit("--markers is required")
+    if not os.path.isfile(args['markers']):
+        _exit("Specified input file '%s' does not exist" % args['markers'])
+    if args['out'] is None:
+        _exit("--out is required")
+    return args
 
 
 COPYRIGHT = ["", "MIDAS: Metagenomic Intra-species Diversity Analysis System", "analysis commands on AMD Instinct MI355X (midas_amd %s)",

@@ -22,11 +22,12 @@ def open_tables(indir):
 
 
 def fetch_samples(tables, mean_depth=0, fract_cov=0, max_samples=float('inf'), keep_samples=None, exclude_samples=None,
-                  rand_samples=None):
+                  rand_samples=None, zero_depth_ok=False):
     """parse_snps.fetch_samples: the rows of snps_summary.txt that pass, in file order; a sample's matrix column is its row.
     keep_samples / exclude_samples are the option strings as given, and `in` is the reference's test on them.
     --rand_samples: the reference's two lines for it cannot run under Python 3; their intent is
-    np.random.choice(list of ids, n, replace=False), and the kept samples stay in file order."""
+    np.random.choice(list of ids, n, replace=False), and the kept samples stay in file order.
+    zero_depth_ok: the caller never divides by a sample's mean_coverage (strain_tracking.py), so 0 is no error."""
     ids = tables.strings('sample_id')
     samples = {}
     for index, id in enumerate(ids):
@@ -53,7 +54,7 @@ def fetch_samples(tables, mean_depth=0, fract_cov=0, max_samples=float('inf'), k
         if s.index >= tables.n_columns or s.index >= tables.freq_columns:
             sys.exit("\nError: %s: sample %s is row %d of snps_summary.txt, but the matrices have %d sample columns\n"
                      % (tables.dir, s.id, s.index + 1, min(tables.n_columns, tables.freq_columns)))
-        if s.mean_depth == 0:         # (depth / mean_depth at the first site: ZeroDivisionError in the reference)
+        if s.mean_depth == 0 and not zero_depth_ok:         # (depth / mean_depth at the first site: ZeroDivisionError in the reference)
             sys.exit("\nError: %s/snps_summary.txt: sample %s has mean_coverage 0\n" % (tables.dir, s.id))
     return samples
 
@@ -85,13 +86,18 @@ def scan(ctx, tables, samples, mask, n_sites, args, flags, **kw):
                               max_sites=-1 if args['max_sites'] == float('inf') else int(args['max_sites']), flags=flags,
                               group_rows=int(args.get('group_rows', 0) or 0), chunk_bytes=int(args.get('chunk_bytes', 0) or 0), **kw)
     except abi.MidasSnpsError as e:
-        bad = getattr(e, 'bad', None)
-        if not bad:
-            sys.exit("\nError: %s\n" % e.message)
-        name = 'snps_freq.txt' if bad[0] == 1 else 'snps_depth.txt'
-        what = "the row has fewer sample columns than the samples in use" if bad[2] < 0 else \
-            "sample %s: the cell is not %s" % (order[bad[2]].id, 'a number' if bad[0] == 1 else 'an integer')
-        sys.exit("\nError: %s, line %d: %s\n" % (os.path.join(tables.dir, name), bad[1] + 2, what))
+        exit_bad_row(tables, order, e)
+
+
+def exit_bad_row(tables, order, e):
+    """End the command on a device call's error: a malformed row with its file and line, anything else as it is."""
+    bad = getattr(e, 'bad', None)
+    if not bad:
+        sys.exit("\nError: %s\n" % e.message)
+    name = 'snps_freq.txt' if bad[0] == 1 else 'snps_depth.txt'
+    what = "the row has fewer sample columns than the samples in use" if bad[2] < 0 else \
+        "sample %s: the cell is not %s" % (order[bad[2]].id, 'a number' if bad[0] == 1 else 'an integer')
+    sys.exit("\nError: %s, line %d: %s\n" % (os.path.join(tables.dir, name), bad[1] + 2, what))
 
 
 def device_context():

@@ -77,3 +77,47 @@ def write_species_dir(path, n_sites, n_samples, seed=0, n_genes=0, block=100000,
                     lines.append('%d\tcontig_1\t%d\t%s\t%s\t%s\t%d\t0\t0\t0\t0\tIGR\t\tbi\t\t\n' % (site + 1, site + 1, a, b, c, n_samples))
             fi.write(''.join(lines))
     return dict(sample_ids=sample_ids)
+
+
+PRIVATE_FREQ = [1000, 1000, 1000, 800, 500, 333, 250, 120, 100, 1001]      # indices into FREQ_PALETTE: 1, 0.8, ..., 0.1, 1e-05
+
+
+def write_strain_species_dir(path, n_sites, n_samples, seed=0, block=100000, max_depth=60, private=0.2, shared=0.06, common=0.03):
+    """-> dict(sample_ids).  A species for strain_tracking.py: every site is fixed (freq 0 in all samples) unless it is planted --
+    with probability `private` one sample carries the minor allele, with probability `shared` two to four samples do, with
+    probability `common` about half of them do -- at a frequency out of PRIVATE_FREQ.  About 3 % of the depths are 0."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    sample_ids = ['sample_%03d' % k for k in range(n_samples)]
+    mean = rng.uniform(6.0, 30.0, n_samples)
+    with open(os.path.join(path, 'snps_summary.txt'), 'w') as f:
+        f.write('\t'.join(['sample_id', 'genome_length', 'covered_bases', 'fraction_covered', 'mean_coverage']) + '\n')
+        for k in range(n_samples):
+            f.write('%s\t%d\t%d\t%s\t%s\n' % (sample_ids[k], n_sites, n_sites // 2, repr(float(rng.uniform(0.4, 1.0))), repr(float(mean[k]))))
+    header = ('\t'.join(['site_id'] + sample_ids) + '\n').encode()
+    depth_palette = [str(k) for k in range(max_depth + 1)]
+    planted = np.array(PRIVATE_FREQ)
+    with open(os.path.join(path, 'snps_freq.txt'), 'wb') as ff, open(os.path.join(path, 'snps_depth.txt'), 'wb') as fd, \
+            open(os.path.join(path, 'snps_info.txt'), 'w') as fi:
+        ff.write(header)
+        fd.write(header)
+        fi.write('\t'.join(['site_id', 'ref_id', 'ref_pos', 'ref_allele', 'major_allele', 'minor_allele', 'count_samples', 'count_a',
+                            'count_c', 'count_g', 'count_t', 'locus_type', 'gene_id', 'snp_type', 'site_type', 'amino_acids']) + '\n')
+        for r0 in range(0, n_sites, block):
+            rows = min(block, n_sites - r0)
+            kind = rng.random(rows)
+            carriers = np.where(kind < private, 1, np.where(kind < private + shared, rng.integers(2, 5, rows), 0))
+            carried = ((kind >= private + shared) & (kind < private + shared + common))[:, None] & (rng.random((rows, n_samples)) < 0.5)
+            for k in range(4):                             # a site's k-th carrier (two picks may fall on one sample)
+                on = np.flatnonzero(carriers > k)
+                carried[on, rng.integers(0, n_samples, on.shape[0])] = True
+            fi_idx = np.where(carried, planted[rng.integers(0, len(planted), (rows, n_samples))], 0)
+            di = np.minimum(rng.poisson(mean[None, :] * rng.uniform(0.3, 1.6, (rows, 1))), max_depth)
+            di[rng.random((rows, n_samples)) < 0.03] = 0
+            ff.write(_matrix_bytes(r0, fi_idx, FREQ_PALETTE).tobytes())
+            fd.write(_matrix_bytes(r0, di, depth_palette).tobytes())
+            al = rng.integers(0, 4, (rows, 3))
+            fi.write(''.join('%d\tcontig_1\t%d\t%s\t%s\t%s\t%d\t0\t0\t0\t0\tIGR\t\tbi\t\t\n'
+                             % (r0 + r + 1, r0 + r + 1, 'ACGT'[al[r, 0]], 'ACGT'[al[r, 1]], 'ACGT'[(al[r, 1] + 1 + al[r, 2] % 3) % 4], n_samples)
+                             for r in range(rows)))
+    return dict(sample_ids=sample_ids)

@@ -23,7 +23,7 @@ HEADERS = ["layout.h", "contigs.h", "kernels.h", "device_common.h", "pileup_comm
 # The atomic optimizer turns a one-lane atomicAdd into mbcnt/readfirstlane and waits for the result at once; the
 # pileup kernel fetches its next work item that way and must not stall on it (pileup_tiles.hip, dynamic items).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
-# sites_scan.hip reproduces sums the interpreter forms with one rounding per operation: no fused multiply-add there
+# sites_scan.hip reproduces sums and products the interpreter forms with one rounding per operation: no fused multiply-add there
 SOURCE_FLAGS = {"sites_scan.hip": ["-ffp-contract=off"]}
 
 

@@ -7,6 +7,8 @@
 //   snps_freq.txt, snps_depth.txt   mapped, NOT parsed: their rows go to the device as bytes (sites_scan.hip).  The header
 //                     row gives the sample ids; the reference keeps the depth file's (parse_snps.py:55-58).
 //
+// strain_tracking.py's two output tables are written here too (midas_sites_write_markers / _pairs): integers and strings.
+//
 // Fields are taken as csv.DictReader(delimiter='\t') takes them from a file opened in text mode: a line ends at '\n'
 // ('\r\n' counts as one), an empty line is skipped, a field is the value of the LAST header column of its name, a row with
 // fewer fields than the header lacks the later ones (an error here when a needed one is missing).  Quoted fields are not
@@ -17,6 +19,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <charconv>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -36,6 +39,39 @@ struct StrCol {        // strings back to back + offsets
     pool.insert(pool.end(), v.begin(), v.end());
     off.push_back((int64_t)pool.size());
   }
+  std::string_view at(size_t k) const { return std::string_view(pool.data() + off[k], (size_t)(off[k + 1] - off[k])); }
+};
+
+// a text file written through a buffer of its own
+struct TextOut {
+  FILE* f = nullptr;
+  std::string buf;
+  ~TextOut() { if (f) fclose(f); }
+  bool open(const char* path) {
+    f = fopen(path, "w");
+    buf.reserve(1 << 20);
+    return f != nullptr;
+  }
+  bool flush() {
+    const bool ok = buf.empty() || fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+    buf.clear();
+    return ok;
+  }
+  void room() { if (buf.size() > (1u << 20) - 4096) bad = !flush() || bad; }
+  void put(std::string_view v) { buf.append(v.data(), v.size()); room(); }
+  void put(char c) { buf.push_back(c); }
+  void put_int(int64_t v) {
+    char tmp[24];
+    const auto r = std::to_chars(tmp, tmp + sizeof tmp, v);
+    buf.append(tmp, (size_t)(r.ptr - tmp));
+  }
+  bool close() {
+    bool ok = flush() && !bad;
+    ok = fclose(f) == 0 && ok;
+    f = nullptr;
+    return ok;
+  }
+  bool bad = false;
 };
 
 struct Mapped {
@@ -249,6 +285,61 @@ int32_t midas_sites_parse_cell(int32_t kind, const char* text, int64_t n, void* 
   const std::string_view v(text, (size_t)n);
   const bool ok = kind == 0 ? midas::parse_f64_py(v, static_cast<double*>(out8)) : midas::parse_i64_py(v, static_cast<int64_t*>(out8));
   return ok ? MIDAS_SNPS_OK : MIDAS_SNPS_ERR_BAD_LAYOUT;
+}
+
+
+// strain_tracking.py id_markers: site_id, allele, count_samples, count_A, count_T, count_C, count_G per marker
+int32_t midas_sites_write_markers(const char* path, const midas_sites_tables* t, int64_t n_markers, const int32_t* rows7, char* err1024) {
+  if (!path || !t || n_markers < 0 || (n_markers > 0 && !rows7)) return MIDAS_SNPS_ERR_INVALID_ARG;
+  if (err1024) err1024[0] = 0;
+  const int64_t n_sites = (int64_t)t->site_id.off.size() - 1;
+  for (int64_t k = 0; k < n_markers; ++k)
+    if (rows7[7 * k] < 0 || rows7[7 * k] >= n_sites || rows7[7 * k + 1] < 0 || rows7[7 * k + 1] > 3) {
+      fail(err1024, path, 0, "a marker row names a site or an allele that does not exist");
+      return MIDAS_SNPS_ERR_INVALID_ARG;
+    }
+  TextOut out;
+  if (!out.open(path)) { fail(err1024, path, 0, "cannot be written"); return MIDAS_SNPS_ERR_INVALID_ARG; }
+  out.put("site_id\tallele\tcount_samples\tcount_A\tcount_T\tcount_C\tcount_G\n");
+  for (int64_t k = 0; k < n_markers; ++k) {
+    const int32_t* r = rows7 + 7 * k;
+    out.put(t->site_id.at((size_t)r[0]));
+    out.put('\t');
+    out.put("ATCG"[r[1]]);
+    for (int c = 2; c < 7; ++c) { out.put('\t'); out.put_int(r[c]); }
+    out.put('\n');
+  }
+  if (!out.close()) { fail(err1024, path, 0, "cannot be written"); return MIDAS_SNPS_ERR_INVALID_ARG; }
+  return MIDAS_SNPS_OK;
+}
+
+// strain_tracking.py track_markers: sample1, sample2, count1, count2, count_both, count_either for every pair i < j
+int32_t midas_sites_write_pairs(const char* path, const midas_sites_tables* t, int32_t n_samples, const int32_t* sample_row,
+                                const int64_t* both, char* err1024) {
+  if (!path || !t || n_samples < 1 || !sample_row || !both) return MIDAS_SNPS_ERR_INVALID_ARG;
+  if (err1024) err1024[0] = 0;
+  const int64_t n_rows = (int64_t)t->sample_ids.off.size() - 1;
+  for (int32_t s = 0; s < n_samples; ++s)
+    if (sample_row[s] < 0 || sample_row[s] >= n_rows) {
+      fail(err1024, path, 0, "a sample names a row of snps_summary.txt that does not exist");
+      return MIDAS_SNPS_ERR_INVALID_ARG;
+    }
+  TextOut out;
+  if (!out.open(path)) { fail(err1024, path, 0, "cannot be written"); return MIDAS_SNPS_ERR_INVALID_ARG; }
+  out.put("sample1\tsample2\tcount1\tcount2\tcount_both\tcount_either\n");
+  const int64_t S = n_samples;
+  for (int64_t i = 0; i < S; ++i)
+    for (int64_t j = i + 1; j < S; ++j) {
+      const int64_t c1 = both[i * S + i], c2 = both[j * S + j], b = both[i * S + j];
+      out.put(t->sample_ids.at((size_t)sample_row[i]));
+      out.put('\t');
+      out.put(t->sample_ids.at((size_t)sample_row[j]));
+      const int64_t v[4] = {c1, c2, b, c1 + c2 - b};
+      for (int c = 0; c < 4; ++c) { out.put('\t'); out.put_int(v[c]); }
+      out.put('\n');
+    }
+  if (!out.close()) { fail(err1024, path, 0, "cannot be written"); return MIDAS_SNPS_ERR_INVALID_ARG; }
+  return MIDAS_SNPS_OK;
 }
 
 }  // extern "C"

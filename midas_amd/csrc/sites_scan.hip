@@ -17,7 +17,15 @@
 //            is the sequential one, bit for bit; per-gene chains switch accumulators where the gene index changes.
 //            Accumulators live in device memory and carry from group to group
 //   seq      call_consensus.py: one byte per (retained site, sample), sample-major
-// This file is compiled with -ffp-contract=off (build.py): 2*f*(1-f) and d*f round twice, as the interpreter does.
+// strain_tracking.py (midas/analyze/track_strains.py) walks the same rows (RowGroups: chunks, index, parse, side lists):
+//   mark     id_markers: one thread a row counts the samples that have the minor, the major, both alleles and any read
+//            (x >= min_freq and round(x * depth) >= min_reads), folds them onto A, T, C, G and decides the marker; the scan
+//            compacts the marker rows
+//   bits     track_markers: the matched sites of a group (one byte a site from the host: none, major, minor) are ranked by the
+//            scan; one wave calls 64 of them for one sample, its ballot is a word of the bit matrix [sample][word]
+//   pairs    both[i][j] += popcount(B[i][w] & B[j][w]) in 64 x 64 tiles of sample pairs staged through LDS; integer sums, held
+//            on the device across groups
+// This file is compiled with -ffp-contract=off (build.py): 2*f*(1-f), d*f and x*depth round as the interpreter rounds them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -472,146 +480,272 @@ struct Chunk {
   bool at_eof = false;
 };
 
-}  // namespace
-}  // namespace midas
 
-using namespace midas;
+// ---- strain_tracking.py: marker alleles and their sharing between samples -----------------------------------------------------
+// A cell's call (midas/analyze/track_strains.py): the allele with frequency x is present in a sample with depth d != 0 when
+// x >= min_freq and round(x * d) >= min_reads; round() is half to even on the fp64 product: rint.
+constexpr uint32_t kCallNonFinite = 1, kCallMinorLetter = 2, kCallMajorLetter = 3;      // why a site cannot be called
+constexpr int kPairTile = MIDAS_SITES_PAIR_TILE;      // samples a side of a workgroup's tile of pairs
+constexpr int kPairRun = 32;                          // words of every sample staged at a time
+constexpr int kPairPad = kPairTile + 1;               // the staged words lie [word][sample]: 65 keeps the transposing stores apart
 
-extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
-                                    int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
-                                    const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
-                                    const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
-                                    int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
-                                    uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8) {
-  if (!ctx || freq_bytes < 0 || depth_bytes < 0 || (freq_bytes > 0 && !freq) || (depth_bytes > 0 && !depth) || n_sites_max < 0 ||
-      n_samples < 1 || !sample_col || !mean_depth || !fparams5 || !iparams8 || !out_stats16 || (n_sites_max > 0 && !site_mask))
-    return MIDAS_SNPS_ERR_INVALID_ARG;
-  const long long site_depth = iparams8[0], max_sites = iparams8[1], flags = iparams8[2], seq_cap = iparams8[6];
-  const long long n_genes_in = iparams8[3];
-  long long G = iparams8[4], chunk_bytes = iparams8[5];
-  const int weight = flags & MIDAS_SITES_WEIGHT ? 1 : 0, round_freq = flags & MIDAS_SITES_ROUND ? 1 : 0,
-            pooled = flags & MIDAS_SITES_POOLED ? 1 : 0, per_gene = flags & MIDAS_SITES_PER_GENE ? 1 : 0,
-            mask_only = flags & MIDAS_SITES_MASK_ONLY ? 1 : 0, want_seq = flags & MIDAS_SITES_SEQ ? 1 : 0,
-            want_sums = flags & MIDAS_SITES_SUMS ? 1 : 0;
-  const int S = n_samples;
-  if ((per_gene && (!site_gene || n_genes_in < 0)) || (want_seq && (!out_seq || !minor || !major || seq_cap < 0)) ||
-      (want_sums && (!out_pi || !out_snps || !out_sites || !out_depth)) || G < 0 || chunk_bytes < 0)
-    return MIDAS_SNPS_ERR_INVALID_ARG;
-  int n_cols = 0;
-  for (int s = 0; s < S; ++s) {
-    if (sample_col[s] < 0) return MIDAS_SNPS_ERR_INVALID_ARG;
-    n_cols = std::max(n_cols, sample_col[s] + 1);
+struct MarkP {
+  const double* fv;            // [S][stride]
+  const long long* dv;
+  const uint8_t* minor;        // [g] 0..3 = A, T, C, G; anything else: another string
+  const uint8_t* major;
+  long long g, stride;         // rows to call
+  int S;
+  double min_freq, min_reads;
+  long long allele_prev;
+  uint32_t* flag;              // [g] the site is a marker
+  int32_t* row6;               // [g][6] allele, total, count A, T, C, G
+  unsigned long long* err;     // min over (row << 32 | sample << 2 | reason)
+};
+
+// id_markers: count_alleles over the samples in order, then the marker decision
+__global__ __launch_bounds__(256) void ss_mark_kernel(MarkP p) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= p.g) return;
+  const int mi = p.minor[r], ma = p.major[r];
+  int n_minor = 0, n_major = 0, n_both = 0, total = 0;
+  uint32_t why = 0;
+  int s = 0;
+  for (; s < p.S; ++s) {
+    const long long at = (long long)s * p.stride + r;
+    const long long d = p.dv[at];
+    if (d == 0) continue;
+    const double f = p.fv[at];
+    bool has_minor = false, has_major = false;
+    if (f >= p.min_freq) {
+      const double x = f * (double)d;
+      if (!isfinite(x)) { why = kCallNonFinite; break; }
+      if (rint(x) >= p.min_reads) {
+        if (mi > 3) { why = kCallMinorLetter; break; }
+        has_minor = true;
+      }
+    }
+    const double q = 1.0 - f;
+    if (q >= p.min_freq) {
+      const double x = q * (double)d;
+      if (!isfinite(x)) { why = kCallNonFinite; break; }
+      if (rint(x) >= p.min_reads) {
+        if (ma > 3) { why = kCallMajorLetter; break; }
+        has_major = true;
+      }
+    }
+    n_minor += has_minor;
+    n_major += has_major;
+    n_both += has_minor && has_major;
+    ++total;
   }
-  if (per_gene)
-    for (int64_t i = 0; i < n_sites_max; ++i)
-      if (site_gene[i] >= n_genes_in) return MIDAS_SNPS_ERR_INVALID_ARG;
-  ctx->clear_error();
-  ctx->err_read = -1;
-  for (int k = 0; k < 16; ++k) out_stats16[k] = 0;
-  out_stats16[4] = 0;
-  out_stats16[5] = -1;
-  out_stats16[6] = -1;
-  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = 0.f;
-  const long long n_genes = per_gene ? n_genes_in : 1;
-  const long long chains = pooled ? 1 : S;
-  const size_t n_acc = (size_t)(chains * n_genes);
-  if (want_sums)
-    for (size_t k = 0; k < n_acc; ++k) { out_pi[k] = 0.0; out_snps[k] = 0; out_sites[k] = 0; out_depth[k] = 0; }
-  if (n_sites_max == 0) return MIDAS_SNPS_OK;
-  std::vector<int32_t> col_slot((size_t)n_cols, -1);
-  for (int s = 0; s < S; ++s) {
-    if (col_slot[(size_t)sample_col[s]] >= 0) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "a matrix column is selected twice");
-    col_slot[(size_t)sample_col[s]] = s;
+  if (why) {
+    atomicMin(p.err, ((unsigned long long)r << 32) | ((unsigned long long)s << 2) | why);
+    p.flag[r] = 0;
+    return;
   }
-  SS_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  // ---- sizes: rows a group (G) and bytes a chunk, from the caller or from a quarter of the free device memory ---------------
-  constexpr long long kChunkMax = (1ll << 30);       // newline offsets are 32-bit
-  const long long per_row = (long long)S * (8 + 8 + 1 + 2 * (long long)sizeof(SideCell) + (want_seq ? 1 : 0)) + 4 + 4 + 4 + 8 + 1 + 8 + 8;
-  if (G == 0 || chunk_bytes == 0) {
-    size_t free_b = 0, total_b = 0;
-    SS_TRY(hipMemGetInfo(&free_b, &total_b));
-    const long long budget = (long long)(free_b / 4);
-    if (chunk_bytes == 0) chunk_bytes = std::min<long long>(kChunkMax, std::max<long long>(1 << 20, budget / 8));
-    if (G == 0) G = std::max<long long>(1, (budget - std::min(budget / 2, 5 * chunk_bytes / 2)) / per_row);
+  int c[4] = {0, 0, 0, 0};       // sets of samples by letter: a sample that has both counts once where the letters agree
+  if (mi <= 3) c[mi] += n_minor;
+  if (ma <= 3) c[ma] += n_major;
+  if (mi == ma && mi <= 3) c[mi] -= n_both;
+  int letters = 0, rare = -1;    // the smaller of two counts; a tie goes to the earlier of A, T, C, G (a stable sort)
+  for (int k = 0; k < 4; ++k) {
+    if (c[k] <= 0) continue;
+    ++letters;
+    if (rare < 0 || c[k] < c[rare]) rare = k;
   }
-  chunk_bytes = std::min(std::max<long long>(chunk_bytes, 64), kChunkMax);
-  chunk_bytes = std::min(chunk_bytes, std::max<long long>(64, std::max(freq_bytes, depth_bytes) + 1));
-  G = std::min<long long>(std::min<long long>(G, n_sites_max), chunk_bytes);
-  G = std::max<long long>(G, 1);
-  const size_t cells = (size_t)G * (size_t)S;
-  if (cells > 0xFFFFFFF0ull) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a row group beyond 2^32 cells: lower group_rows");
-  SsBufs dev;
-  SsEvents ev;
-  for (auto& x : ev.e) SS_TRY(hipEventCreate(&x));
+  const bool marker = letters == 2 && (long long)c[rare] <= p.allele_prev;
+  p.flag[r] = marker ? 1u : 0u;
+  int32_t* o = p.row6 + 6 * r;
+  o[0] = rare; o[1] = total; o[2] = c[0]; o[3] = c[1]; o[4] = c[2]; o[5] = c[3];
+}
+
+// the markers of the group, in row order: out[rank] = row, allele, total, counts
+__global__ __launch_bounds__(256) void ss_mark_compact_kernel(const uint32_t* flag, const uint32_t* rank, const int32_t* row6, long long g,
+                                                              long long base, int32_t* out7) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= g || !flag[r]) return;
+  int32_t* o = out7 + 7 * (long long)rank[r];
+  o[0] = (int32_t)(base + r);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) o[1 + k] = row6[6 * r + k];
+}
+
+__global__ __launch_bounds__(256) void ss_which_flag_kernel(const uint8_t* which, long long g, uint32_t* flag) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r < g) flag[r] = which[r] != 0 ? 1u : 0u;
+}
+
+// matched site k of the group -> its row and its allele (1 major, 2 minor): row << 2 | which
+__global__ __launch_bounds__(256) void ss_which_list_kernel(const uint8_t* which, const uint32_t* rank, long long g, uint32_t* list) {
+  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (r < g && which[r] != 0) list[rank[r]] = ((uint32_t)r << 2) | which[r];
+}
+
+// track_markers: the bit matrix.  One wave a (sample, 64 matched sites): a lane calls its site, the ballot is the word.
+__global__ __launch_bounds__(256) void ss_bits_kernel(const double* fv, const long long* dv, const uint32_t* list, long long m, long long stride,
+                                                      int S, double min_freq, double min_reads, unsigned long long* bits, long long wstride,
+                                                      unsigned long long* err) {
+  const int s = blockIdx.y * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (s >= S) return;                                  // (the whole wave)
+  const long long k = (long long)blockIdx.x * 64 + lane;
+  bool present = false;
+  if (k < m) {
+    const uint32_t e = list[k];
+    const long long r = e >> 2;
+    const long long at = (long long)s * stride + r;
+    const long long d = dv[at];
+    if (d != 0) {
+      const double f = fv[at];
+      const double mf = (e & 3u) == 1u ? 1.0 - f : f;
+      const double x = mf * (double)d;
+      if (!isfinite(x)) atomicMin(err, ((unsigned long long)r << 32) | ((unsigned long long)s << 2) | kCallNonFinite);
+      else present = mf >= min_freq && rint(x) >= min_reads;
+    }
+  }
+  const unsigned long long word = __ballot(present);
+  if (lane == 0) bits[(long long)s * wstride + blockIdx.x] = word;
+}
+
+// both[i][j] += sum over words of popcount(B[i][w] & B[j][w]) for i <= j.  A workgroup owns a 64 x 64 tile of pairs on or
+// above the diagonal (blockIdx.x counts those tiles row by row) and a run of words (blockIdx.y); it stages 32 words of its
+// two strips of samples in LDS, [word][sample], and a thread keeps a 4 x 4 part of the tile: rows ty + 16 i, columns
+// tx + 16 j, so that a wave's reads of one word are 16 neighbouring columns and 4 rows (broadcast).  Sums of integers: the
+// order of the groups, of the word runs and of the atomics does not matter.
+__global__ __launch_bounds__(256) void ss_pairs_kernel(const unsigned long long* bits, long long wstride, long long n_words, long long run_words,
+                                                       int S, int tiles_side, unsigned long long* both) {
+  __shared__ unsigned long long sa[kPairRun][kPairPad], sb[kPairRun][kPairPad];
+  int ti = 0, left = blockIdx.x;
+  while (left >= tiles_side - ti) { left -= tiles_side - ti; ++ti; }
+  const int tj = ti + left;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const long long w0 = (long long)blockIdx.y * run_words, w1 = w0 + run_words < n_words ? w0 + run_words : n_words;
+  uint32_t sum[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sum[i][j] = 0;
+  for (long long k0 = w0; k0 < w1; k0 += kPairRun) {
+#pragma unroll
+    for (int it = 0; it < kPairTile * kPairRun / 256; ++it) {
+      const int e = it * 256 + tid, s = e / kPairRun, k = e % kPairRun;
+      const long long w = k0 + k;
+      const int gi = ti * kPairTile + s, gj = tj * kPairTile + s;
+      sa[k][s] = (gi < S && w < w1) ? bits[(long long)gi * wstride + w] : 0ull;
+      sb[k][s] = (gj < S && w < w1) ? bits[(long long)gj * wstride + w] : 0ull;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int k = 0; k < kPairRun; ++k) {
+      unsigned long long a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { a[i] = sa[k][ty + 16 * i]; b[i] = sb[k][tx + 16 * i]; }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sum[i][j] += (uint32_t)__popcll(a[i] & b[j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int gi = ti * kPairTile + ty + 16 * i, gj = tj * kPairTile + tx + 16 * j;
+      if (gi <= gj && gj < S && sum[i][j]) atomicAdd(&both[(long long)gi * S + gj], (unsigned long long)sum[i][j]);
+    }
+}
+
+// The rows of the two matrices on the device, a group at a time: upload, line index, cell parse, side-list patching.  Every
+// entry point of this file walks the tables through it: next() leaves the group's cells in d_fv / d_dv, [sample][G].
+struct RowGroups {
+  midas_snps_ctx* ctx;
+  hipStream_t st;
+  SsBufs& dev;
+  SsEvents& ev;                  // e[1], e[2], e[3] are used here
+  float* ms;                     // [0] upload + index (host clock), [1] index, [2] parse
+  int64_t* stats;                // the caller's out_stats16: [2] / [3] cells converted by the host, [0], [4..6] on a bad row
+  int S = 0, n_cols = 0;
+  long long G = 0, chunk_bytes = 0, n_sites_max = 0;
+  size_t cells = 0;
   Chunk ck[2];
-  ck[0].host = freq; ck[0].bytes = freq_bytes;
-  ck[1].host = depth; ck[1].bytes = depth_bytes;
-  auto alloc_chunk = [&](Chunk& c, long long cb) -> int32_t {
+  uint32_t* d_scratch = nullptr;
+  double* d_fv = nullptr;
+  long long* d_dv = nullptr;
+  int32_t* d_col_slot = nullptr;
+  long long* d_patch_at = nullptr;
+  void* d_patch_v = nullptr;
+  size_t patch_cap = 0;
+  std::vector<SideCell> side_h;
+  std::vector<long long> patch_at;
+  std::vector<double> patch_f;
+  std::vector<long long> patch_i;
+  long long base = 0, groups = 0;
+  uint32_t end_at[2] = {0, 0};
+  unsigned long long bad[2] = {kNoBad, kNoBad};
+
+  static constexpr long long kChunkMax = (1ll << 30);       // newline offsets are 32-bit
+
+  RowGroups(midas_snps_ctx* c, SsBufs& d, SsEvents& e, float* ms8, int64_t* stats16) : ctx(c), st(c->stream), dev(d), ev(e), ms(ms8), stats(stats16) {}
+
+  int32_t alloc_chunk(Chunk& c, long long cb) {
     const size_t padded = ((size_t)cb + 1 + 15) / 16 * 16;
     SS_TRY(dev.get(&c.d_text, padded));
     SS_TRY(dev.get(&c.d_counts, padded / 16 * 4));
     return MIDAS_SNPS_OK;
-  };
-  for (Chunk& c : ck) {
-    int32_t rc = alloc_chunk(c, chunk_bytes);
-    if (rc != MIDAS_SNPS_OK) return rc;
-    SS_TRY(dev.get(&c.d_ends, ((size_t)G + 1) * 4));
-    SS_TRY(dev.get(&c.d_side, cells * sizeof(SideCell)));
-    SS_TRY(dev.get(&c.d_side_n, 4));
-    SS_TRY(dev.get(&c.d_bad, 8));
   }
-  uint32_t* d_scratch = nullptr;
-  SS_TRY(dev.get(&d_scratch, std::max(scan_scratch_words((kChunkMax + 16) / 16), scan_scratch_words(G)) * 4));
-  double *d_fv = nullptr, *d_pooled = nullptr, *d_mean = nullptr, *d_pi = nullptr;
-  long long *d_dv = nullptr, *d_last = nullptr, *d_snps = nullptr, *d_sites = nullptr, *d_depth = nullptr, *d_patch_at = nullptr;
-  uint8_t *d_cell = nullptr, *d_mask = nullptr, *d_final = nullptr, *d_seq = nullptr;
-  uint32_t *d_keep = nullptr, *d_rank = nullptr;
-  int32_t *d_gene = nullptr, *d_col_slot = nullptr;
-  char *d_minor = nullptr, *d_major = nullptr;
-  unsigned long long* d_no_gene = nullptr;
-  void* d_patch_v = nullptr;
-  size_t patch_cap = 0;
-  SS_TRY(dev.get(&d_fv, cells * 8));
-  SS_TRY(dev.get(&d_dv, cells * 8));
-  SS_TRY(dev.get(&d_cell, cells));
-  SS_TRY(dev.get(&d_mask, (size_t)G));
-  SS_TRY(dev.get(&d_final, (size_t)G));
-  SS_TRY(dev.get(&d_keep, (size_t)G * 4));
-  SS_TRY(dev.get(&d_rank, (size_t)G * 4));
-  SS_TRY(dev.get(&d_pooled, (size_t)G * 8));
-  SS_TRY(dev.get(&d_mean, (size_t)S * 8));
-  SS_TRY(dev.get(&d_col_slot, (size_t)n_cols * 4));
-  SS_TRY(dev.get(&d_last, 8));
-  SS_TRY(dev.get(&d_no_gene, 8));
-  SS_TRY(hipMemsetAsync(d_no_gene, 0, 8, st));
-  if (per_gene) SS_TRY(dev.get(&d_gene, (size_t)G * 4));
-  if (want_seq) {
-    SS_TRY(dev.get(&d_seq, cells));
-    SS_TRY(dev.get(&d_minor, (size_t)G));
-    SS_TRY(dev.get(&d_major, (size_t)G));
+
+  // sizes: rows a group (G) and bytes a chunk, from the caller or from a quarter of the free device memory; per_row = the
+  // device bytes a row of the group takes in the caller's and in these buffers
+  int32_t init(const char* freq, long long freq_bytes, const char* depth, long long depth_bytes, long long n_max, int n_samples,
+               const std::vector<int32_t>& col_slot, long long G_in, long long chunk_in, long long per_row) {
+    S = n_samples;
+    n_cols = (int)col_slot.size();
+    n_sites_max = n_max;
+    G = G_in;
+    chunk_bytes = chunk_in;
+    if (G == 0 || chunk_bytes == 0) {
+      size_t free_b = 0, total_b = 0;
+      SS_TRY(hipMemGetInfo(&free_b, &total_b));
+      const long long budget = (long long)(free_b / 4);
+      if (chunk_bytes == 0) chunk_bytes = std::min<long long>(kChunkMax, std::max<long long>(1 << 20, budget / 8));
+      if (G == 0) G = std::max<long long>(1, (budget - std::min(budget / 2, 5 * chunk_bytes / 2)) / per_row);
+    }
+    chunk_bytes = std::min(std::max<long long>(chunk_bytes, 64), kChunkMax);
+    chunk_bytes = std::min(chunk_bytes, std::max<long long>(64, std::max(freq_bytes, depth_bytes) + 1));
+    G = std::min<long long>(std::min<long long>(G, n_sites_max), chunk_bytes);
+    G = std::max<long long>(G, 1);
+    cells = (size_t)G * (size_t)S;
+    if (cells > 0xFFFFFFF0ull) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a row group beyond 2^32 cells: lower group_rows");
+    for (auto& x : ev.e) SS_TRY(hipEventCreate(&x));
+    ck[0].host = freq; ck[0].bytes = freq_bytes;
+    ck[1].host = depth; ck[1].bytes = depth_bytes;
+    for (Chunk& c : ck) {
+      int32_t rc = alloc_chunk(c, chunk_bytes);
+      if (rc != MIDAS_SNPS_OK) return rc;
+      SS_TRY(dev.get(&c.d_ends, ((size_t)G + 1) * 4));
+      SS_TRY(dev.get(&c.d_side, cells * sizeof(SideCell)));
+      SS_TRY(dev.get(&c.d_side_n, 4));
+      SS_TRY(dev.get(&c.d_bad, 8));
+    }
+    SS_TRY(dev.get(&d_scratch, std::max(scan_scratch_words((kChunkMax + 16) / 16), scan_scratch_words(G)) * 4));
+    SS_TRY(dev.get(&d_fv, cells * 8));
+    SS_TRY(dev.get(&d_dv, cells * 8));
+    SS_TRY(dev.get(&d_col_slot, (size_t)n_cols * 4));
+    SS_TRY(hipMemcpyAsync(d_col_slot, col_slot.data(), (size_t)n_cols * 4, hipMemcpyHostToDevice, st));
+    SS_TRY(hipStreamSynchronize(st));          // (col_slot is the caller's)
+    return MIDAS_SNPS_OK;
   }
-  if (want_sums) {
-    SS_TRY(dev.get(&d_pi, n_acc * 8));
-    SS_TRY(dev.get(&d_snps, n_acc * 8));
-    SS_TRY(dev.get(&d_sites, n_acc * 8));
-    SS_TRY(dev.get(&d_depth, n_acc * 8));
-    SS_TRY(hipMemsetAsync(d_pi, 0, n_acc * 8, st));
-    SS_TRY(hipMemsetAsync(d_snps, 0, n_acc * 8, st));
-    SS_TRY(hipMemsetAsync(d_sites, 0, n_acc * 8, st));
-    SS_TRY(hipMemsetAsync(d_depth, 0, n_acc * 8, st));
-  }
-  SS_TRY(hipMemcpyAsync(d_mean, mean_depth, (size_t)S * 8, hipMemcpyHostToDevice, st));
-  SS_TRY(hipMemcpyAsync(d_col_slot, col_slot.data(), (size_t)n_cols * 4, hipMemcpyHostToDevice, st));
-  float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, site, order, sums, seq, download
-  auto lap = [&](int a, int b, int slot) -> hipError_t {
+
+  hipError_t lap(int a, int b, int slot) {
     float t = 0.f;
     const hipError_t e = hipEventElapsedTime(&t, ev.e[a], ev.e[b]);
     if (e == hipSuccess) ms[slot] += t;
     return e;
-  };
+  }
+
   // upload the next chunk of one matrix and index its lines
-  auto load_chunk = [&](Chunk& c) -> int32_t {
+  int32_t load_chunk(Chunk& c) {
     const long long left = c.bytes - c.at;
     long long n = std::min(left, chunk_bytes);
     c.at_eof = n == left;
@@ -641,100 +775,247 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     SS_TRY(lap(1, 2, 1));
     c.lines = (long long)last_count + last_prefix;
     return MIDAS_SNPS_OK;
-  };
-  static const char* kFile[2] = {"freq", "depth"};
-  std::vector<SideCell> side_h;
-  std::vector<long long> patch_at;
-  std::vector<double> patch_f;
-  std::vector<long long> patch_i;
-  long long base = 0, kept = 0, groups = 0;
-  bool stop = false;
-  while (!stop && base < n_sites_max) {
-    // ---- the group's rows: complete lines of both chunks ----------------------------------------------------------------
-    const auto t_load = std::chrono::steady_clock::now();
-    for (Chunk& c : ck) {
-      int32_t rc = load_chunk(c);
-      if (rc != MIDAS_SNPS_OK) return rc;
-    }
-    // (host clock around copies that end in a synchronise: upload + index of both chunks; the index alone is ms[1])
-    ms[0] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_load).count();
-    long long g = std::min(std::min(ck[0].lines, ck[1].lines), std::min(G, n_sites_max - base));
-    if (g == 0) {
-      bool grow = false;
-      for (Chunk& c : ck)
-        if (c.lines == 0 && !c.at_eof) grow = true;
-      if (!grow) break;                    // one of the matrices has no row left: the reference stops here too
-      if (chunk_bytes >= kChunkMax) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a matrix row longer than 1 GiB");
-      chunk_bytes = std::min(kChunkMax, chunk_bytes * 2);
+  }
+
+  // the next group: *g_out complete rows of both matrices parsed into d_fv / d_dv, or 0 when the rows are used up
+  int32_t next(long long* g_out) {
+    *g_out = 0;
+    while (base < n_sites_max) {
+      // ---- the group's rows: complete lines of both chunks ----------------------------------------------------------------
+      const auto t_load = std::chrono::steady_clock::now();
       for (Chunk& c : ck) {
-        int32_t rc = alloc_chunk(c, chunk_bytes);
+        int32_t rc = load_chunk(c);
         if (rc != MIDAS_SNPS_OK) return rc;
       }
-      continue;
-    }
-    ++groups;
-    // ---- parse ---------------------------------------------------------------------------------------------------------
-    SS_TRY(hipEventRecord(ev.e[2], st));
-    for (int m = 0; m < 2; ++m) {
-      Chunk& c = ck[m];
-      SS_TRY(hipMemsetAsync(c.d_side_n, 0, 4, st));
-      SS_TRY(hipMemsetAsync(c.d_bad, 0xFF, 8, st));
-      ParseP pp;
-      pp.text = c.d_text; pp.ends = c.d_ends; pp.g = g; pp.stride = G; pp.col_slot = d_col_slot; pp.n_cols = n_cols;
-      pp.val = m == 0 ? (void*)d_fv : (void*)d_dv; pp.side = c.d_side; pp.side_n = c.d_side_n; pp.side_cap = (uint32_t)cells;
-      pp.bad = c.d_bad;
-      if (m == 0) hipLaunchKernelGGL(ss_parse_kernel<false>, dim3(nblocks(g, 256)), dim3(256), 0, st, pp);
-      else hipLaunchKernelGGL(ss_parse_kernel<true>, dim3(nblocks(g, 256)), dim3(256), 0, st, pp);
-      SS_TRY(hipGetLastError());
-    }
-    SS_TRY(hipEventRecord(ev.e[3], st));
-    uint32_t side_n[2] = {0, 0}, end_at[2] = {0, 0};
-    unsigned long long bad[2] = {kNoBad, kNoBad};
-    for (int m = 0; m < 2; ++m) {
-      SS_TRY(hipMemcpyAsync(&side_n[m], ck[m].d_side_n, 4, hipMemcpyDeviceToHost, st));
-      SS_TRY(hipMemcpyAsync(&bad[m], ck[m].d_bad, 8, hipMemcpyDeviceToHost, st));
-      SS_TRY(hipMemcpyAsync(&end_at[m], ck[m].d_ends + g - 1, 4, hipMemcpyDeviceToHost, st));
-    }
-    SS_TRY(hipStreamSynchronize(st));
-    SS_TRY(lap(2, 3, 2));
-    // ---- the side lists: cells off the fast path, converted by the host's exact parser and patched in ----------------------
-    for (int m = 0; m < 2; ++m) {
-      const uint32_t n = side_n[m];
-      out_stats16[2 + m] += n;
-      if (n == 0) continue;
-      side_h.resize(n);
-      SS_TRY(hipMemcpy(side_h.data(), ck[m].d_side, (size_t)n * sizeof(SideCell), hipMemcpyDeviceToHost));
-      patch_at.clear(); patch_f.clear(); patch_i.clear();
-      const char* text = ck[m].host + ck[m].at;
-      for (const SideCell& sc : side_h) {
-        // (a cell that starts at the appended terminator of an unterminated last line is empty: off + len stays inside)
-        const std::string_view cell(text + sc.off, sc.len);
-        bool ok;
-        double vf = 0.0;
-        int64_t vi = 0;
-        if (m == 0) ok = parse_f64_py(cell, &vf);
-        else ok = parse_i64_py(cell, &vi);
-        if (!ok) {
-          bad[m] = std::min(bad[m], ((unsigned long long)sc.row << 32) | (sc.slot + 1ull));
-          continue;
+      // (host clock around copies that end in a synchronise: upload + index of both chunks; the index alone is ms[1])
+      ms[0] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_load).count();
+      const long long g = std::min(std::min(ck[0].lines, ck[1].lines), std::min(G, n_sites_max - base));
+      if (g == 0) {
+        bool grow = false;
+        for (Chunk& c : ck)
+          if (c.lines == 0 && !c.at_eof) grow = true;
+        if (!grow) return MIDAS_SNPS_OK;     // one of the matrices has no row left: the reference stops here too
+        if (chunk_bytes >= kChunkMax) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a matrix row longer than 1 GiB");
+        chunk_bytes = std::min(kChunkMax, chunk_bytes * 2);
+        for (Chunk& c : ck) {
+          int32_t rc = alloc_chunk(c, chunk_bytes);
+          if (rc != MIDAS_SNPS_OK) return rc;
         }
-        patch_at.push_back((long long)sc.slot * G + sc.row);
-        if (m == 0) patch_f.push_back(vf); else patch_i.push_back((long long)vi);
+        continue;
       }
-      const size_t np = patch_at.size();
-      if (np == 0) continue;
-      if (np > patch_cap) {
-        patch_cap = std::max(np, patch_cap * 2);
-        SS_TRY(dev.get(&d_patch_at, patch_cap * 8));
-        SS_TRY(dev.get((char**)&d_patch_v, patch_cap * 8));
+      ++groups;
+      // ---- parse ---------------------------------------------------------------------------------------------------------
+      SS_TRY(hipEventRecord(ev.e[2], st));
+      for (int m = 0; m < 2; ++m) {
+        Chunk& c = ck[m];
+        SS_TRY(hipMemsetAsync(c.d_side_n, 0, 4, st));
+        SS_TRY(hipMemsetAsync(c.d_bad, 0xFF, 8, st));
+        ParseP pp;
+        pp.text = c.d_text; pp.ends = c.d_ends; pp.g = g; pp.stride = G; pp.col_slot = d_col_slot; pp.n_cols = n_cols;
+        pp.val = m == 0 ? (void*)d_fv : (void*)d_dv; pp.side = c.d_side; pp.side_n = c.d_side_n; pp.side_cap = (uint32_t)cells;
+        pp.bad = c.d_bad;
+        if (m == 0) hipLaunchKernelGGL(ss_parse_kernel<false>, dim3(nblocks(g, 256)), dim3(256), 0, st, pp);
+        else hipLaunchKernelGGL(ss_parse_kernel<true>, dim3(nblocks(g, 256)), dim3(256), 0, st, pp);
+        SS_TRY(hipGetLastError());
       }
-      SS_TRY(hipMemcpyAsync(d_patch_at, patch_at.data(), np * 8, hipMemcpyHostToDevice, st));
-      SS_TRY(hipMemcpyAsync(d_patch_v, m == 0 ? (const void*)patch_f.data() : (const void*)patch_i.data(), np * 8, hipMemcpyHostToDevice, st));
-      if (m == 0) hipLaunchKernelGGL(ss_patch_kernel<double>, dim3(nblocks((long long)np, 256)), dim3(256), 0, st, d_fv, d_patch_at, (const double*)d_patch_v, (long long)np);
-      else hipLaunchKernelGGL(ss_patch_kernel<long long>, dim3(nblocks((long long)np, 256)), dim3(256), 0, st, d_dv, d_patch_at, (const long long*)d_patch_v, (long long)np);
-      SS_TRY(hipGetLastError());
-      SS_TRY(hipStreamSynchronize(st));       // (the host vectors are reused by the other matrix)
+      SS_TRY(hipEventRecord(ev.e[3], st));
+      uint32_t side_n[2] = {0, 0};
+      end_at[0] = end_at[1] = 0;
+      bad[0] = bad[1] = kNoBad;
+      for (int m = 0; m < 2; ++m) {
+        SS_TRY(hipMemcpyAsync(&side_n[m], ck[m].d_side_n, 4, hipMemcpyDeviceToHost, st));
+        SS_TRY(hipMemcpyAsync(&bad[m], ck[m].d_bad, 8, hipMemcpyDeviceToHost, st));
+        SS_TRY(hipMemcpyAsync(&end_at[m], ck[m].d_ends + g - 1, 4, hipMemcpyDeviceToHost, st));
+      }
+      SS_TRY(hipStreamSynchronize(st));
+      SS_TRY(lap(2, 3, 2));
+      // ---- the side lists: cells off the fast path, converted by the host's exact parser and patched in ----------------------
+      for (int m = 0; m < 2; ++m) {
+        const uint32_t n = side_n[m];
+        stats[2 + m] += n;
+        if (n == 0) continue;
+        side_h.resize(n);
+        SS_TRY(hipMemcpy(side_h.data(), ck[m].d_side, (size_t)n * sizeof(SideCell), hipMemcpyDeviceToHost));
+        patch_at.clear(); patch_f.clear(); patch_i.clear();
+        const char* text = ck[m].host + ck[m].at;
+        for (const SideCell& sc : side_h) {
+          // (a cell that starts at the appended terminator of an unterminated last line is empty: off + len stays inside)
+          const std::string_view cell(text + sc.off, sc.len);
+          bool ok;
+          double vf = 0.0;
+          int64_t vi = 0;
+          if (m == 0) ok = parse_f64_py(cell, &vf);
+          else ok = parse_i64_py(cell, &vi);
+          if (!ok) {
+            bad[m] = std::min(bad[m], ((unsigned long long)sc.row << 32) | (sc.slot + 1ull));
+            continue;
+          }
+          patch_at.push_back((long long)sc.slot * G + sc.row);
+          if (m == 0) patch_f.push_back(vf); else patch_i.push_back((long long)vi);
+        }
+        const size_t np = patch_at.size();
+        if (np == 0) continue;
+        if (np > patch_cap) {
+          patch_cap = std::max(np, patch_cap * 2);
+          SS_TRY(dev.get(&d_patch_at, patch_cap * 8));
+          SS_TRY(dev.get((char**)&d_patch_v, patch_cap * 8));
+        }
+        SS_TRY(hipMemcpyAsync(d_patch_at, patch_at.data(), np * 8, hipMemcpyHostToDevice, st));
+        SS_TRY(hipMemcpyAsync(d_patch_v, m == 0 ? (const void*)patch_f.data() : (const void*)patch_i.data(), np * 8, hipMemcpyHostToDevice, st));
+        if (m == 0) hipLaunchKernelGGL(ss_patch_kernel<double>, dim3(nblocks((long long)np, 256)), dim3(256), 0, st, d_fv, d_patch_at, (const double*)d_patch_v, (long long)np);
+        else hipLaunchKernelGGL(ss_patch_kernel<long long>, dim3(nblocks((long long)np, 256)), dim3(256), 0, st, d_dv, d_patch_at, (const long long*)d_patch_v, (long long)np);
+        SS_TRY(hipGetLastError());
+        SS_TRY(hipStreamSynchronize(st));       // (the host vectors are reused by the other matrix)
+      }
+      *g_out = g;
+      return MIDAS_SNPS_OK;
     }
+    return MIDAS_SNPS_OK;
+  }
+
+  // a short row or a cell that is no number among the first read_rows rows of the group: the error, with its place in stats
+  int32_t check_rows(long long read_rows) {
+    static const char* kFile[2] = {"freq", "depth"};
+    for (int m = 0; m < 2; ++m) {
+      if (bad[m] == kNoBad || (long long)(bad[m] >> 32) >= read_rows) continue;
+      const long long row = base + (long long)(bad[m] >> 32);
+      const long long slot = (long long)(bad[m] & 0xFFFFFFFFull) - 1;
+      stats[4] = m + 1;
+      stats[5] = row;
+      stats[6] = slot;
+      stats[0] = base;
+      char buf[160];
+      if (slot < 0) snprintf(buf, sizeof buf, "%s matrix, data row %lld: fewer than %d sample columns", kFile[m], row, n_cols);
+      else snprintf(buf, sizeof buf, "%s matrix, data row %lld, sample %lld: not a number", kFile[m], row, slot);
+      return ss_fail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+    }
+    return MIDAS_SNPS_OK;
+  }
+
+  // the first of the group's first read_rows rows that is short or holds a cell that is no number; -1: none
+  long long first_bad_row(long long read_rows) const {
+    long long row = -1;
+    for (int m = 0; m < 2; ++m) {
+      if (bad[m] == kNoBad || (long long)(bad[m] >> 32) >= read_rows) continue;
+      if (row < 0 || (long long)(bad[m] >> 32) < row) row = (long long)(bad[m] >> 32);
+    }
+    return row;
+  }
+
+  // the group is done with: the next one starts behind its last row
+  void advance(long long g) {
+    base += g;
+    for (int m = 0; m < 2; ++m) ck[m].at = std::min(ck[m].bytes, ck[m].at + (long long)end_at[m] + 1);
+  }
+};
+
+}  // namespace
+}  // namespace midas
+
+using namespace midas;
+
+extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                    int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                                    const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                                    const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
+                                    int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
+                                    uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8) {
+  if (!ctx || freq_bytes < 0 || depth_bytes < 0 || (freq_bytes > 0 && !freq) || (depth_bytes > 0 && !depth) || n_sites_max < 0 ||
+      n_samples < 1 || !sample_col || !mean_depth || !fparams5 || !iparams8 || !out_stats16 || (n_sites_max > 0 && !site_mask))
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  const long long site_depth = iparams8[0], max_sites = iparams8[1], flags = iparams8[2], seq_cap = iparams8[6];
+  const long long n_genes_in = iparams8[3];
+  const int weight = flags & MIDAS_SITES_WEIGHT ? 1 : 0, round_freq = flags & MIDAS_SITES_ROUND ? 1 : 0,
+            pooled = flags & MIDAS_SITES_POOLED ? 1 : 0, per_gene = flags & MIDAS_SITES_PER_GENE ? 1 : 0,
+            mask_only = flags & MIDAS_SITES_MASK_ONLY ? 1 : 0, want_seq = flags & MIDAS_SITES_SEQ ? 1 : 0,
+            want_sums = flags & MIDAS_SITES_SUMS ? 1 : 0;
+  const int S = n_samples;
+  if ((per_gene && (!site_gene || n_genes_in < 0)) || (want_seq && (!out_seq || !minor || !major || seq_cap < 0)) ||
+      (want_sums && (!out_pi || !out_snps || !out_sites || !out_depth)) || iparams8[4] < 0 || iparams8[5] < 0)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  int n_cols = 0;
+  for (int s = 0; s < S; ++s) {
+    if (sample_col[s] < 0) return MIDAS_SNPS_ERR_INVALID_ARG;
+    n_cols = std::max(n_cols, sample_col[s] + 1);
+  }
+  if (per_gene)
+    for (int64_t i = 0; i < n_sites_max; ++i)
+      if (site_gene[i] >= n_genes_in) return MIDAS_SNPS_ERR_INVALID_ARG;
+  ctx->clear_error();
+  ctx->err_read = -1;
+  for (int k = 0; k < 16; ++k) out_stats16[k] = 0;
+  out_stats16[4] = 0;
+  out_stats16[5] = -1;
+  out_stats16[6] = -1;
+  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = 0.f;
+  const long long n_genes = per_gene ? n_genes_in : 1;
+  const long long chains = pooled ? 1 : S;
+  const size_t n_acc = (size_t)(chains * n_genes);
+  if (want_sums)
+    for (size_t k = 0; k < n_acc; ++k) { out_pi[k] = 0.0; out_snps[k] = 0; out_sites[k] = 0; out_depth[k] = 0; }
+  if (n_sites_max == 0) return MIDAS_SNPS_OK;
+  std::vector<int32_t> col_slot((size_t)n_cols, -1);
+  for (int s = 0; s < S; ++s) {
+    if (col_slot[(size_t)sample_col[s]] >= 0) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "a matrix column is selected twice");
+    col_slot[(size_t)sample_col[s]] = s;
+  }
+  SS_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const long long per_row = (long long)S * (8 + 8 + 1 + 2 * (long long)sizeof(SideCell) + (want_seq ? 1 : 0)) + 4 + 4 + 4 + 8 + 1 + 8 + 8;
+  SsBufs dev;
+  SsEvents ev;
+  float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, site, order, sums, seq, download
+  RowGroups rg(ctx, dev, ev, ms, out_stats16);
+  {
+    const int32_t rc = rg.init(freq, freq_bytes, depth, depth_bytes, n_sites_max, S, col_slot, iparams8[4], iparams8[5], per_row);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
+  const long long G = rg.G;
+  const size_t cells = rg.cells;
+  double *d_fv = rg.d_fv, *d_pooled = nullptr, *d_mean = nullptr, *d_pi = nullptr;
+  long long *d_dv = rg.d_dv, *d_last = nullptr, *d_snps = nullptr, *d_sites = nullptr, *d_depth = nullptr;
+  uint8_t *d_cell = nullptr, *d_mask = nullptr, *d_final = nullptr, *d_seq = nullptr;
+  uint32_t *d_keep = nullptr, *d_rank = nullptr, *d_scratch = rg.d_scratch;
+  int32_t* d_gene = nullptr;
+  char *d_minor = nullptr, *d_major = nullptr;
+  unsigned long long* d_no_gene = nullptr;
+  SS_TRY(dev.get(&d_cell, cells));
+  SS_TRY(dev.get(&d_mask, (size_t)G));
+  SS_TRY(dev.get(&d_final, (size_t)G));
+  SS_TRY(dev.get(&d_keep, (size_t)G * 4));
+  SS_TRY(dev.get(&d_rank, (size_t)G * 4));
+  SS_TRY(dev.get(&d_pooled, (size_t)G * 8));
+  SS_TRY(dev.get(&d_mean, (size_t)S * 8));
+  SS_TRY(dev.get(&d_last, 8));
+  SS_TRY(dev.get(&d_no_gene, 8));
+  SS_TRY(hipMemsetAsync(d_no_gene, 0, 8, st));
+  if (per_gene) SS_TRY(dev.get(&d_gene, (size_t)G * 4));
+  if (want_seq) {
+    SS_TRY(dev.get(&d_seq, cells));
+    SS_TRY(dev.get(&d_minor, (size_t)G));
+    SS_TRY(dev.get(&d_major, (size_t)G));
+  }
+  if (want_sums) {
+    SS_TRY(dev.get(&d_pi, n_acc * 8));
+    SS_TRY(dev.get(&d_snps, n_acc * 8));
+    SS_TRY(dev.get(&d_sites, n_acc * 8));
+    SS_TRY(dev.get(&d_depth, n_acc * 8));
+    SS_TRY(hipMemsetAsync(d_pi, 0, n_acc * 8, st));
+    SS_TRY(hipMemsetAsync(d_snps, 0, n_acc * 8, st));
+    SS_TRY(hipMemsetAsync(d_sites, 0, n_acc * 8, st));
+    SS_TRY(hipMemsetAsync(d_depth, 0, n_acc * 8, st));
+  }
+  SS_TRY(hipMemcpyAsync(d_mean, mean_depth, (size_t)S * 8, hipMemcpyHostToDevice, st));
+  long long kept = 0;
+  bool stop = false;
+  while (!stop) {
+    long long g = 0;
+    {
+      const int32_t rc = rg.next(&g);
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
+    if (g == 0) break;
+    const long long base = rg.base;
     // ---- site kernel, order, sums, sequences ---------------------------------------------------------------------------
     SS_TRY(hipMemcpyAsync(d_mask, site_mask + base, (size_t)g, hipMemcpyHostToDevice, st));
     if (per_gene) SS_TRY(hipMemcpyAsync(d_gene, site_gene + base, (size_t)g * 4, hipMemcpyHostToDevice, st));
@@ -777,26 +1058,16 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     }
     SS_TRY(hipEventRecord(ev.e[7], st));
     SS_TRY(hipStreamSynchronize(st));
-    SS_TRY(lap(3, 4, 3));
-    SS_TRY(lap(4, 5, 4));
-    SS_TRY(lap(5, 6, 5));
-    SS_TRY(lap(6, 7, 6));
+    SS_TRY(rg.lap(3, 4, 3));
+    SS_TRY(rg.lap(4, 5, 4));
+    SS_TRY(rg.lap(5, 6, 5));
+    SS_TRY(rg.lap(6, 7, 6));
     long long kept_g = (long long)last_rank + last_keep;
     if (max_sites >= 0) kept_g = std::min(kept_g, max_sites - kept);
     // the rows the reference reads: all of the group, or up to the one after the row that fills max_sites
-    const long long read_rows = last_row >= 0 ? last_row + 2 : g;
-    for (int m = 0; m < 2; ++m) {
-      if (bad[m] == kNoBad || (long long)(bad[m] >> 32) >= read_rows) continue;
-      const long long row = base + (long long)(bad[m] >> 32);
-      const long long slot = (long long)(bad[m] & 0xFFFFFFFFull) - 1;
-      out_stats16[4] = m + 1;
-      out_stats16[5] = row;
-      out_stats16[6] = slot;
-      out_stats16[0] = base;
-      char buf[160];
-      if (slot < 0) snprintf(buf, sizeof buf, "%s matrix, data row %lld: fewer than %d sample columns", kFile[m], row, n_cols);
-      else snprintf(buf, sizeof buf, "%s matrix, data row %lld, sample %lld: not a number", kFile[m], row, slot);
-      return ss_fail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+    {
+      const int32_t rc = rg.check_rows(last_row >= 0 ? last_row + 2 : g);
+      if (rc != MIDAS_SNPS_OK) return rc;
     }
     SS_TRY(hipEventRecord(ev.e[0], st));
     if (dump_freq || dump_depth)
@@ -812,10 +1083,9 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     }
     SS_TRY(hipEventRecord(ev.e[1], st));
     SS_TRY(hipStreamSynchronize(st));
-    SS_TRY(lap(0, 1, 7));
+    SS_TRY(rg.lap(0, 1, 7));
     kept += kept_g;
-    base += g;
-    for (int m = 0; m < 2; ++m) ck[m].at = std::min(ck[m].bytes, ck[m].at + (long long)end_at[m] + 1);
+    rg.advance(g);
     if (last_row >= 0) stop = true;
   }
   if (want_sums) {
@@ -827,12 +1097,281 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
   unsigned long long no_gene = 0;
   SS_TRY(hipMemcpyAsync(&no_gene, d_no_gene, 8, hipMemcpyDeviceToHost, st));
   SS_TRY(hipStreamSynchronize(st));
-  out_stats16[0] = base;
+  out_stats16[0] = rg.base;
   out_stats16[1] = kept;
-  out_stats16[7] = groups;
+  out_stats16[7] = rg.groups;
   out_stats16[8] = (int64_t)no_gene;
   out_stats16[9] = G;
-  out_stats16[10] = chunk_bytes;
+  out_stats16[10] = rg.chunk_bytes;
+  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = ms[k];
+  return MIDAS_SNPS_OK;
+}
+
+namespace {
+
+// what the two strain_tracking.py entry points check and set up alike
+int32_t strains_begin(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes, int64_t n_parse,
+                      int64_t n_call, int32_t n_samples, const int32_t* sample_col, const double* fparams2, const int64_t* iparams8,
+                      int64_t* out_stats16, float* out_ms8, std::vector<int32_t>* col_slot) {
+  if (!ctx || freq_bytes < 0 || depth_bytes < 0 || (freq_bytes > 0 && !freq) || (depth_bytes > 0 && !depth) || n_parse < 0 || n_call < 0 ||
+      n_call > n_parse || n_parse > 0x7FFFFFFFll || n_samples < 1 || !sample_col || !fparams2 || !iparams8 || !out_stats16 || iparams8[2] < 0 ||
+      iparams8[3] < 0 || iparams8[5] < 0)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  int n_cols = 0;
+  for (int s = 0; s < n_samples; ++s) {
+    if (sample_col[s] < 0) return MIDAS_SNPS_ERR_INVALID_ARG;
+    n_cols = std::max(n_cols, sample_col[s] + 1);
+  }
+  ctx->clear_error();
+  ctx->err_read = -1;
+  for (int k = 0; k < 16; ++k) out_stats16[k] = 0;
+  out_stats16[5] = -1;
+  out_stats16[6] = -1;
+  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = 0.f;
+  col_slot->assign((size_t)n_cols, -1);
+  for (int s = 0; s < n_samples; ++s) {
+    if ((*col_slot)[(size_t)sample_col[s]] >= 0) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "a matrix column is selected twice");
+    (*col_slot)[(size_t)sample_col[s]] = s;
+  }
+  return MIDAS_SNPS_OK;
+}
+
+// The reference converts a row's cells and then calls the site, row by row: of a row that cannot be read and a site that
+// cannot be called, the one it meets first is the error, whatever the row groups are (a row with both: the cells come first).
+bool call_error_comes_first(const RowGroups& rg, long long g, unsigned long long err) {
+  if (err == kNoBad) return false;
+  const long long bad_row = rg.first_bad_row(g);
+  return bad_row < 0 || (long long)(err >> 32) < bad_row;
+}
+
+// a site that cannot be called (the reference raises there): its place in stats, the reason in words
+int32_t strains_call_error(midas_snps_ctx* ctx, unsigned long long err, long long base, int64_t* stats) {
+  const long long row = base + (long long)(err >> 32), slot = (long long)((err & 0xFFFFFFFFull) >> 2);
+  const int why = (int)(err & 3u);
+  stats[4] = 2 + why;
+  stats[5] = row;
+  stats[6] = slot;
+  stats[0] = base;
+  char buf[160];
+  if (why == (int)kCallNonFinite) snprintf(buf, sizeof buf, "data row %lld, sample %lld: frequency x depth is not a finite number", row, slot);
+  else snprintf(buf, sizeof buf, "data row %lld, sample %lld: the %s allele is none of A, T, C, G", row, slot, why == (int)kCallMinorLetter ? "minor" : "major");
+  return ss_fail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+}
+
+}  // namespace
+
+extern "C" int32_t midas_sites_id_markers(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                          int64_t n_parse, int64_t n_call, const uint8_t* minor_code, const uint8_t* major_code,
+                                          int32_t n_samples, const int32_t* sample_col, const double* fparams2, const int64_t* iparams8,
+                                          int32_t* out_rows7, int64_t* out_stats16, float* out_ms8) {
+  std::vector<int32_t> col_slot;
+  {
+    const int32_t rc = strains_begin(ctx, freq, freq_bytes, depth, depth_bytes, n_parse, n_call, n_samples, sample_col, fparams2, iparams8,
+                                     out_stats16, out_ms8, &col_slot);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
+  if (n_call > 0 && (!minor_code || !major_code || !out_rows7)) return MIDAS_SNPS_ERR_INVALID_ARG;
+  if (n_parse == 0) return MIDAS_SNPS_OK;
+  const int S = n_samples;
+  const long long capacity = iparams8[4];
+  SS_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const long long per_row = (long long)S * (8 + 8 + 2 * (long long)sizeof(SideCell)) + 4 + 4 + 4 + 1 + 1 + 24 + 28;
+  SsBufs dev;
+  SsEvents ev;
+  float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, call, compact, -, -, download
+  RowGroups rg(ctx, dev, ev, ms, out_stats16);
+  {
+    const int32_t rc = rg.init(freq, freq_bytes, depth, depth_bytes, n_parse, S, col_slot, iparams8[2], iparams8[3], per_row);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
+  const long long G = rg.G;
+  uint8_t *d_minor = nullptr, *d_major = nullptr;
+  uint32_t *d_flag = nullptr, *d_rank = nullptr;
+  int32_t *d_row6 = nullptr, *d_out7 = nullptr;
+  unsigned long long* d_err = nullptr;
+  SS_TRY(dev.get(&d_minor, (size_t)G));
+  SS_TRY(dev.get(&d_major, (size_t)G));
+  SS_TRY(dev.get(&d_flag, (size_t)G * 4));
+  SS_TRY(dev.get(&d_rank, (size_t)G * 4));
+  SS_TRY(dev.get(&d_row6, (size_t)G * 24));
+  SS_TRY(dev.get(&d_out7, (size_t)G * 28));
+  SS_TRY(dev.get(&d_err, 8));
+  long long found = 0;
+  for (;;) {
+    long long g = 0;
+    {
+      const int32_t rc = rg.next(&g);
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
+    if (g == 0) break;
+    const long long base = rg.base, gc = std::max<long long>(0, std::min<long long>(g, n_call - base));
+    long long n = 0;
+    unsigned long long err = kNoBad;
+    if (gc > 0) {
+      SS_TRY(hipMemcpyAsync(d_minor, minor_code + base, (size_t)gc, hipMemcpyHostToDevice, st));
+      SS_TRY(hipMemcpyAsync(d_major, major_code + base, (size_t)gc, hipMemcpyHostToDevice, st));
+      SS_TRY(hipMemsetAsync(d_err, 0xFF, 8, st));
+      SS_TRY(hipEventRecord(ev.e[3], st));
+      MarkP mp;
+      mp.fv = rg.d_fv; mp.dv = rg.d_dv; mp.minor = d_minor; mp.major = d_major; mp.g = gc; mp.stride = G; mp.S = S;
+      mp.min_freq = fparams2[0]; mp.min_reads = (double)iparams8[0]; mp.allele_prev = iparams8[1]; mp.flag = d_flag; mp.row6 = d_row6;
+      mp.err = d_err;
+      hipLaunchKernelGGL(ss_mark_kernel, dim3(nblocks(gc, 256)), dim3(256), 0, st, mp);
+      SS_TRY(hipGetLastError());
+      SS_TRY(hipEventRecord(ev.e[4], st));
+      uint32_t last_flag = 0, last_rank = 0;
+      SS_TRY(hipMemcpyAsync(&last_flag, d_flag + gc - 1, 4, hipMemcpyDeviceToHost, st));
+      SS_TRY(launch_scan_u32(d_flag, d_rank, gc, rg.d_scratch, st));
+      hipLaunchKernelGGL(ss_mark_compact_kernel, dim3(nblocks(gc, 256)), dim3(256), 0, st, d_flag, d_rank, d_row6, gc, base, d_out7);
+      SS_TRY(hipGetLastError());
+      SS_TRY(hipEventRecord(ev.e[5], st));
+      SS_TRY(hipMemcpyAsync(&last_rank, d_rank + gc - 1, 4, hipMemcpyDeviceToHost, st));
+      SS_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, st));
+      SS_TRY(hipStreamSynchronize(st));
+      SS_TRY(rg.lap(3, 4, 3));
+      SS_TRY(rg.lap(4, 5, 4));
+      n = (long long)last_rank + last_flag;
+    }
+    if (call_error_comes_first(rg, g, err)) return strains_call_error(ctx, err, base, out_stats16);
+    {
+      const int32_t rc = rg.check_rows(g);      // (n_parse ends with the last row the reference reads)
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
+    if (n > 0) {
+      if (found + n > capacity) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "the markers do not fit the output capacity");
+      SS_TRY(hipEventRecord(ev.e[0], st));
+      SS_TRY(hipMemcpyAsync(out_rows7 + 7 * found, d_out7, (size_t)n * 28, hipMemcpyDeviceToHost, st));
+      SS_TRY(hipEventRecord(ev.e[1], st));
+      SS_TRY(hipStreamSynchronize(st));
+      SS_TRY(rg.lap(0, 1, 7));
+      found += n;
+    }
+    rg.advance(g);
+  }
+  out_stats16[0] = rg.base;
+  out_stats16[1] = found;
+  out_stats16[7] = rg.groups;
+  out_stats16[9] = G;
+  out_stats16[10] = rg.chunk_bytes;
+  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = ms[k];
+  return MIDAS_SNPS_OK;
+}
+
+extern "C" int32_t midas_sites_track_markers(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                             int64_t n_parse, int64_t n_call, const uint8_t* site_which, int32_t n_samples,
+                                             const int32_t* sample_col, const double* fparams2, const int64_t* iparams8, int64_t* out_both,
+                                             int64_t* out_stats16, float* out_ms8) {
+  std::vector<int32_t> col_slot;
+  {
+    const int32_t rc = strains_begin(ctx, freq, freq_bytes, depth, depth_bytes, n_parse, n_call, n_samples, sample_col, fparams2, iparams8,
+                                     out_stats16, out_ms8, &col_slot);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
+  if (!out_both || (n_call > 0 && !site_which)) return MIDAS_SNPS_ERR_INVALID_ARG;
+  for (int64_t i = 0; i < n_call; ++i)
+    if (site_which[i] > 2) return MIDAS_SNPS_ERR_INVALID_ARG;
+  const int S = n_samples;
+  const size_t n_acc = (size_t)S * (size_t)S;
+  for (size_t k = 0; k < n_acc; ++k) out_both[k] = 0;
+  if (n_parse == 0) return MIDAS_SNPS_OK;
+  SS_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const long long per_row = (long long)S * (8 + 8 + 2 * (long long)sizeof(SideCell)) + 4 + 4 + 4 + 4 + 1 + (S + 7) / 8;
+  SsBufs dev;
+  SsEvents ev;
+  float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, matched sites, bit matrix, pairs, -, download
+  RowGroups rg(ctx, dev, ev, ms, out_stats16);
+  {
+    const int32_t rc = rg.init(freq, freq_bytes, depth, depth_bytes, n_parse, S, col_slot, iparams8[2], iparams8[3], per_row);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
+  const long long G = rg.G, wstride = (G + 63) / 64;
+  uint8_t* d_which = nullptr;
+  uint32_t *d_flag = nullptr, *d_rank = nullptr, *d_list = nullptr;
+  unsigned long long *d_bits = nullptr, *d_both = nullptr, *d_err = nullptr;
+  SS_TRY(dev.get(&d_which, (size_t)G));
+  SS_TRY(dev.get(&d_flag, (size_t)G * 4));
+  SS_TRY(dev.get(&d_rank, (size_t)G * 4));
+  SS_TRY(dev.get(&d_list, (size_t)G * 4));
+  SS_TRY(dev.get(&d_bits, (size_t)S * (size_t)wstride * 8));
+  SS_TRY(dev.get(&d_both, n_acc * 8));
+  SS_TRY(dev.get(&d_err, 8));
+  SS_TRY(hipMemsetAsync(d_both, 0, n_acc * 8, st));
+  const int tiles_side = (S + kPairTile - 1) / kPairTile;
+  const long long n_tiles = (long long)tiles_side * (tiles_side + 1) / 2;
+  const long long pair_blocks = iparams8[5] > 0 ? iparams8[5] : 1024;      // workgroups the pair kernel aims at
+  long long matched = 0, word_pairs = 0, max_runs = 0, max_steps = 0;
+  for (;;) {
+    long long g = 0;
+    {
+      const int32_t rc = rg.next(&g);
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
+    if (g == 0) break;
+    const long long base = rg.base, gc = std::max<long long>(0, std::min<long long>(g, n_call - base));
+    unsigned long long err = kNoBad;
+    if (gc > 0) {
+      SS_TRY(hipMemcpyAsync(d_which, site_which + base, (size_t)gc, hipMemcpyHostToDevice, st));
+      SS_TRY(hipEventRecord(ev.e[3], st));
+      hipLaunchKernelGGL(ss_which_flag_kernel, dim3(nblocks(gc, 256)), dim3(256), 0, st, d_which, gc, d_flag);
+      SS_TRY(hipGetLastError());
+      uint32_t last_flag = 0, last_rank = 0;
+      SS_TRY(hipMemcpyAsync(&last_flag, d_flag + gc - 1, 4, hipMemcpyDeviceToHost, st));
+      SS_TRY(launch_scan_u32(d_flag, d_rank, gc, rg.d_scratch, st));
+      hipLaunchKernelGGL(ss_which_list_kernel, dim3(nblocks(gc, 256)), dim3(256), 0, st, d_which, d_rank, gc, d_list);
+      SS_TRY(hipGetLastError());
+      SS_TRY(hipMemcpyAsync(&last_rank, d_rank + gc - 1, 4, hipMemcpyDeviceToHost, st));
+      SS_TRY(hipEventRecord(ev.e[4], st));
+      SS_TRY(hipStreamSynchronize(st));
+      SS_TRY(rg.lap(3, 4, 3));
+      const long long m = (long long)last_rank + last_flag, n_words = (m + 63) / 64;
+      if (m > 0) {
+        SS_TRY(hipMemsetAsync(d_err, 0xFF, 8, st));
+        SS_TRY(hipEventRecord(ev.e[4], st));
+        hipLaunchKernelGGL(ss_bits_kernel, dim3((unsigned)n_words, (unsigned)((S + 3) / 4)), dim3(256), 0, st, rg.d_fv, rg.d_dv, d_list, m, G, S,
+                           fparams2[0], (double)iparams8[0], d_bits, wstride, d_err);
+        SS_TRY(hipGetLastError());
+        SS_TRY(hipEventRecord(ev.e[5], st));
+        // word runs: enough workgroups to fill the device when the tiles are few, each run whole staging steps
+        long long runs = std::max<long long>(1, std::min<long long>((pair_blocks + n_tiles - 1) / n_tiles, (n_words + kPairRun - 1) / kPairRun));
+        runs = std::min<long long>(runs, 65535);
+        const long long run_words = ((n_words + runs - 1) / runs + kPairRun - 1) / kPairRun * kPairRun;
+        runs = (n_words + run_words - 1) / run_words;
+        hipLaunchKernelGGL(ss_pairs_kernel, dim3((unsigned)n_tiles, (unsigned)runs), dim3(256), 0, st, d_bits, wstride, n_words, run_words, S,
+                           tiles_side, d_both);
+        SS_TRY(hipGetLastError());
+        SS_TRY(hipEventRecord(ev.e[6], st));
+        SS_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, st));
+        SS_TRY(hipStreamSynchronize(st));
+        SS_TRY(rg.lap(4, 5, 4));
+        SS_TRY(rg.lap(5, 6, 5));
+        matched += m;
+        word_pairs += (long long)S * (S + 1) / 2 * n_words;
+        max_runs = std::max(max_runs, runs);
+        max_steps = std::max(max_steps, run_words / kPairRun);
+      }
+    }
+    if (call_error_comes_first(rg, g, err)) return strains_call_error(ctx, err, base, out_stats16);
+    {
+      const int32_t rc = rg.check_rows(g);
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
+    rg.advance(g);
+  }
+  SS_TRY(hipEventRecord(ev.e[0], st));
+  SS_TRY(hipMemcpyAsync(out_both, d_both, n_acc * 8, hipMemcpyDeviceToHost, st));
+  SS_TRY(hipEventRecord(ev.e[1], st));
+  SS_TRY(hipStreamSynchronize(st));
+  SS_TRY(rg.lap(0, 1, 7));
+  out_stats16[0] = rg.base;
+  out_stats16[1] = matched;
+  out_stats16[7] = rg.groups;
+  out_stats16[8] = word_pairs;
+  out_stats16[11] = max_runs;
+  out_stats16[12] = max_steps;
+  out_stats16[9] = G;
+  out_stats16[10] = rg.chunk_bytes;
   if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = ms[k];
   return MIDAS_SNPS_OK;
 }
