@@ -807,6 +807,52 @@ int32_t midas_sites_write_markers(const char* path, const midas_sites_tables* t,
 int32_t midas_sites_write_pairs(const char* path, const midas_sites_tables* t, int32_t n_samples, const int32_t* sample_row,
                                 const int64_t* both, char* err1024);
 
+/* ---- compare_genes.py: gene-content distances between all pairs of samples of one `merge_midas.py genes` directory ----------
+ * midas_genes_matrix_*: one genes_<kind>.txt mapped and left as text.  counts: out4 = sample columns of the header, data rows
+ *   (lines after the header; a last line without '\n' counts), bytes of those rows, bytes of the sample ids.  columns: out4 =
+ *   the header's sample ids back to back (char), their offsets (int64, n + 1), the rows (char), the header's first field
+ *   (char, *out_first_bytes long).  They belong to the handle.
+ * midas_genes_compare: rows [0, n_rows_max) of `text` (the rows after the header, host memory); every row must have n_columns
+ *   sample columns after its gene id, of which the first n_samples are used.  A cell is converted the way pandas' C reader
+ *   converts it under read_table's defaults -- at most 17 digits accumulated in fp64, then ONE fp64 multiply or divide by a
+ *   power of ten -- which is not float(); midas_genes_compare_parse_cell is that converter on the host (*out_plain_int: the
+ *   cell has neither '.' nor an exponent).  A row of another width, or a cell among the used columns that is no finite decimal
+ *   literal, is MIDAS_SNPS_ERR_BAD_LAYOUT with out_stats16[4] = 1 (width) or 2 (cell), [5] the 0-based data row, [6] the
+ *   sample column (-1: width); the earliest in file order is reported, whatever the row groups are.
+ *   MIDAS_GENES_PRESABS: a gene is present where its value > cutoff; out_count [n_samples][n_samples], filled for i <= j: genes
+ *     present in both (the diagonal: in sample i).  Integers held on the device across row groups.
+ *   MIDAS_GENES_COPYNUM: out_both / out_either [n_samples][n_samples], filled for i <= j: the sums of min(a, b) / max(a, b)
+ *     over the rows IN ORDER, one fp64 add per row starting from 0, min = b < a ? b : a and max = b > a ? b : a (the
+ *     diagonal of out_both: the sample's own sum); out_dist: the same sum of (a - b) * (a - b) (MIDAS_GENES_EUCLIDEAN, two
+ *     roundings and the add) or |a - b| (MIDAS_GENES_MANHATTAN); unused under MIDAS_GENES_JACCARD.  The row axis is never split
+ *     between workgroups or reduced in a tree and the sums carry across row groups in device memory: the bits do not depend
+ *     on group_rows or chunk_bytes.
+ *   out_col_float [n_samples]: 1 when some cell of the column has '.' or an exponent.  dump_cells (nullable, tests): the
+ *   converted cells [n_samples][n_rows_max].  iparams4 = group_rows, chunk_bytes (0: from the free device memory), pair_blocks
+ *   (presabs, as midas_sites_track_markers), 0.  out_stats16: [0] rows read, [7] row groups, [8] presabs: (pairs i <= j) x words,
+ *   copynum: (pairs i <= j) x rows, [9] group_rows and [10] chunk_bytes in use, [11] pair tiles.  out_ms8 (nullable): upload +
+ *   index (host clock), index, parse, bit matrix, pairs (popcount or ordered), -, -, download (device events).
+ * midas_genes_compare_write_pairs: sample1, sample2, count1, count2, count_both, count_either, distance for every pair i < j in
+ *   itertools.combinations order, numbers as str() writes them; n_rows = rows read (0: the sums are the integer 0).            */
+#define MIDAS_GENES_PRESABS 0
+#define MIDAS_GENES_COPYNUM 1
+#define MIDAS_GENES_JACCARD 0
+#define MIDAS_GENES_EUCLIDEAN 1
+#define MIDAS_GENES_MANHATTAN 2
+typedef struct midas_genes_matrix midas_genes_matrix;
+int32_t midas_genes_matrix_open(const char* path, midas_genes_matrix** out, char* err1024);
+int32_t midas_genes_matrix_counts(const midas_genes_matrix* m, int64_t* out4);
+int32_t midas_genes_matrix_columns(const midas_genes_matrix* m, const void** out4, int64_t* out_first_bytes);
+void midas_genes_matrix_close(midas_genes_matrix* m);
+int32_t midas_genes_compare_parse_cell(const char* text, int64_t n, double* out, int32_t* out_plain_int);
+int32_t midas_genes_compare(midas_snps_ctx* ctx, const char* text, int64_t text_bytes, int64_t n_rows_max, int32_t n_samples,
+                            int32_t n_columns, int32_t dtype, int32_t distance, double cutoff, const int64_t* iparams4,
+                            int64_t* out_count, double* out_both, double* out_either, double* out_dist, uint8_t* out_col_float,
+                            double* dump_cells, int64_t* out_stats16, float* out_ms8);
+int32_t midas_genes_compare_write_pairs(const char* path, const midas_genes_matrix* m, int32_t n_samples, int32_t dtype, int32_t distance,
+                                        int64_t n_rows, const int64_t* count, const double* both, const double* either, const double* dist,
+                                        char* err1024);
+
 /* ---- the exchange between ranks (comm.cpp): RCCL itself, no process group ------------------------------------------------
  * One process per GPU; the only thing ranks exchange on this path is the per-species summary rows -- the reference's pool
  * workers return (species_id, aln_stats) through a pipe, midas/run/snps.py:225-241, midas/utility.py:81-107 -- plus, on the

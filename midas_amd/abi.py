@@ -355,6 +355,13 @@ def load_library(build_if_missing: bool = True):
         'midas_sites_track_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, i32] + [vp] * 6),
         'midas_sites_write_markers': (i32, [C.c_char_p, vp, i64, vp, C.c_char_p]),
         'midas_sites_write_pairs': (i32, [C.c_char_p, vp, i32, vp, vp, C.c_char_p]),
+        'midas_genes_matrix_open': (i32, [C.c_char_p, C.POINTER(vp), C.c_char_p]),
+        'midas_genes_matrix_counts': (i32, [vp, vp]),
+        'midas_genes_matrix_columns': (i32, [vp, vp, C.POINTER(i64)]),
+        'midas_genes_matrix_close': (None, [vp]),
+        'midas_genes_compare_parse_cell': (i32, [C.c_char_p, i64, C.POINTER(C.c_double), C.POINTER(i32)]),
+        'midas_genes_compare': (i32, [vp, vp, i64, i64, i32, i32, i32, i32, C.c_double] + [vp] * 9),
+        'midas_genes_compare_write_pairs': (i32, [C.c_char_p, vp, i32, i32, i32, i64, vp, vp, vp, vp, C.c_char_p]),
     })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing: fail loudly
@@ -395,6 +402,8 @@ EXPORTED_SYMBOLS = [
     'midas_genes_merge_map_close', 'midas_genes_merge_tables_open', 'midas_genes_merge_tables_rows', 'midas_genes_merge_tables_resolve',
     'midas_genes_merge_tables_columns', 'midas_genes_merge_tables_close', 'midas_genes_merge', 'midas_genes_merge_write_matrix',
     'midas_genes_merge_format_f64',
+    'midas_genes_matrix_open', 'midas_genes_matrix_counts', 'midas_genes_matrix_columns', 'midas_genes_matrix_close',
+    'midas_genes_compare_parse_cell', 'midas_genes_compare', 'midas_genes_compare_write_pairs',
 ]
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
@@ -919,6 +928,58 @@ class SitesTables:
         first = pool[np.minimum(off[:-1], pool.shape[0] - 1)].copy()
         first[ln == 0] = 0
         return first, ln
+
+
+GENES_DTYPES = {'presabs': 0, 'copynum': 1}                            # MIDAS_GENES_PRESABS / _COPYNUM
+GENES_DISTANCES = {'jaccard': 0, 'euclidean': 1, 'manhattan': 2}       # MIDAS_GENES_JACCARD / _EUCLIDEAN / _MANHATTAN
+
+
+class GenesMatrix:
+    """One genes_<kind>.txt of `merge_midas.py genes` (midas_genes_matrix_*): mapped, not parsed.  .first_field and .sample_ids
+    from the header line, .n_rows data rows, .text the rows after the header (uint8 view owned by the handle)."""
+
+    def __init__(self, path: str):
+        lib = load_library()
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        st = lib.midas_genes_matrix_open(path.encode(), C.byref(h), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_matrix_open failed")
+        self._owner = _GenesOwner(lib, h, 'midas_genes_matrix_close')
+        self.path = path
+        counts = (C.c_int64 * 4)()
+        lib.midas_genes_matrix_counts(h, counts)
+        self.n_columns, self.n_rows = int(counts[0]), int(counts[1])
+        ptrs, nfirst = (C.c_void_p * 4)(), C.c_int64(0)
+        lib.midas_genes_matrix_columns(h, ptrs, C.byref(nfirst))
+        col = lambda k, n, dt: np.asarray(_Column(self._owner, ptrs[k] or 0, n, dt))
+        pool = col(0, int(counts[3]), np.uint8).tobytes()
+        off = col(1, self.n_columns + 1, np.int64)
+        self.sample_ids = [pool[int(off[k]):int(off[k + 1])].decode('utf-8', errors='surrogateescape') for k in range(self.n_columns)]
+        self.text = col(2, int(counts[2]), np.uint8)
+        self.first_field = C.string_at(ptrs[3], nfirst.value).decode('utf-8', errors='surrogateescape') if nfirst.value else ''
+
+    def write_pairs(self, path: str, res: dict):
+        """The table of compare_genes.py (midas_genes_compare_write_pairs) from what Context.genes_compare returned."""
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        arr = lambda k, dt: None if res.get(k) is None else np.ascontiguousarray(res[k], dtype=dt)
+        count, both, either, dist = arr('count', np.int64), arr('both', np.float64), arr('either', np.float64), arr('dist', np.float64)
+        err = C.create_string_buffer(1024)
+        st = self._owner._lib.midas_genes_compare_write_pairs(path.encode(), self._owner._h, int(res['n_samples']), GENES_DTYPES[res['dtype']],
+                                                              GENES_DISTANCES[res['distance']], int(res['n_rows']), p(count), p(both),
+                                                              p(either), p(dist), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_compare_write_pairs failed")
+
+
+def pandas_cell(text: bytes):
+    """A matrix cell as pandas' C reader converts it, by the library's host build of the device converter
+    (midas_genes_compare_parse_cell) -> (value, plain_int), or None when it is no finite decimal literal."""
+    lib = load_library()
+    out, plain = C.c_double(0), C.c_int32(0)
+    if lib.midas_genes_compare_parse_cell(text, len(text), C.byref(out), C.byref(plain)) != 0:
+        return None
+    return float(out.value), bool(plain.value)
 
 
 def parse_cell(text: bytes, kind: str):
@@ -1468,6 +1529,42 @@ class Context:
         out, stats = self._strains_call(self._lib.midas_sites_track_markers, freq_text, depth_text, n_call if n_parse is None else n_parse, n_call,
                                         [which], sample_col, float(min_freq), [int(min_reads), 0, group_rows, chunk_bytes, 0, int(pair_blocks)], both)
         out.update(both=both, n_matched=int(stats[1]), word_pairs=int(stats[8]), pair_runs=int(stats[11]), pair_steps=int(stats[12]))
+        return out
+
+    def genes_compare(self, text, n_rows: int, n_samples: int, n_columns: int, dtype: str = 'presabs', distance: str = 'jaccard',
+                      cutoff: float = 0.35, group_rows: int = 0, chunk_bytes: int = 0, pair_blocks: int = 0, dump: bool = False):
+        """midas_genes_compare(): compare_genes.py over the text rows of genes_copynum.txt, the first n_samples of n_columns sample
+        columns, rows [0, n_rows).  -> dict(dtype, distance, n_samples, n_rows read, col_float uint8 [S], groups, steps, tiles,
+        group_rows, chunk_bytes, ms [8]; presabs: count int64 [S, S]; copynum: both, either and (euclidean / manhattan) dist f64
+        [S, S], all filled for i <= j; with dump: cells f64 [S, n_rows]).  A malformed row raises MidasSnpsError with
+        .bad = (1 width | 2 cell, data row, sample column or -1)."""
+        tx = np.ascontiguousarray(text, dtype=np.uint8)
+        S, N = int(n_samples), int(n_rows)
+        copynum = dtype == 'copynum'
+        kd = GENES_DISTANCES[distance]
+        count = None if copynum else np.zeros((S, S), np.int64)
+        both = np.zeros((S, S), np.float64) if copynum else None
+        either = np.zeros((S, S), np.float64) if copynum else None
+        dist = np.zeros((S, S), np.float64) if copynum and kd else None
+        col_float = np.zeros(S, np.uint8)
+        cells = np.zeros((S, max(N, 1)), np.float64) if dump else None
+        ip = np.array([group_rows, chunk_bytes, pair_blocks, 0], np.int64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_genes_compare(self._h, p(tx), tx.shape[0], N, S, int(n_columns), GENES_DTYPES[dtype], kd, float(cutoff), p(ip),
+                                           p(count), p(both), p(either), p(dist), p(col_float), p(cells), p(stats), p(ms))
+        if st != 0:
+            try:
+                self._check(st)
+            except MidasSnpsError as e:
+                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
+                raise
+        n = int(stats[0])
+        out = dict(dtype=dtype, distance=distance, n_samples=S, n_rows=n, col_float=col_float, groups=int(stats[7]), steps=int(stats[8]),
+                   tiles=int(stats[11]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), ms=ms.tolist(), count=count, both=both,
+                   either=either, dist=dist)
+        if dump:
+            out['cells'] = cells[:, :n]
         return out
 
     def batch(self, contigs: ContigTable, reads: ReadsSoA) -> "Batch":

@@ -1,6 +1,6 @@
-"""The command lines of snp_diversity.py, call_consensus.py and strain_tracking.py: the reference's option names, defaults,
-check_args messages and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146,
-scripts/strain_tracking.py:10-137), shared where they agree."""
+"""The command lines of snp_diversity.py, call_consensus.py, strain_tracking.py and compare_genes.py: the reference's option
+names, defaults, check_args messages and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146,
+scripts/strain_tracking.py:10-137, scripts/compare_genes.py:10-65), shared where they agree."""
 import argparse
 import os
 import sys
@@ -228,6 +228,44 @@ def track_markers_arguments(argv=None):
         _exit("Specified input file '%s' does not exist" % args['markers'])
     if args['out'] is None:
         _exit("--out is required")
+    return args
+
+
+def compare_genes_arguments(argv=None):
+    """parse_arguments + init_paths of compare_genes.py: its screen layout (no usage line of argparse's own), option names and
+    defaults; the three genes_*.txt must exist, though only the copy numbers are read.  --group_rows is hidden."""
+    parser = argparse.ArgumentParser(
+        prog='compare_genes.py', formatter_class=argparse.RawTextHelpFormatter, usage=argparse.SUPPRESS,
+        description="Description:\nDistances between the gene content of all pairs of samples of one species, on the device.\n"
+                    "Run `merge_midas.py genes` first.\n\nUsage: compare_genes.py indir [options]\n",
+        epilog="Examples:\n"
+               "1) defaults (presence / absence at copy number 0.35, Jaccard distance):\n"
+               "compare_genes.py OUT/species_1 --out distances.txt\n\n"
+               "2) a quick look at part of the matrix:\n"
+               "compare_genes.py OUT/species_1 --out distances.txt --max_genes 1000 --max_samples 10\n\n"
+               "3) another metric, on the copy numbers themselves:\n"
+               "compare_genes.py OUT/species_1 --out distances.txt --dtype copynum --distance manhattan\n\n"
+               "4) a lenient or a strict call of presence:\n"
+               "compare_genes.py OUT/species_1 --out distances.txt --cutoff 0.10\n"
+               "compare_genes.py OUT/species_1 --out distances.txt --cutoff 0.75\n")
+    parser.add_argument('indir', metavar='PATH', type=str,
+                        help="one species directory written by `merge_midas.py genes` (holds genes_presabs.txt,\n"
+                             "genes_copynum.txt, genes_depth.txt)")
+    parser.add_argument('--out', metavar='PATH', type=str, default='/dev/stdout', help="output file (/dev/stdout)")
+    parser.add_argument('--max_genes', metavar='INT', type=int, help="read this many genes (rows) only (all)")
+    parser.add_argument('--max_samples', metavar='INT', type=int, help="use the first INT samples (columns) only (all)")
+    parser.add_argument('--distance', choices=['jaccard', 'euclidean', 'manhattan'], default='jaccard', help="the distance (jaccard)")
+    parser.add_argument('--dtype', choices=['presabs', 'copynum'], default='presabs',
+                        help="compare presence / absence or the copy numbers (presabs)")
+    parser.add_argument('--cutoff', metavar='FLOAT', type=float, default=0.35,
+                        help="presabs: a gene is present above this copy number (0.35)")
+    parser.add_argument('--group_rows', type=int, default=0, help=argparse.SUPPRESS)
+    args = vars(parser.parse_args(argv))
+    for ext in ['presabs', 'depth', 'copynum']:
+        inpath = '%s/genes_%s.txt' % (args['indir'], ext)
+        if not os.path.isfile(inpath):
+            sys.exit("\nError: Input file does not exist: %s\n" % inpath)
+        args[ext] = inpath
     return args
 
 

@@ -121,3 +121,29 @@ def write_strain_species_dir(path, n_sites, n_samples, seed=0, block=100000, max
                              % (r0 + r + 1, r0 + r + 1, 'ACGT'[al[r, 0]], 'ACGT'[al[r, 1]], 'ACGT'[(al[r, 1] + 1 + al[r, 2] % 3) % 4], n_samples)
                              for r in range(rows)))
     return dict(sample_ids=sample_ids)
+
+
+def write_genes_dir(path, n_genes, n_samples, seed=0, block=100000, palette_size=4093, absent=0.3):
+    """-> dict(sample_ids).  One species directory in the shape `merge_midas.py genes` writes, for compare_genes.py:
+    genes_copynum.txt holds repr() of doubles out of a seeded palette -- 17 significant digits in most, as the merge writes
+    them, a share `absent` of the cells 0.0, a few scaled to e-07 / e+07; genes_presabs.txt and genes_depth.txt, which the
+    command only wants to exist, hold their header line."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    sample_ids = ['sample_%03d' % k for k in range(n_samples)]
+    values = rng.gamma(2.0, 0.6, palette_size)
+    values[rng.random(palette_size) < 0.1] *= 0.25                 # around the cutoffs
+    scale = rng.random(palette_size)
+    values = np.where(scale < 0.03, values * 1e-07, np.where(scale < 0.06, values * 1e+07, values))
+    palette = ['0.0'] + [repr(float(v)) for v in values]
+    header = ('\t'.join(['gene_id'] + sample_ids) + '\n').encode()
+    for kind in ('presabs', 'depth'):
+        with open(os.path.join(path, 'genes_%s.txt' % kind), 'wb') as f:
+            f.write(header)
+    with open(os.path.join(path, 'genes_copynum.txt'), 'wb') as f:
+        f.write(header)
+        for r0 in range(0, n_genes, block):
+            rows = min(block, n_genes - r0)
+            idx = np.where(rng.random((rows, n_samples)) < absent, 0, rng.integers(1, len(palette), (rows, n_samples)))
+            f.write(_matrix_bytes(r0, idx, palette).tobytes())
+    return dict(sample_ids=sample_ids)
