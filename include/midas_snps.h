@@ -413,6 +413,30 @@ int32_t midas_bam_open_slice_device(const char* path, int32_t slice, int32_t n_s
 int32_t midas_bam_load_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
                               int64_t* qual_bytes, int64_t* n_cigar, char* err256);
 int32_t midas_bam_payload_on_device(const midas_bam* bam);
+/* The aligner's SAM TEXT instead of a BAM, parsed and coordinate-sorted on the device of `ctx` (sam_scan.hip).  bowtie2 writes SAM;
+ * the reference pipes it through `samtools view -b | samtools sort` into snps/temp/genomes.bam (midas/run/snps.py:116-120) and opens
+ * that (:186).  This call replaces the three: the file is mapped, its '@' lines are read by the host (@SQ SN: / LN: give the
+ * references in file order; every other header line is skipped), the record lines go up in chunks that end on a complete line
+ * (bounded by the free device memory; MIDAS_SNPS_SAM_CHUNK_BYTES, read at every call, overrides the size -- the decoded bytes do
+ * not depend on it), one thread a line decodes FLAG, RNAME -> refID, POS (0-based; POS 0 -> -1), MAPQ, l_seq, the CIGAR's op
+ * count and the first NM:i: tag (-1: none), a wave a line turns SEQ into 4-bit codes ("=ACMGRSVTWYHKDBN", either case, anything
+ * else 15), QUAL into phred bytes ('*': l_seq bytes of 0xFF) and the CIGAR text into len << 4 | op words, and the records with
+ * a reference (RNAME '*' is dropped, as the BAM decode drops refID < 0) are sorted by (refID, pos + 1) with the library's stable
+ * radix sort -- equal keys keep file order.  The handle then answers midas_bam_n_refs / _ref / _columns / _payload_on_device /
+ * _close exactly as one of midas_bam_load_device does: small columns in host memory, entries 9-11 of midas_bam_columns device
+ * addresses, midas_bam_copy refuses them.  QNAME, RNEXT, PNEXT, TLEN and every tag but NM are not stored.
+ * MIDAS_SNPS_ERR_BAD_LAYOUT, the message naming the 1-based line of the file (the first bad line in file order): an @SQ without
+ * SN: or LN:, a repeated SN:, a record in front of any @SQ; a line of fewer than 11 fields; FLAG / POS / MAPQ that are not
+ * decimal or beyond 65535 / 2^31 - 1 / 255; an RNAME that no @SQ names; a CIGAR op outside MIDNSHP=X, without a length, with
+ * one of 2^28 or more, or more than 65535 ops; a QUAL that is not '*' and has not l_seq characters in '!'..'~'; an NM:i: whose
+ * value is no integer.  MIDAS_SNPS_ERR_UNSUPPORTED: more than 2 * 10^9 records, 4 GiB of QUAL or 2^32 CIGAR ops in one file
+ * (the sorted offsets are rebuilt by the library's 32-bit scan), a line longer than 1 GiB.  No host decoder stands behind it.
+ *   midas_sam_decode_timing   host-clock milliseconds of the context's last midas_sam_load_device: out_ms8 = {map + header, upload,
+ *                             line index, pass 1 (fields), scans, pass 2 (payload), sort + gather, columns down}
+ *                             (measurement aid; no reference counterpart).                                                  */
+int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
+                              int64_t* qual_bytes, int64_t* n_cigar, char* err256);
+int32_t midas_sam_decode_timing(const midas_snps_ctx* ctx, float* out_ms8);
 /* A handle of midas_bam_open_slice / _open_share whose ranges are loaded needs its file no more: the mapping is handed to a
  * thread that unmaps it (a page-table walk of 0.2 s for a 9 GB BAM) while the caller piles the records up; the columns / the
  * resident records stay.  midas_bam_load_ranges* on the handle afterwards is MIDAS_SNPS_ERR_INVALID_ARG.                       */

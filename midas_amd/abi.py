@@ -285,6 +285,8 @@ def load_library(build_if_missing: bool = True):
         'midas_bam_open_slice_device': (i32, [C.c_char_p, i32, i32, vp, C.POINTER(vp), C.c_char_p]),
         'midas_bam_load_device': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_bam_payload_on_device': (i32, [vp]),
+        'midas_sam_load_device': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
+        'midas_sam_decode_timing': (i32, [vp, vp]),
         'midas_bam_release_file': (None, [vp]),
         'midas_bam_load_resident': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_bam_load_ranges_resident': (i32, [vp, vp, i32, vp, vp, C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
@@ -409,6 +411,11 @@ EXPORTED_SYMBOLS = [
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
                  'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_id_markers', 'midas_sites_track_markers',
                  'midas_sites_write_markers', 'midas_sites_write_pairs']
+
+
+# the SAM decode (run_midas.py snps --sam): bound above like the rest, listed by themselves
+SAM_SYMBOLS = ['midas_sam_load_device', 'midas_sam_decode_timing']
+SAM_PHASES = ('map + header', 'upload', 'line index', 'pass 1 (fields)', 'scans', 'pass 2 (payload)', 'sort + gather', 'columns down')
 
 
 def deflate_rows(text: bytes, row_begin, tail_begin) -> bytes:
@@ -641,6 +648,35 @@ def read_bam(path: str, ctx=None, payload_on_device: bool = False, resident: boo
         raise MidasSnpsError(st, err.value.decode())
     refid, reads = _bam_columns(lib, h, int(n.value), int(sb.value), int(qb.value), int(nc.value), owner)
     return names, lens, refid, reads
+
+
+def read_sam(path: str, ctx=None):
+    """Decode the aligner's SAM text on the device of `ctx` (midas_sam_load_device) -> (ref_names, ref_lengths, refid[int32],
+    ReadsSoA), the tuple read_bam(..., payload_on_device=True) returns: the records with a reference, coordinate-sorted there
+    (equal keys in file order), the small columns as views of the decoder's host buffers, SEQ / QUAL / CIGAR as device
+    addresses (`device`).  There is no host decoder: without a device context this raises ERR_INVALID_ARG."""
+    if ctx is None or not getattr(ctx, 'inflates', False):
+        raise MidasSnpsError(ERR_INVALID_ARG, "read_sam needs a device context (the SAM text is parsed and sorted on the GPU)")
+    lib = load_library()
+    h = C.c_void_p()
+    err = C.create_string_buffer(256)
+    n, sb, qb, nc = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+    st = lib.midas_sam_load_device(path.encode(), ctx._h, C.byref(h), C.byref(n), C.byref(sb), C.byref(qb), C.byref(nc), err)
+    if st != 0:
+        raise MidasSnpsError(st, err.value.decode())
+    owner = _BamOwner(lib, h)
+    names, lens = _bam_refs(lib, h)
+    refid, reads = _bam_columns(lib, h, int(n.value), int(sb.value), int(qb.value), int(nc.value), owner, on_device=True)
+    return names, lens, refid, reads
+
+
+def sam_decode_timing(ctx) -> dict:
+    """Host-clock milliseconds of the phases of the context's last read_sam (midas_sam_decode_timing), by name."""
+    ms = (C.c_float * 8)()
+    st = load_library().midas_sam_decode_timing(ctx._h, ms)
+    if st != 0:
+        raise MidasSnpsError(st, "midas_sam_decode_timing failed")
+    return dict(zip(SAM_PHASES, (float(x) for x in ms)))
 
 
 def _bam_refs(lib, h):

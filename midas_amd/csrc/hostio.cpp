@@ -1229,6 +1229,20 @@ void midas::bam_set_device_payload(midas_bam* b, void* seq4, void* qual, void* c
   std::vector<uint64_t>().swap(b->rec_off);
 }
 
+midas_bam* midas::bam_new_columns_handle(const char* path, const std::vector<std::string>& ref_names, const std::vector<int64_t>& ref_lens) {
+  midas_bam* b = new (std::nothrow) midas_bam();
+  if (!b) return nullptr;
+  b->path = path;
+  b->ref_names = ref_names;
+  b->ref_lens = ref_lens;
+  return b;
+}
+void midas::bam_columns_ready(midas_bam* b, int64_t n_records) {
+  b->n_records = (size_t)n_records;
+  b->loaded = true;
+  b->payload_on_device = true;
+}
+
 // The BAM header out of the first `n` inflated bytes: 0 parsed (b->ref_names / ref_lens / rec_begin set), 1 more bytes
 // needed, -1 not a BAM.
 static int parse_bam_header(const uint8_t* d, size_t n, midas_bam* b) {

@@ -1,6 +1,8 @@
 #pragma once
 #include "../../include/midas_snps.h"
 #include <cstddef>
+#include <string>
+#include <vector>
 
 namespace midas {
 
@@ -122,6 +124,12 @@ int32_t bam_open_share(const char* path, int32_t slice, int32_t n_slices, int64_
 int32_t bam_load_ranges_on_device(midas_bam* bam, const DeviceDecoder* dec, int32_t n_ranges, const int64_t* range_begin,
                                   const int64_t* range_end, int64_t* n_reads, int64_t* seq_bytes, int64_t* qual_bytes,
                                   int64_t* n_cigar, char* err256, int payload = 1);
+
+// midas_sam_load_device (sam_scan.hip): a handle over columns that did not come out of a BAM -- the references of the SAM header,
+// then bam_alloc_host_columns for the small columns, bam_set_device_payload for the three on the device, and bam_columns_ready:
+// from there on the handle answers like one of midas_bam_load_device.  nullptr: out of memory.
+midas_bam* bam_new_columns_handle(const char* path, const std::vector<std::string>& ref_names, const std::vector<int64_t>& ref_lens);
+void bam_columns_ready(midas_bam* b, int64_t n_records);
 
 // Members whose DEFLATE streams exist already (the device's row coder): frame them (this library's gzip header with the
 // member's size and row count, CRC-32, ISIZE) and write them in order behind the header line's member.

@@ -302,8 +302,16 @@ def build_genome_db(args, species):
 
 def genome_align(args):
     """bowtie2 (no unaligned reads) | samtools view -b | samtools sort -> snps/temp/genomes.bam, with the same
-    switches the reference passes (midas/run/snps.py:97-128)."""
-    if not args.get('bowtie2') or not args.get('samtools'):
+    switches the reference passes (midas/run/snps.py:97-128).  args['sam']: bowtie2 alone, the same switches plus
+    -S snps/temp/genomes.sam -- the pileup parses and sorts the text on the device (midas_sam_load_device)."""
+    if args.get('sam'):
+        if not args.get('bowtie2'):
+            sys.exit("\nError: bowtie2 not found on PATH (needed for --align --sam; the aligner is not part of this build)\n")
+        # --pileup prefers genomes.bam: an older one would be piled up in place of the SAM written now
+        stale = os.path.join(args['outdir'], 'snps', 'temp', 'genomes.bam')
+        if os.path.isfile(stale):
+            sys.exit("\nError: %s exists and --pileup reads it in preference to genomes.sam: remove it, or align without --sam\n" % stale)
+    elif not args.get('bowtie2') or not args.get('samtools'):
         sys.exit("\nError: bowtie2 / samtools not found on PATH (needed for --align; the aligner is not part of this build)\n")
     temp = os.path.join(args['outdir'], 'snps', 'temp')
     bt2 = [args['bowtie2'], '--no-unal', '-x', os.path.join(temp, 'genomes')]
@@ -319,6 +327,10 @@ def genome_align(args):
         bt2 += ['--interleaved', args['m1']]
     else:
         bt2 += ['-U', args['m1']]
+    if args.get('sam'):
+        _shell(args, [bt2 + ['-S', os.path.join(temp, 'genomes.sam')]])
+        print("  finished aligning")
+        return
     view = [args['samtools'], 'view', '-b', '-', '--threads', args['threads']]
     sort = [args['samtools'], 'sort', '-', '--threads', args['threads'], '-o', os.path.join(temp, 'genomes.bam')]
     _shell(args, [bt2, view, sort])
@@ -331,9 +343,23 @@ def index_bam(args):
     host has nothing to do; the step is kept so that logs and callers look the same."""
     start = time()
     print("\nIndexing bamfile")
-    args['log'].write("\nIndexing bamfile\ncommand: (none) per-tile read index is built on the GPU by index_reads_kernel\n")
+    if _alignment_path(args)[1]:
+        args['log'].write("\nIndexing bamfile\ncommand: (none) genomes.sam is parsed and coordinate-sorted on the GPU (the library's radix sort); "
+                          "per-tile read index is built on the GPU by index_reads_kernel\n")
+    else:
+        args['log'].write("\nIndexing bamfile\ncommand: (none) per-tile read index is built on the GPU by index_reads_kernel\n")
     print("  %s minutes" % round((time() - start) / 60, 2))
     print("  %s Gb maximum memory" % utility.max_mem_usage())
+
+
+def _alignment_path(args):
+    """(path, is_sam): snps/temp/genomes.bam when it exists -- or when nothing does: the messages about a missing alignment name
+    it -- else snps/temp/genomes.sam (--align --sam, or any aligner's SAM put there)."""
+    bampath = '%s/snps/temp/genomes.bam' % args['outdir']
+    sampath = '%s/snps/temp/genomes.sam' % args['outdir']
+    if not os.path.isfile(bampath) and os.path.isfile(sampath):
+        return sampath, True
+    return bampath, False
 
 
 _ERR_TEXT = {
@@ -688,11 +714,12 @@ def _remove_stale_parts(args):
 
 def species_pileup(args, species_id, contigs):
     """midas/run/snps.py:164-216 for ONE species on GPU 0: writes <species>.snps.gz, returns (species_id, aln_stats)."""
-    bampath = '%s/snps/temp/genomes.bam' % args['outdir']
+    bampath, is_sam = _alignment_path(args)
     order, span = _whole(_species_contig_order([species_id], contigs), contigs)
     try:
         with abi.Context(int(os.environ.get("LOCAL_RANK", "0"))) as ctx:
-            decoded = abi.read_bam(bampath, ctx if _inflate_on_device(args, ctx, bampath, 1) else None)
+            decoded = abi.read_sam(bampath, ctx) if is_sam else \
+                abi.read_bam(bampath, ctx if _inflate_on_device(args, ctx, bampath, 1) else None)
             stats = _pileup_contigs(args, [species_id], order[species_id], order, {}, decoded, ctx, span, contigs)
     except abi.MidasSnpsError as e:
         _exit_on(e)
@@ -921,10 +948,15 @@ def _count_alleles(args, species, contigs, ctx):
         print("\nCounting alleles")
         args['log'].write("\nCounting alleles\n")
 
-    bampath = '%s/snps/temp/genomes.bam' % args['outdir']
+    bampath, is_sam = _alignment_path(args)
     if rank == 0:
         _remove_stale_parts(args)       # (before the first point every rank waits at)
-    inflater = ctx if _inflate_on_device(args, ctx, bampath, ws) else None
+    # only a SAM, several ranks: the rank-local plans below deal the BAM's BGZF blocks; text has none
+    # (every rank sees the same two files, so every rank takes this branch or none does: a BAM run's collectives are as they were)
+    if is_sam and ws > 1:
+        dist.agree_or_exit("\nError: %d-rank runs need snps/temp/genomes.bam (the ranks' shares are runs of BGZF blocks); only "
+                           "genomes.sam was found: run one rank, or sort it into a BAM\n" % ws)
+    inflater = ctx if not is_sam and _inflate_on_device(args, ctx, bampath, ws) else None
     # N ranks, ONE pass where the contigs are short beside a rank's share (the usual metagenome): contiguous shares of whole
     # contigs, every block inflated once, by the rank that piles its records up (_one_pass_shares).  A contig longer than the
     # split length wants to be cut into pieces, which needs the slices' walk: the two-pass plan below.
@@ -991,7 +1023,13 @@ def _count_alleles(args, species, contigs, ctx):
                 t_in = time()
                 opened = args.pop('_bam_opener').wait() if args.get('_bam_opener') is not None else None
                 t_in = _lap("  BAM opened: its block table waited for", t_in)
-                if opened is not None and inflater is not None and ws == 1 and 0 <= opened.first < opened.total:
+                if is_sam:
+                    if opened is not None:
+                        opened.close()
+                    # (text from the aligner: parsed and coordinate-sorted on the device, SEQ / QUAL / CIGAR stay there)
+                    decoded = abi.read_sam(bampath, ctx)
+                    _lap("  SAM decoded and sorted on the device", t_in)
+                elif opened is not None and inflater is not None and ws == 1 and 0 <= opened.first < opened.total:
                     # (the file was mapped and its block table walked while the device context came up)
                     refid, rr = opened.load_ranges([(opened.first, opened.total)], inflater, resident=True)
                     t_in = _lap("  decode on the device (resident)", t_in)
@@ -1209,7 +1247,7 @@ def run_pipeline(args):
             contigs.start()
         if rank == 0:
             index_bam(args)
-        if ws == 1 and args.get('device_inflate', 'auto') not in (False, 'off') and '_bam_opener' not in args:
+        if ws == 1 and args.get('device_inflate', 'auto') not in (False, 'off') and '_bam_opener' not in args and not _alignment_path(args)[1]:
             args['_bam_opener'] = BamInBackground('%s/snps/temp/genomes.bam' % args['outdir'])
         t_lap = _lap("species, genome reader started, index_bam", t_lap)
         pysam_pileup(args, species, contigs)

@@ -31,6 +31,8 @@ OPTION_GROUPS = [
         (['--build_db'], dict(action='store_true', help="concatenate the representative genomes and index them with bowtie2-build")),
         (['--align'], dict(action='store_true', help="map the reads with bowtie2 | samtools view | samtools sort")),
         (['--pileup'], dict(action='store_true', dest='call', help="count A/C/G/T per genomic site (this is the GPU stage)")),
+        (['--sam'], dict(action='store_true', help="with --align, keep bowtie2's SAM as snps/temp/genomes.sam and skip samtools;\n"
+                                                   "--pileup reads it when there is no genomes.bam (parsed and sorted on the GPU)")),
     ]),
     ("Which species (for --build_db)", [
         (['-d'], dict(dest='db', default=os.environ.get('MIDAS_DB'), help="MIDAS reference database (default: $MIDAS_DB)")),
@@ -199,6 +201,8 @@ def check_arguments(program, args):
         die("Could not find species abundance profile: %s\n"
             "--species_topn / --species_cov need the output of `run_midas.py species`; use --species_id otherwise" % profile)
     have_fa, have_bam = (os.path.isfile(os.path.join(temp, f)) for f in (fa_name, bam_name))
+    if program == 'snps' and not have_bam:       # (--sam: the aligner's text stands in for the BAM)
+        have_bam = os.path.isfile(os.path.join(temp, 'genomes.sam'))
     if args['align'] and not args['build_db'] and not have_fa:
         die("You've specified --align, but no database has been built\nTry running with --build_db")
     if args[last] and not args['align'] and not have_bam:
@@ -242,6 +246,8 @@ def print_arguments(program, args):
         shown += [('reads', ' '.join(x for x in (args['m1'], args['m2']) if x) + (' (interleaved)' if args['interleaved'] else '')),
                   ('bowtie2', '--%s%s' % (args['speed'], '-local' if args['mode'] == 'local' else '')),
                   ('max reads', args['max_reads'] or 'all'), ('threads', args['threads'])]
+        if args.get('sam'):
+            shown += [('alignments', 'snps/temp/genomes.sam (bowtie2 -S; no samtools)')]
     if last[1]:
         shown += [(k, args[k]) for k in ('mapid', 'mapq', 'baseq', 'readq', 'aln_cov', 'trim') if k in args]
     text = "=== run_midas.py %s (MI355X) ===\n" % program + ''.join("%-18s %s\n" % (k + ':', v) for k, v in shown) + "===\n"
@@ -263,6 +269,8 @@ summary.txt                   per species: genome_length, covered_bases, fractio
                               aligned_reads, mapped_reads
 log.txt                       parameters and external commands of this run
 temp/                         genomes.fa, bowtie2 index, genomes.bam (deleted by --remove_temp)
+                              with --sam: genomes.sam, bowtie2's own output, in the BAM's place; --pileup parses and
+                              coordinate-sorts it on the GPU when there is no genomes.bam
 
 Reads counted: identity >= --mapid, mean quality >= --readq, mapping quality >= --mapq, aligned fraction
 >= --aln_cov; bases counted: A/C/G/T with quality >= --baseq.  mean_coverage is over covered sites only.
