@@ -1,9 +1,13 @@
+// ROUND 8 EXPERIMENT, NOT SHIPPED (profiles/r08_direct_issue.txt section 4): the byte-mask rows of a partial pass fetched for ALL
+// groups in front of the pass's first ds_add (MIDAS_DIRECT_ROWS_AHEAD), so that no row waits for the atomics of the group before it.
+// Bit-exact; -0.2 .. -0.5 % of the step on configs[2] on top of the 38-base lanes, and the masked copy of a lane's ten words costs
+// eight VGPRs: the 38-base instantiation reaches 128 and spills two.  The rest of the file is the shipped kernel of that round.
 // gfx950 (CDNA4) pileup kernel of the MIDAS SNP path that reads the reads in input order: per read ONE 16-byte record (pos,
 // l_seq, n_cigar, NM, mapq, payload offset -- layout.h DirectRec) and its payload -- BAM's CIGAR, the sum of its qualities and
 // ONE byte a base (layout.h dense_byte) -- one run per read: nothing sorted or decided beforehand, ONE visit per read.
 // Integer counting: no MFMA.
 //
-// Reference semantics implemented here (citations into /root/reference):
+// Reference semantics implemented here (citations into the reference project):
 //   keep_read                       midas/run/snps.py:141-162  (query_alignment_sequence :145, np.mean(query_qualities) :151)
 //   count_coverage call site        midas/run/snps.py:194-199  ([EXT] pysam: get_aligned_pairs(matches_only), qual >= quality_threshold,
 //                                   only 'A','C','G','T' counted)
@@ -18,9 +22,8 @@
 // can touch the tile -- the input is position-sorted, so that is a contiguous run of the read arrays.  It is dealt to the
 // workgroup's waves as wave-iterations of floor(64 / lanes per read) reads.
 //
-// Lane mapping.  A lane owns LB (30, 32 or 38: direct_lane_bases below) consecutive bases of a read's STORED query: two 16-byte
-// loads of base bytes, and an 8-byte one for 38.  A read of l_seq bases takes ceil(l_seq / LB) adjacent lanes (4 for 150 bp, 5
-// for 151).  Loads are issued two iterations (the read's record: one dwordx4) and one iteration (bases + the first four
+// Lane mapping.  A lane owns LB (30, 32 or 38: direct_lane_bases below) consecutive bases of a read's STORED query: two 16-byte loads of
+// base bytes, and an 8-byte one for 38.  A read of l_seq bases takes ceil(l_seq / LB) adjacent lanes (4 for 150 bp, 5 for 151).  Loads are issued two iterations (the read's record: one dwordx4) and one iteration (bases + the first four
 // CIGAR ops + the quality sum: three dwordx4 and a dword off ONE scalar base per wave-iteration -- the payload of the
 // iteration's first read -- plus a 32-bit lane offset) ahead of their use; none of them sits in a branch.
 //
@@ -151,6 +154,10 @@ struct Stream { int rb, n0, total; };
 #endif
 constexpr int kDirectBlock = MIDAS_DIRECT_BLOCK;
 static_assert(kDirectBlock % 64 == 0 && kDirectBlock >= 128 && kDirectBlock <= 1024, "whole wavefronts");
+// (developer A/B: -DMIDAS_DIRECT_ROWS_AHEAD=1 fetches the byte-mask rows of a partial pass ahead of its atomics)
+#ifndef MIDAS_DIRECT_ROWS_AHEAD
+#define MIDAS_DIRECT_ROWS_AHEAD 1
+#endif
 constexpr int kDirectWavesPerSimd = (kWorkgroupsPerCU * kDirectBlock / 64 + 3) / 4;      // four workgroups per CU
 
 
@@ -258,6 +265,9 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
 
   // The lanes `go` tally bases [lo, hi) of their LB, the first of the lane at tile-relative site loc0, group by group of
   // eight.  Partial lanes zero the bytes outside [lo, hi) (a zero byte never counts): two rows of the byte-mask table (LDS).
+  // The rows of ALL groups are fetched in front of the pass's first ds_add: LDS answers in order, so a row fetched between
+  // two groups would wait for the eight atomics in front of it (and the compiler, which cannot see them inside the asm
+  // block, waits for lgkmcnt(0)).
   // (sparse: a pass with few lanes, e.g. the one lane of a read that holds its indel -- a group of eight bases none of the
   // wave's lanes has a base in is skipped)
   auto tally_range = [&](bool go, int lo, int hi, int loc0, const uint32_t (&bv)[NW], auto sparse_tag) {
@@ -272,9 +282,27 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     if (!go) return;
     const uint32_t* const row_hi = s_kb + NW * (hi > KROWS - 1 ? KROWS - 1 : hi);      // bytes [lo, hi): row hi less row lo
     const uint32_t* const row_lo = s_kb + NW * (lo < 0 ? 0 : lo);
+#if MIDAS_DIRECT_ROWS_AHEAD
+    uint32_t xv[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) xv[w] = bv[w];
+    if (masked) {
+#pragma unroll
+      for (int S = 0; S < NG; ++S) {
+        if (SPARSE && gmask[S] == 0ull) continue;
+        const uint2 kh = *reinterpret_cast<const uint2*>(row_hi + 2 * S);
+        const uint2 kl = *reinterpret_cast<const uint2*>(row_lo + 2 * S);
+        xv[2 * S] &= kh.x & ~kl.x;
+        xv[2 * S + 1] &= kh.y & ~kl.y;
+      }
+    }
+#endif
     auto group = [&](auto sidx, auto nbases) {
       constexpr int S = decltype(sidx)::value;
       if (SPARSE && gmask[S] == 0ull) return;
+#if MIDAS_DIRECT_ROWS_AHEAD
+      const uint32_t x0 = xv[2 * S], x1 = xv[2 * S + 1];
+#else
       uint32_t x0 = bv[2 * S], x1 = bv[2 * S + 1];
       if (masked) {
         const uint2 kh = *reinterpret_cast<const uint2*>(row_hi + 2 * S);
@@ -282,6 +310,7 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         x0 &= kh.x & ~kl.x;
         x1 &= kh.y & ~kl.y;
       }
+#endif
       tally_group<128 * S, decltype(nbases)::value>(x0, x1, thr, abase, one);
     };
     using std::integral_constant;

@@ -392,7 +392,7 @@ hipError_t launch_direct_layout_fill(const DirectLayoutParams& p, hipStream_t s)
 hipError_t launch_direct_ranges(const DirectIndexParams& p, hipStream_t s);      // every pass: the tile ranges, from the positions
 hipError_t launch_direct_outliers(const DirectOutlier* list, uint32_t n, uint32_t* tbegin, hipStream_t s);   // every pass behind it, when the batch has outliers
 hipError_t launch_pileup_direct(const DirectParams& p, int lane_bases, hipStream_t s);
-int direct_lane_bases(int32_t max_l_seq);
+int direct_lane_bases(int32_t max_l_seq);      // 30, 32 or 38: the bases a lane of the direct kernel owns, from the batch's longest read
 int direct_index_blocks(int64_t n_reads);
 
 hipError_t launch_index_reads(const IndexParams& p, hipStream_t stream);

@@ -132,7 +132,7 @@ struct midas_snps_batch {
   unsigned long long* d_probe = nullptr;   // developer builds only (MIDAS_SNPS_DEBUG_BITS & 256)
   int64_t direct_general = 0;   // reads the pileup kernel walks op by op (facts pass)
   int32_t direct_reach = 1;     // longest reference span of a read: what a tile's range must reach back over
-  int32_t direct_lane_bases = 30, direct_lanes_per_read = 1;
+  int32_t direct_lane_bases = 30, direct_lanes_per_read = 1;      // (pileup_direct.hip direct_lane_bases: 30, 32 or 38)
   int64_t direct_stream_reads = 0;   // sum over tiles of the positions their streams hold (>= n_reads: straddlers twice)
   int64_t direct_max_tile_reads = 0;
   int64_t direct_run_count = 0;
