@@ -239,13 +239,14 @@ def test_short_reads(hip_ctx, thr_default, read_len, var_len):
 
 @pytest.mark.parametrize("read_len", [32, 64, 96, 125, 128, 151, 160, 250])
 def test_read_lengths_on_both_sides_of_the_lane_size(hip_ctx, thr_default, read_len):
-    """A batch packs 31 bases per lane, or 32 where that saves a lane per read (32, 64, 96, 125, 128, 160 here): both
-    layouts, reads straddling tiles, indels and clips included."""
+    """The packed path packs 31 bases per lane, or 32 where that saves a lane per read (32, 64, 96, 125, 128, 160 here); the
+    direct path takes 30, 32 where that saves a lane over 30, or 38 where that saves one over both (97 .. 114 and 129 .. 150
+    bases: none of these lengths, all of which take 32).  Both layouts, reads straddling tiles, indels and clips included."""
     contigs, reads = synth.make_dataset(n_species=2, contigs_per_species=2, contig_len=9000, n_reads=5000,
                                         read_len=read_len, seed=47 + read_len, var_len=False)
     _assert_same(hip_ctx, thr_default, contigs, reads)
     b = hip_ctx.batch(contigs, reads)
-    # packed path: 31 bases per lane, or 32 where that saves a lane; direct path: 30, or 32 where that saves a lane
+    # packed path: 31 bases per lane, or 32 where that saves a lane; direct path: 30, 32 or 38 (direct_lane_bases), 32 at every length here
     b.select_path(abi.PATH_PACKED)
     assert b.info().lanes_per_read == {32: 1, 64: 2, 96: 3, 125: 4, 128: 4, 151: 5, 160: 5, 250: 9}[read_len]
     b.select_path(abi.PATH_DIRECT)

@@ -18,15 +18,6 @@ CHUNK = 4 * TILE
 BORDERS = (37, 38, 39, 75, 76, 77, 113, 114, 115)      # query offsets on both sides of the lanes' borders
 
 
-def _lane_shape(max_len):
-    """(lane_bases, lanes_per_read) of the direct path for a batch's longest read: the rule of direct_lane_bases."""
-    lanes = lambda lb: (max_len + lb - 1) // lb
-    lb = 32 if lanes(32) < lanes(30) else 30
-    if lb == 30 and 96 < max_len <= 160 and lanes(38) < lanes(32):
-        lb = 38
-    return lb, lanes(lb)
-
-
 def _same_on_both_paths(ctx, thr, contigs, reads, max_len, runs=1):
     st, er, oc, oa, os_ = c_oracle.pileup(thr, contigs, reads)
     assert st == 0, "oracle refused the input (%d at read %d)" % (st, er)
@@ -34,7 +25,7 @@ def _same_on_both_paths(ctx, thr, contigs, reads, max_len, runs=1):
     try:
         b.select_path(abi.PATH_DIRECT)
         info = b.info()
-        assert (info.lane_bases, info.lanes_per_read) == _lane_shape(max_len)
+        assert (info.lane_bases, info.lanes_per_read) == H.direct_lane_shape(max_len)
         for _ in range(runs):
             b.run(thr)
             counts, allele, stats = b.fetch()
