@@ -102,7 +102,8 @@ typedef struct midas_snps_reads {
   const int64_t* cigar_off;
   const uint8_t* seq4;        /* these three: host memory, or memory of the context's device (midas_bam_load_device leaves  */
   const uint8_t* qual;        /* them there) -- all three alike; midas_snps_batch_create / midas_snps_pileup copy either way;     */
-  const uint32_t* cigar;      /* the host-only entry points (midas_snps_write_*, midas_genes_*) take host memory only                 */
+  const uint32_t* cigar;      /* the host-only entry points (midas_snps_write_*, midas_genes_count / _terms) take host memory only;   */
+                              /* midas_genes_count_device takes qual / cigar on the device                                            */
 } midas_snps_reads;
 
 /* Contig table: what initialize_contigs() builds (midas/run/snps.py:55-67), flattened.
@@ -437,6 +438,17 @@ int32_t midas_bam_payload_on_device(const midas_bam* bam);
 int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
                               int64_t* qual_bytes, int64_t* n_cigar, char* err256);
 int32_t midas_sam_decode_timing(const midas_snps_ctx* ctx, float* out_ms8);
+/* The same decode with the order of the records chosen by the caller.  MIDAS_SAM_ORDER_COORDINATE: midas_sam_load_device, to the
+ * byte.  MIDAS_SAM_ORDER_FILE: the records that have a reference in the order of their lines -- what `samtools view -b` of the
+ * aligner's output holds, and the order midas_genes_count's fp64 sums follow (run_midas.py genes --sam).  Nothing is sorted and
+ * nothing is gathered: the columns the chunk loop accumulated are the result (64 zero bytes behind each payload column, as in
+ * the sorted form), so the limits of 4 GiB of QUAL / 2^32 CIGAR ops do not apply and slot "sort + gather" of
+ * midas_sam_decode_timing stays 0.  Every field rule, message and status is midas_sam_load_device's; another `order` is
+ * MIDAS_SNPS_ERR_INVALID_ARG.                                                                                                 */
+#define MIDAS_SAM_ORDER_COORDINATE 0
+#define MIDAS_SAM_ORDER_FILE 1
+int32_t midas_sam_load_device_order(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam** out, int64_t* n_reads,
+                                    int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar, char* err256);
 /* A handle of midas_bam_open_slice / _open_share whose ranges are loaded needs its file no more: the mapping is handed to a
  * thread that unmaps it (a page-table walk of 0.2 s for a 9 GB BAM) while the caller piles the records up; the columns / the
  * resident records stay.  midas_bam_load_ranges* on the handle afterwards is MIDAS_SNPS_ERR_INVALID_ARG.                       */
@@ -664,6 +676,23 @@ int32_t midas_merge_write_info(const char* path, const char* header_line, int64_
 int32_t midas_genes_count(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const midas_snps_reads* reads,
                           const int32_t* ref_id, int64_t n_genes, const int64_t* gene_length, int64_t* out_aligned,
                           int64_t* out_mapped, double* out_depth, float* out_kernel_ms);
+
+/* midas_genes_count over reads whose QUAL and CIGAR columns lie on the context's DEVICE (reads->qual / ->cigar are device
+ * addresses, as midas_snps_batch_create accepts them: a handle of midas_sam_load_device_order(MIDAS_SAM_ORDER_FILE), of
+ * midas_bam_load_device or of midas_bam_load_ranges_device; reads->seq4 is not looked at).  The per-read pass over the
+ * quality bytes and the CIGAR ends that midas_genes_count runs on the host's cores is a kernel here (genes_facts_kernel,
+ * sixteen lanes a read); the small columns and ref_id are host memory and go up once (29 bytes a read).  reads->qual_off[n] /
+ * ->cigar_off[n] are taken for the sizes of the two columns: nothing outside [qual, qual + qual_off[n]) and [cigar, cigar +
+ * cigar_off[n]) is read, and a read whose offsets point outside them is MIDAS_SNPS_ERR_BAD_LAYOUT.  Everything behind the
+ * records (filter, stable sort by gene, ordered sums) is shared with midas_genes_count:
+ *   midas_genes_count_device(reads) == midas_genes_count(the same reads in host memory)
+ * in every count, every depth bit for bit, the status and midas_snps_last_error_read (tests/test_gpu_genes_sam.py).
+ *   midas_genes_count_timing   device milliseconds of the context's last midas_genes_count_device: out_ms2 = {facts kernel,
+ *                              filter + sort + sums} (measurement aid; no reference counterpart).                         */
+int32_t midas_genes_count_device(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const midas_snps_reads* reads,
+                                 const int32_t* ref_id, int64_t n_genes, const int64_t* gene_length, int64_t* out_aligned,
+                                 int64_t* out_mapped, double* out_depth, float* out_kernel_ms);
+int32_t midas_genes_count_timing(const midas_snps_ctx* ctx, float* out_ms2);
 
 /* The two halves of midas_genes_count, for N ranks below the species (midas_amd/run/genes.py): a gene's running fp64 sum has
  * to be formed in BAM order on ONE rank, so every rank turns ITS slice of the unsorted BAM into terms, the (gene, term) pairs

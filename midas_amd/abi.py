@@ -287,6 +287,7 @@ def load_library(build_if_missing: bool = True):
         'midas_bam_payload_on_device': (i32, [vp]),
         'midas_sam_load_device': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_sam_decode_timing': (i32, [vp, vp]),
+        'midas_sam_load_device_order': (i32, [C.c_char_p, vp, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_bam_release_file': (None, [vp]),
         'midas_bam_load_resident': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_bam_load_ranges_resident': (i32, [vp, vp, i32, vp, vp, C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
@@ -323,6 +324,8 @@ def load_library(build_if_missing: bool = True):
         'midas_snps_table_copy': (i32, [vp, vp, vp, vp]),
         'midas_genes_count': (i32, [vp, C.POINTER(Thresholds), C.POINTER(_Reads), vp, i64, vp, vp, vp, vp, C.POINTER(C.c_float)]),
         'midas_genes_terms': (i32, [vp, C.POINTER(Thresholds), C.POINTER(_Reads), vp, i64, vp, vp, C.POINTER(C.c_float)]),
+        'midas_genes_count_device': (i32, [vp, C.POINTER(Thresholds), C.POINTER(_Reads), vp, i64, vp, vp, vp, vp, C.POINTER(C.c_float)]),
+        'midas_genes_count_timing': (i32, [vp, vp]),
         'midas_genes_sum': (i32, [vp, i64, vp, vp, i64, vp, vp, vp, C.POINTER(C.c_float)]),
         'midas_merge_sites': (i32, [vp, C.POINTER(MergeParams), i32, i64, C.POINTER(vp), vp] + [vp] * 5 + [C.POINTER(C.c_float)]),
         'midas_bam_open_share': (i32, [C.c_char_p, i32, i32, i64, C.POINTER(vp), vp, C.c_char_p]),
@@ -397,6 +400,7 @@ EXPORTED_SYMBOLS = [
     'midas_fasta_load', 'midas_fasta_n_records', 'midas_fasta_columns', 'midas_fasta_close',
     'midas_snps_table_open', 'midas_snps_table_open_range', 'midas_snps_table_count_rows', 'midas_snps_table_close', 'midas_snps_table_rows', 'midas_snps_table_key_bytes',
     'midas_snps_table_copy', 'midas_merge_sites', 'midas_genes_count', 'midas_genes_terms', 'midas_genes_sum', 'midas_merge_write_info',
+    'midas_genes_count_device', 'midas_genes_count_timing',
     'midas_merge_write_matrix',
     'midas_bam_open_share',
     'midas_comm_device_key', 'midas_comm_probe', 'midas_comm_unique_id', 'midas_comm_create', 'midas_comm_destroy', 'midas_comm_all_gather', 'midas_comm_all_to_all_v',
@@ -413,8 +417,9 @@ SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_
                  'midas_sites_write_markers', 'midas_sites_write_pairs']
 
 
-# the SAM decode (run_midas.py snps --sam): bound above like the rest, listed by themselves
-SAM_SYMBOLS = ['midas_sam_load_device', 'midas_sam_decode_timing']
+# the SAM decode (run_midas.py snps --sam, genes --sam): bound above like the rest, listed by themselves
+SAM_SYMBOLS = ['midas_sam_load_device', 'midas_sam_decode_timing', 'midas_sam_load_device_order']
+SAM_ORDERS = {'coordinate': 0, 'file': 1}        # MIDAS_SAM_ORDER_*
 SAM_PHASES = ('map + header', 'upload', 'line index', 'pass 1 (fields)', 'scans', 'pass 2 (payload)', 'sort + gather', 'columns down')
 
 
@@ -650,18 +655,25 @@ def read_bam(path: str, ctx=None, payload_on_device: bool = False, resident: boo
     return names, lens, refid, reads
 
 
-def read_sam(path: str, ctx=None):
+def read_sam(path: str, ctx=None, order: str = 'coordinate'):
     """Decode the aligner's SAM text on the device of `ctx` (midas_sam_load_device) -> (ref_names, ref_lengths, refid[int32],
     ReadsSoA), the tuple read_bam(..., payload_on_device=True) returns: the records with a reference, coordinate-sorted there
     (equal keys in file order), the small columns as views of the decoder's host buffers, SEQ / QUAL / CIGAR as device
-    addresses (`device`).  There is no host decoder: without a device context this raises ERR_INVALID_ARG."""
+    addresses (`device`).  order='file': the records stay in the order of their lines (midas_sam_load_device_order; what
+    Context.genes_count_device wants).  There is no host decoder: without a device context this raises ERR_INVALID_ARG."""
     if ctx is None or not getattr(ctx, 'inflates', False):
         raise MidasSnpsError(ERR_INVALID_ARG, "read_sam needs a device context (the SAM text is parsed and sorted on the GPU)")
+    if order not in SAM_ORDERS:
+        raise MidasSnpsError(ERR_INVALID_ARG, "read_sam: order is 'coordinate' or 'file', not %r" % (order,))
     lib = load_library()
     h = C.c_void_p()
     err = C.create_string_buffer(256)
     n, sb, qb, nc = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
-    st = lib.midas_sam_load_device(path.encode(), ctx._h, C.byref(h), C.byref(n), C.byref(sb), C.byref(qb), C.byref(nc), err)
+    if order == 'coordinate':
+        st = lib.midas_sam_load_device(path.encode(), ctx._h, C.byref(h), C.byref(n), C.byref(sb), C.byref(qb), C.byref(nc), err)
+    else:
+        st = lib.midas_sam_load_device_order(path.encode(), ctx._h, SAM_ORDERS[order], C.byref(h), C.byref(n), C.byref(sb), C.byref(qb),
+                                             C.byref(nc), err)
     if st != 0:
         raise MidasSnpsError(st, err.value.decode())
     owner = _BamOwner(lib, h)
@@ -1377,6 +1389,31 @@ class Context:
                                          C.byref(ms))
         self._check(st)
         return aligned, mapped, depth, float(ms.value)
+
+    def genes_count_device(self, thr: Thresholds, reads: "ReadsSoA", ref_id, gene_length):
+        """midas_genes_count_device(): genes_count over a ReadsSoA whose QUAL / CIGAR lie on this context's device (read_sam(...,
+        order='file'), read_bam(..., payload_on_device=True), BamSlice.load_ranges(ctx=...)); the per-read facts are made there."""
+        if isinstance(reads, ResidentReads):
+            reads = reads.to_columns(self)
+        if reads.device is None:
+            raise MidasSnpsError(ERR_INVALID_ARG, "genes_count_device takes reads whose payload is on the device (genes_count takes host columns)")
+        rid = np.ascontiguousarray(ref_id, dtype=np.int32)
+        gl = np.ascontiguousarray(gene_length, dtype=np.int64)
+        n = gl.shape[0]
+        aligned, mapped, depth = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        ms = C.c_float(0)
+        r = reads._c()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        st = self._lib.midas_genes_count_device(self._h, C.byref(thr), C.byref(r), p(rid), n, p(gl), p(aligned), p(mapped), p(depth),
+                                                C.byref(ms))
+        self._check(st)
+        return aligned, mapped, depth, float(ms.value)
+
+    def genes_count_timing(self) -> dict:
+        """Device milliseconds of the last genes_count_device on this context (midas_genes_count_timing), by phase."""
+        ms = (C.c_float * 2)()
+        self._check(self._lib.midas_genes_count_timing(self._h, ms))
+        return {'facts kernel': float(ms[0]), 'filter + sort + sums': float(ms[1])}
 
     def genes_terms(self, thr: Thresholds, reads: "ReadsSoA", ref_id, gene_length):
         """midas_genes_terms(): per read of a slice its term (f64; +0.0 for a read keep_read drops)."""

@@ -93,6 +93,7 @@ struct midas_snps_ctx {
   int pad_rule = 0;       // MIDAS_SNPS_PAD_SPEC: what P does to the query position (midas_snps_set_pad_rule)
   int row_coder = 0;      // MIDAS_SNPS_ROWS_DEVICE: who formats and deflates a batch's rows (midas_snps_set_row_coder)
   float sam_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // phases of the last midas_sam_load_device (midas_sam_decode_timing)
+  float genes_ms[2] = {0, 0};                   // facts kernel, filter + sort + sums of the last midas_genes_count_device (midas_genes_count_timing)
   int default_path = 0;   // MIDAS_SNPS_PATH_AUTO: what batches created on this context take (midas_snps_set_default_path)
   // midas_snps_batch_write_part may be called from several host threads at once (one table each): the device part of a
   // call -- kernel, copies through the staging ring below -- is taken one at a time, the file writes run side by side

@@ -4,8 +4,10 @@
 //
 // The reference walks the (unsorted) BAM once and accumulates `gene.depth += align_len / float(gene.length)` read by
 // read.  fp64 addition is not associative, so the sum has to be reproduced in exactly that order:
-//   host    per read, 8 bytes: aligned length (pysam's clip rules), l_seq, NM, floor(mean quality), mapq, three
-//           "absent" flags -- a pass over the quality bytes and CIGARs on all host cores;
+//   facts   per read, 8 bytes: aligned length (pysam's clip rules), l_seq, NM, floor(mean quality), mapq, three
+//           "absent" flags -- a pass over the quality bytes and CIGARs: on all host cores when those columns are host
+//           memory (pack_records), by sixteen lanes a read when they lie on the device (genes_facts_kernel,
+//           midas_genes_count_device: what midas_sam_load_device_order / midas_bam_load_device hand out);
 //   filter  one thread per read, BAM order: keep_read with the exceptions the reference would raise (lowest read
 //           index wins), and the read's term  align_len / float(gene.length)  (+0.0 for a read that is dropped:
 //           adding it leaves the running sum unchanged bit for bit);
@@ -76,6 +78,99 @@ __global__ __launch_bounds__(256) void genes_filter_kernel(FilterKParams p) {
   if (err) atomicMin(p.err, ((unsigned long long)i << 8) | err);
   // the reference's own expression; a dropped read contributes +0.0
   p.term[i] = keep ? (double)align_len / (double)p.gene_len[p.gene[i]] : 0.0;
+}
+
+// ---- the 8-byte record from DEVICE-resident QUAL / CIGAR columns: pack_records, to the bit ---------------------------------
+// A read's record is made by sixteen lanes (a quarter wave).  Its quality run [q0, q0 + l) starts at any byte: lane k takes
+// the 16-byte ALIGNED granules k, k + 16, ... of the run (one global_load_dwordx4 each, 256 contiguous bytes a read and
+// step), drops the bytes in front of and behind the run with a byte mask, and adds the rest up four at a time (v_sad_u8
+// against zero).  A granule that is not wholly inside the column [qual, qual + qual_total) -- only a run's first one when
+// the column starts off a 16-byte border, only its last one when the column ends there (the last read's) -- is not loaded
+// as a vector: its at most 15 bytes of the run are fetched one by one, so no load reaches outside the column whatever its
+// address and whatever lies behind it.  The partial sums meet by four xor-shuffles inside the quarter wave.  Lane 0 walks
+// the few CIGAR ops at both ends and stores the record (one 8-byte store).
+// A read pack_records would refuse leaves (read << 8 | kind) in *bad, lowest read first, and a record of zeros; its gene is
+// set to 0 so that the filter kernel behind this one indexes nothing outside the gene table.  Offsets that point outside
+// their column are refused here too (kFactLayout): the host's pass would read whatever lies there, a kernel must not.
+enum : uint32_t { kFactRef = 1, kFactLayout = 2, kFactSize = 3 };
+constexpr int kFactLanes = 16;
+
+struct FactsKParams {
+  const int32_t* l_seq; const int32_t* nm; const uint8_t* mapq;      // [n]
+  const long long* qual_off; const long long* cigar_off;             // [n + 1]
+  const uint8_t* qual; const uint32_t* cigar;                        // the columns, qual_total bytes / cigar_total ops
+  long long qual_total, cigar_total;
+  uint32_t* gene;                // [n] in: ref_id; a gene outside the table becomes 0
+  uint2* rec;                    // [n] out
+  unsigned long long* bad;       // atomicMin((read << 8) | kind)
+  long long n, n_genes;
+};
+
+__device__ __forceinline__ uint32_t byte_mask4(uint32_t nib) {      // bit k of nib -> byte k all ones
+  return ((nib & 1u) | (nib & 2u) << 7 | (nib & 4u) << 14 | (nib & 8u) << 21) * 0xFFu;
+}
+
+__global__ __launch_bounds__(256) void genes_facts_kernel(FactsKParams p) {
+  const int sub = threadIdx.x & (kFactLanes - 1);
+  const long long i = (long long)blockIdx.x * (256 / kFactLanes) + (threadIdx.x / kFactLanes);
+  if (i >= p.n) return;                               // (the same in all sixteen lanes of a read, like everything up to the loads)
+  const long long g = (long long)(int32_t)p.gene[i];
+  const long long l = p.l_seq[i], nm = p.nm[i];
+  const long long q0 = p.qual_off[i], q1 = p.qual_off[i + 1], c0 = p.cigar_off[i], c1 = p.cigar_off[i + 1];
+  const long long nc = c1 - c0;
+  uint32_t kind = 0;
+  if (g < 0 || g >= p.n_genes) kind = kFactRef;
+  else if (l < 0 || nc < 0 || q1 - q0 < l || q0 < 0 || q0 + l > p.qual_total || c0 < 0 || c1 > p.cigar_total) kind = kFactLayout;
+  else if (l > kMaxLSeq || nm > kMaxField16) kind = kFactSize;
+  if (kind) {
+    if (sub == 0) {
+      atomicMin(p.bad, ((unsigned long long)i << 8) | kind);
+      p.rec[i] = make_uint2(0u, 0u);
+      if (kind == kFactRef) p.gene[i] = 0u;
+    }
+    return;
+  }
+  // ---- sum of the l quality bytes ------------------------------------------------------------------------------------------
+  const unsigned long long col_lo = (unsigned long long)p.qual, col_hi = col_lo + (unsigned long long)p.qual_total;
+  const unsigned long long run_lo = col_lo + (unsigned long long)q0, run_hi = run_lo + (unsigned long long)l;
+  uint32_t qsum = 0;
+  for (unsigned long long b = (run_lo & ~15ull) + 16ull * (unsigned)sub; b < run_hi; b += 16ull * kFactLanes) {
+    const unsigned long long lo = b < run_lo ? run_lo : b, hi = b + 16 > run_hi ? run_hi : b + 16;     // the run's bytes of this granule
+    if (b >= col_lo && b + 16 <= col_hi) {
+      const uint4 v = *reinterpret_cast<const uint4*>(p.qual + (b - col_lo));        // (off the column's pointer: a global load)
+      const uint32_t m = ((1u << (unsigned)(hi - b)) - 1u) & ~((1u << (unsigned)(lo - b)) - 1u);         // (hi - b <= 16)
+      qsum = __builtin_amdgcn_sad_u8(v.x & byte_mask4(m & 15u), 0u, qsum);
+      qsum = __builtin_amdgcn_sad_u8(v.y & byte_mask4((m >> 4) & 15u), 0u, qsum);
+      qsum = __builtin_amdgcn_sad_u8(v.z & byte_mask4((m >> 8) & 15u), 0u, qsum);
+      qsum = __builtin_amdgcn_sad_u8(v.w & byte_mask4((m >> 12) & 15u), 0u, qsum);
+    } else {
+      for (unsigned long long a = lo; a < hi; ++a) qsum += p.qual[a - col_lo];          // (a column's border granule: < 16 bytes)
+    }
+  }
+#pragma unroll
+  for (int w = kFactLanes / 2; w >= 1; w >>= 1) qsum += (uint32_t)__shfl_xor((int)qsum, w, kFactLanes);
+  if (sub != 0) return;
+  // ---- [EXT] pysam query_alignment_start / _end, as pack_records walks them -----------------------------------------------------
+  const uint32_t* cg = p.cigar + c0;
+  long long qs = 0;
+  for (long long k = 0; k < nc; ++k) {
+    const uint32_t w = cg[k], op = w & 15u;
+    if (op == 5u) continue;
+    if (op == 4u) qs += w >> 4; else break;
+  }
+  long long qe = l;
+  for (long long k = nc - 1; k >= 1; --k) {
+    const uint32_t w = cg[k], op = w & 15u;
+    if (op == 5u) continue;
+    if (op == 4u) qe -= w >> 4; else break;
+  }
+  long long al = qe - qs > 0 ? qe - qs : 0;
+  if (al > l) al = l;
+  const bool no_qual = l > 0 && p.qual[q0] == 0xFFu;
+  const uint32_t flags = (l == 0 ? kNoSeq : 0u) | (nm < 0 ? kNoNm : 0u) | (no_qual ? kNoQual : 0u);
+  const uint32_t nm_u = (uint32_t)(nm < 0 ? 0 : nm);
+  const uint32_t qmean = l > 0 ? qsum / (uint32_t)l : 0u;
+  p.rec[i] = make_uint2((uint32_t)al | ((uint32_t)l << 11) | (flags << 22), nm_u | (qmean << 16) | ((uint32_t)p.mapq[i] << 24));
 }
 
 // first sorted position of every gene: begin[g] = lowest i with key[i] >= g; begin[n_genes] = n
@@ -214,6 +309,20 @@ struct DevBufs {
     }                                                                                                            \
   } while (0)
 
+// The first read in BAM order that no record can be made of: the status and message of both routes (pack_records on the host,
+// genes_facts_kernel on the device).
+int32_t raise_malformed(midas_snps_ctx* ctx, int64_t first, uint32_t kind, const int32_t* ref_id) {
+  ctx->err_read = first;
+  char buf[200];
+  if (kind == kFactRef) {
+    snprintf(buf, sizeof buf, "read %lld: reference id %lld is not a gene of the pangenome (the reference fails in getrname / genes[...])",
+             (long long)first, (long long)ref_id[first]);
+    return gfail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+  }
+  if (kind == kFactLayout) return gfail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, "negative size or CSR offsets shorter than l_seq");
+  return gfail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "l_seq > 1024 or NM > 65534 is not supported");
+}
+
 // host: per read, the numbers keep_read looks at (all cores).  0, or the status of the first malformed read in BAM order.
 int32_t pack_records(midas_snps_ctx* ctx, const midas_snps_reads* reads, const int32_t* ref_id, int64_t n_genes, std::vector<uint2>* recs,
                      int32_t* max_l_out) {
@@ -267,15 +376,7 @@ int32_t pack_records(midas_snps_ctx* ctx, const midas_snps_reads* reads, const i
   // the first malformed read in BAM order decides, as a single forward pass would
   const int64_t first = std::min(bad_ref.load(), std::min(bad_layout.load(), bad_size.load()));
   if (first == INT64_MAX) return MIDAS_SNPS_OK;
-  ctx->err_read = first;
-  char buf[200];
-  if (first == bad_ref.load()) {
-    snprintf(buf, sizeof buf, "read %lld: reference id %lld is not a gene of the pangenome (the reference fails in getrname / genes[...])",
-             (long long)first, (long long)ref_id[first]);
-    return gfail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
-  }
-  if (first == bad_layout.load()) return gfail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, "negative size or CSR offsets shorter than l_seq");
-  return gfail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "l_seq > 1024 or NM > 65534 is not supported");
+  return raise_malformed(ctx, first, first == bad_ref.load() ? kFactRef : first == bad_layout.load() ? kFactLayout : kFactSize, ref_id);
 }
 
 int32_t raise_status(midas_snps_ctx* ctx, unsigned long long err) {
@@ -289,12 +390,13 @@ int32_t raise_status(midas_snps_ctx* ctx, unsigned long long err) {
   return kind;
 }
 
-// One call, either half or both.  reads != nullptr: the terms are made here (host records + filter kernel) from the reads and
-// their genes `gene` (= ref_id); else `term_in` holds them.  out_term != nullptr: they are handed back (and, with no sums asked
+// One call, either half or both.  reads != nullptr: the terms are made here (records + filter kernel) from the reads and
+// their genes `gene` (= ref_id) -- the records by the host's cores (pack_records), or, with payload_on_device (reads->qual /
+// ->cigar are device addresses), by genes_facts_kernel; everything behind the records is the same; else `term_in` holds them.  out_term != nullptr: they are handed back (and, with no sums asked
 // for, that is all).  out_aligned != nullptr: sort + bounds + sums.
 int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const midas_snps_reads* reads, int64_t n, const int32_t* gene,
                   const double* term_in, int64_t n_genes, const int64_t* gene_length, double* out_term, int64_t* out_aligned,
-                  int64_t* out_mapped, double* out_depth, float* out_kernel_ms) {
+                  int64_t* out_mapped, double* out_depth, float* out_kernel_ms, bool payload_on_device = false) {
   ctx->clear_error();
   ctx->err_read = -1;
   if (out_kernel_ms) *out_kernel_ms = 0.f;
@@ -303,7 +405,12 @@ int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const m
   std::vector<uint2> recs;
   FilterTables ft;
   memset(&ft, 0, sizeof ft);
-  if (filter) {
+  const bool facts = filter && payload_on_device;
+  if (facts) {
+    // (no pass over the reads here: the tables for every length a record can hold -- an entry is only ever read at a read's own
+    // lengths, so the ones pack_records' max_l would have left zero are never looked at)
+    build_filter_tables(thr->mapid, thr->aln_cov, kMaxLSeq, &ft);
+  } else if (filter) {
     int32_t max_l = 0;
     const int32_t st = pack_records(ctx, reads, gene, n_genes, &recs, &max_l);
     if (st != MIDAS_SNPS_OK) return st;
@@ -323,6 +430,7 @@ int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const m
   uint2* d_recs = nullptr; uint32_t* d_key = nullptr; uint32_t* d_key_b = nullptr; double* d_term = nullptr; double* d_term_b = nullptr;
   int64_t* d_len = nullptr; FilterTables* d_ft = nullptr; long long* d_begin = nullptr; long long* d_al = nullptr; long long* d_mp = nullptr;
   double* d_dp = nullptr; unsigned long long* d_err = nullptr; unsigned int* d_heavy = nullptr; uint32_t* d_hist = nullptr;
+  int32_t* d_lseq = nullptr; int32_t* d_nm = nullptr; uint8_t* d_mapq = nullptr; long long* d_qoff = nullptr; long long* d_coff = nullptr;
   G_TRY(dev.get(&d_key, nr * 4));
   G_TRY(dev.get(&d_term, nr * 8));
   G_TRY(dev.get(&d_err, 16));
@@ -330,6 +438,13 @@ int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const m
     G_TRY(dev.get(&d_recs, nr * sizeof(uint2)));
     G_TRY(dev.get(&d_len, ng * 8));
     G_TRY(dev.get(&d_ft, sizeof(FilterTables)));
+  }
+  if (facts) {        // the small columns of the reads: 29 bytes a read, uploaded once
+    G_TRY(dev.get(&d_lseq, nr * 4));
+    G_TRY(dev.get(&d_nm, nr * 4));
+    G_TRY(dev.get(&d_mapq, nr));
+    G_TRY(dev.get(&d_qoff, (nr + 1) * 8));
+    G_TRY(dev.get(&d_coff, (nr + 1) * 8));
   }
   if (sums) {
     G_TRY(dev.get(&d_key_b, nr * 4));
@@ -345,24 +460,44 @@ int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const m
   while (key_bits < 32 && ((int64_t)1 << key_bits) < n_genes) ++key_bits;
   if (n > 0) {
     G_TRY(hipMemcpyAsync(d_key, gene, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (filter) G_TRY(hipMemcpyAsync(d_recs, recs.data(), (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, s));
+    if (facts) {
+      G_TRY(hipMemcpyAsync(d_lseq, reads->l_seq, (size_t)n * 4, hipMemcpyHostToDevice, s));
+      G_TRY(hipMemcpyAsync(d_nm, reads->nm, (size_t)n * 4, hipMemcpyHostToDevice, s));
+      G_TRY(hipMemcpyAsync(d_mapq, reads->mapq, (size_t)n, hipMemcpyHostToDevice, s));
+      G_TRY(hipMemcpyAsync(d_qoff, reads->qual_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+      G_TRY(hipMemcpyAsync(d_coff, reads->cigar_off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+    } else if (filter) G_TRY(hipMemcpyAsync(d_recs, recs.data(), (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, s));
     else G_TRY(hipMemcpyAsync(d_term, term_in, (size_t)n * 8, hipMemcpyHostToDevice, s));
   }
   if (filter) {
     if (n_genes > 0) G_TRY(hipMemcpyAsync(d_len, gene_length, (size_t)n_genes * 8, hipMemcpyHostToDevice, s));
     G_TRY(hipMemcpyAsync(d_ft, &ft, sizeof ft, hipMemcpyHostToDevice, s));
   }
-  G_TRY(hipMemsetAsync(d_err, 0xFF, 8, s));
+  G_TRY(hipMemsetAsync(d_err, 0xFF, 16, s));        // [0]: the filter's, [1]: the facts kernel's
   if (sums) G_TRY(hipMemsetAsync(d_heavy, 0, 4, s));
   struct EvGuard {      // (constructed before either event exists: a failing second create must not leak the first)
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipEvent_t a = nullptr, b = nullptr, c = nullptr;
+    ~EvGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); if (c) (void)hipEventDestroy(c); }
   } evg;
   G_TRY(hipEventCreate(&evg.a));
   G_TRY(hipEventCreate(&evg.b));
-  const hipEvent_t e0 = evg.a, e1 = evg.b;
-  unsigned long long err = ~0ull;
+  if (facts) G_TRY(hipEventCreate(&evg.c));
+  const hipEvent_t e0 = evg.a, e1 = evg.b, ef = evg.c;
+  unsigned long long err[2] = {~0ull, ~0ull};
   G_TRY(hipEventRecord(e0, s));
+  if (facts) {
+    if (n > 0) {
+      // (qual_off[n] / cigar_off[n]: the columns' sizes -- what the caller says lies at reads->qual / ->cigar)
+      FactsKParams f;
+      f.l_seq = d_lseq; f.nm = d_nm; f.mapq = d_mapq; f.qual_off = d_qoff; f.cigar_off = d_coff;
+      f.qual = reads->qual; f.cigar = reads->cigar; f.qual_total = reads->qual_off[n]; f.cigar_total = reads->cigar_off[n];
+      f.gene = d_key; f.rec = d_recs; f.bad = d_err + 1; f.n = n; f.n_genes = n_genes;
+      constexpr int kPerBlock = 256 / kFactLanes;
+      hipLaunchKernelGGL(genes_facts_kernel, dim3((unsigned)((n + kPerBlock - 1) / kPerBlock)), dim3(256), 0, s, f);
+      G_TRY(hipGetLastError());
+    }
+    G_TRY(hipEventRecord(ef, s));
+  }
   if (filter && n > 0) {
     FilterKParams f;
     f.rec = d_recs; f.gene = d_key; f.gene_len = d_len; f.filt = d_ft; f.term = d_term; f.err = d_err; f.n = n;
@@ -396,12 +531,20 @@ int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const m
   } else {
     G_TRY(hipEventRecord(e1, s));
   }
-  G_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, s));
+  G_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, s));
   G_TRY(hipStreamSynchronize(s));
   float ms = 0.f;
   G_TRY(hipEventElapsedTime(&ms, e0, e1));
   if (out_kernel_ms) *out_kernel_ms = ms;
-  if (err != ~0ull) return raise_status(ctx, err);
+  if (facts) {
+    float ms_f = 0.f;
+    G_TRY(hipEventElapsedTime(&ms_f, e0, ef));
+    ctx->genes_ms[0] = ms_f;
+    ctx->genes_ms[1] = ms - ms_f;
+  }
+  // a read no record could be made of comes first, as pack_records returns before the filter has seen anything
+  if (err[1] != ~0ull) return raise_malformed(ctx, (int64_t)(err[1] >> 8), (uint32_t)(err[1] & 0xFF), gene);
+  if (err[0] != ~0ull) return raise_status(ctx, err[0]);
   return MIDAS_SNPS_OK;
 }
 
@@ -421,6 +564,25 @@ extern "C" int32_t midas_genes_count(midas_snps_ctx* ctx, const midas_snps_thres
   double dummy_d = 0.0;
   return genes_run(ctx, thr, reads, reads->n_reads, ref_id, nullptr, n_genes, gene_length, nullptr, n_genes > 0 ? out_aligned : &dummy_a,
                    n_genes > 0 ? out_mapped : &dummy_m, n_genes > 0 ? out_depth : &dummy_d, out_kernel_ms);
+}
+
+extern "C" int32_t midas_genes_count_device(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const midas_snps_reads* reads,
+                                            const int32_t* ref_id, int64_t n_genes, const int64_t* gene_length,
+                                            int64_t* out_aligned, int64_t* out_mapped, double* out_depth, float* out_kernel_ms) {
+  if (!ctx || !thr || n_genes < 0 || !reads_ok(reads, ref_id) || (n_genes > 0 && (!gene_length || !out_aligned || !out_mapped || !out_depth)))
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  if (reads->n_reads > 0 && (reads->qual_off[reads->n_reads] < 0 || reads->cigar_off[reads->n_reads] < 0)) return MIDAS_SNPS_ERR_INVALID_ARG;
+  int64_t dummy_a = 0, dummy_m = 0;
+  double dummy_d = 0.0;
+  return genes_run(ctx, thr, reads, reads->n_reads, ref_id, nullptr, n_genes, gene_length, nullptr, n_genes > 0 ? out_aligned : &dummy_a,
+                   n_genes > 0 ? out_mapped : &dummy_m, n_genes > 0 ? out_depth : &dummy_d, out_kernel_ms, true);
+}
+
+extern "C" int32_t midas_genes_count_timing(const midas_snps_ctx* ctx, float* out_ms2) {
+  if (!ctx || !out_ms2) return MIDAS_SNPS_ERR_INVALID_ARG;
+  out_ms2[0] = ctx->genes_ms[0];
+  out_ms2[1] = ctx->genes_ms[1];
+  return MIDAS_SNPS_OK;
 }
 
 extern "C" int32_t midas_genes_terms(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const midas_snps_reads* reads,

@@ -14,6 +14,9 @@
 //            len << 4 | op (a lane that holds an op letter ranks itself by ballot and reads its digits backwards)
 //   sort     (pos + 1, index) through the library's stable radix sort, then (refID, index): equal keys keep file order
 //   gather   one wave a sorted record: the small columns, the rebuilt offsets, the payload bytes in sorted order
+// MIDAS_SAM_ORDER_FILE (midas_sam_load_device_order; run_midas.py genes, whose fp64 sums follow the order of the aligner's
+// lines): no sort and no gather -- the columns pass 2 accumulated, chunk after chunk, ARE the result: the small ones are
+// copied down, the three payload arrays are handed to the handle as they are.
 // Everything a kernel reads of the text lies inside its line; everything it writes lies inside room the host sized from the
 // scans' totals before the launch.
 #include <hip/hip_runtime.h>
@@ -452,9 +455,21 @@ extern "C" int32_t midas_sam_decode_timing(const midas_snps_ctx* ctx, float* out
   return MIDAS_SNPS_OK;
 }
 
-extern "C" int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
-                                         int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
-  if (!ctx || !path || !out) return MIDAS_SNPS_ERR_INVALID_ARG;
+namespace {
+
+// the three payload arrays of a file-order decode: separate allocations, freed together when the handle closes
+struct SamPayloadOwner { void* p[3]; };
+void sam_payload_free(void* o) {
+  SamPayloadOwner* w = static_cast<SamPayloadOwner*>(o);
+  if (!w) return;
+  for (void* q : w->p) if (q) (void)hipFree(q);
+  delete w;
+}
+
+int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
+                 int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
+  if (!ctx || !path || !out || (order != MIDAS_SAM_ORDER_COORDINATE && order != MIDAS_SAM_ORDER_FILE)) return MIDAS_SNPS_ERR_INVALID_ARG;
+  const bool file_order = order == MIDAS_SAM_ORDER_FILE;
   *out = nullptr;
   if (err256) err256[0] = 0;
   using clock = std::chrono::steady_clock;
@@ -635,8 +650,9 @@ extern "C" int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, 
     SAM_TRY(g_lseq.need(n2 * 4, (size_t)n * 4, st)); SAM_TRY(g_ncig.need(n2 * 4, (size_t)n * 4, st)); SAM_TRY(g_mapq.need(n2, (size_t)n, st));
     SAM_TRY(g_flag.need(n2 * 2, (size_t)n * 2, st)); SAM_TRY(g_soff.need(n2 * 8, (size_t)n * 8, st)); SAM_TRY(g_qoff.need(n2 * 8, (size_t)n * 8, st));
     SAM_TRY(g_coff.need(n2 * 8, (size_t)n * 8, st));
-    SAM_TRY(g_seq.need((size_t)tot_seq + tot[1], (size_t)tot_seq, st)); SAM_TRY(g_qual.need((size_t)tot_qual + tot[2], (size_t)tot_qual, st));
-    SAM_TRY(g_cigar.need(((size_t)tot_cigar + tot[3]) * 4, (size_t)tot_cigar * 4, st));
+    // (64 bytes of room behind each: a file-order decode keeps these arrays, and zeroes that room as the sorted one does)
+    SAM_TRY(g_seq.need((size_t)tot_seq + tot[1] + 64, (size_t)tot_seq, st)); SAM_TRY(g_qual.need((size_t)tot_qual + tot[2] + 64, (size_t)tot_qual, st));
+    SAM_TRY(g_cigar.need(((size_t)tot_cigar + tot[3]) * 4 + 64, (size_t)tot_cigar * 4, st));
     cols.refid = static_cast<int32_t*>(g_refid.p); cols.pos = static_cast<int32_t*>(g_pos.p); cols.nm = static_cast<int32_t*>(g_nm.p);
     cols.l_seq = static_cast<int32_t*>(g_lseq.p); cols.n_cigar = static_cast<uint32_t*>(g_ncig.p); cols.mapq = static_cast<uint8_t*>(g_mapq.p);
     cols.flag = static_cast<uint16_t*>(g_flag.p); cols.seq_off = static_cast<long long*>(g_soff.p); cols.qual_off = static_cast<long long*>(g_qoff.p);
@@ -652,6 +668,39 @@ extern "C" int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, 
     if (n > 2000000000ll) return sam_err(err256, MIDAS_SNPS_ERR_UNSUPPORTED, "%s: more than 2 * 10^9 records (%lld): decode it in parts", path, n);
     lines_before += lines;
     at += (long long)last_end + 1;           // (a final line without '\n': one past the text, and the loop ends)
+  }
+  if (file_order) {
+    // ---- file order: the accumulated columns are the result ------------------------------------------------------------------------
+    std::unique_ptr<midas_bam, void (*)(midas_bam*)> b(bam_new_columns_handle(path, names, lens), midas_bam_close);
+    HostColumns hc{};
+    if (!b || !bam_alloc_host_columns(b.get(), n, &hc)) return sam_err(err256, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "%s: out of host memory for %lld records", path, n);
+    SAM_TRY(g_seq.need(64, 0, st)); SAM_TRY(g_qual.need(64, 0, st)); SAM_TRY(g_cigar.need(64, 0, st));      // (no record at all: the room alone)
+    SAM_TRY(hipMemsetAsync(static_cast<uint8_t*>(g_seq.p) + tot_seq, 0, 64, st));
+    SAM_TRY(hipMemsetAsync(static_cast<uint8_t*>(g_qual.p) + tot_qual, 0, 64, st));
+    SAM_TRY(hipMemsetAsync(static_cast<uint8_t*>(g_cigar.p) + (size_t)tot_cigar * 4, 0, 64, st));
+    if (n > 0) {
+      const size_t nn = (size_t)n;
+      SAM_TRY(hipMemcpyAsync(hc.refid, cols.refid, nn * 4, hipMemcpyDeviceToHost, st)); SAM_TRY(hipMemcpyAsync(hc.pos, cols.pos, nn * 4, hipMemcpyDeviceToHost, st));
+      SAM_TRY(hipMemcpyAsync(hc.nm, cols.nm, nn * 4, hipMemcpyDeviceToHost, st)); SAM_TRY(hipMemcpyAsync(hc.l_seq, cols.l_seq, nn * 4, hipMemcpyDeviceToHost, st));
+      SAM_TRY(hipMemcpyAsync(hc.flag, cols.flag, nn * 2, hipMemcpyDeviceToHost, st)); SAM_TRY(hipMemcpyAsync(hc.mapq, cols.mapq, nn, hipMemcpyDeviceToHost, st));
+      SAM_TRY(hipMemcpyAsync(hc.seq_off, cols.seq_off, nn * 8, hipMemcpyDeviceToHost, st)); SAM_TRY(hipMemcpyAsync(hc.qual_off, cols.qual_off, nn * 8, hipMemcpyDeviceToHost, st));
+      SAM_TRY(hipMemcpyAsync(hc.cigar_off, cols.cigar_off, nn * 8, hipMemcpyDeviceToHost, st));
+    }
+    SAM_TRY(hipStreamSynchronize(st));
+    hc.seq_off[n] = tot_seq; hc.qual_off[n] = tot_qual; hc.cigar_off[n] = tot_cigar;
+    lap(7);
+    SamPayloadOwner* own = new (std::nothrow) SamPayloadOwner{{g_seq.p, g_qual.p, g_cigar.p}};
+    if (!own) return sam_err(err256, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "%s: out of host memory for %lld records", path, n);
+    bam_set_device_payload(b.get(), g_seq.p, g_qual.p, g_cigar.p, own, sam_payload_free);
+    g_seq.p = g_qual.p = g_cigar.p = nullptr;
+    bam_columns_ready(b.get(), n);
+    if (n_reads) *n_reads = n;
+    if (seq_bytes) *seq_bytes = tot_seq;
+    if (qual_bytes) *qual_bytes = tot_qual;
+    if (n_cigar) *n_cigar = tot_cigar;
+    for (int k = 0; k < 8; ++k) ctx->sam_ms[k] = ms[k];
+    *out = b.release();
+    return MIDAS_SNPS_OK;
   }
   if (tot_qual >= (1ll << 32))
     return sam_err(err256, MIDAS_SNPS_ERR_UNSUPPORTED, "%s: %lld bytes of QUAL: the SAM decode's sorted offsets address 4 GiB of them", path, tot_qual);
@@ -736,4 +785,16 @@ extern "C" int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, 
   for (int k = 0; k < 8; ++k) ctx->sam_ms[k] = ms[k];
   *out = b.release();
   return MIDAS_SNPS_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
+                                         int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
+  return sam_load(path, ctx, MIDAS_SAM_ORDER_COORDINATE, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
+}
+
+extern "C" int32_t midas_sam_load_device_order(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam** out, int64_t* n_reads,
+                                               int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
+  return sam_load(path, ctx, order, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
 }

@@ -5,6 +5,9 @@ genes, bowtie2 alignment, then per gene: aligned reads, reads passing the read f
 the median depth of the species' marker genes -- with the pass over the BAM (count_mapped_bp, :165-180) done by the
 device through the C-ABI (midas_genes_count): every read of a gene is filtered and its aligned length / gene length
 added to the gene's depth in BAM order, so the fp64 sums are the reference's bit for bit.  No CPU fallback for it.
+--sam: bowtie2's own SAM text (genes/temp/pangenomes.sam) stands in for the BAM and samtools is not needed -- the text is
+parsed on the device in the order of its lines (= the BAM's order) and the per-read facts are made there as well
+(read_sam(order='file'), midas_genes_count_device).
 """
 
 import csv
@@ -129,10 +132,18 @@ def build_pangenome_db(args, species):
 
 def pangenome_align(args):
     """bowtie2 (no unaligned reads) | samtools view -b > genes/temp/pangenomes.bam, unsorted, with the reference's
-    switches (genes.py:118-146)."""
-    if not args.get('bowtie2') or not args.get('samtools'):
-        sys.exit("\nError: bowtie2 / samtools not found on PATH (needed for --align; the aligner is not part of this build)\n")
+    switches (genes.py:118-146).  args['sam']: bowtie2 alone, the same switches plus -S genes/temp/pangenomes.sam -- --call_genes
+    parses the text on the device, in the order of its lines (midas_sam_load_device_order)."""
     temp = os.path.join(args['outdir'], 'genes', 'temp')
+    if args.get('sam'):
+        if not args.get('bowtie2'):
+            sys.exit("\nError: bowtie2 not found on PATH (needed for --align --sam; the aligner is not part of this build)\n")
+        # --call_genes prefers pangenomes.bam: an older one would be counted in place of the SAM written now
+        stale = os.path.join(temp, 'pangenomes.bam')
+        if os.path.isfile(stale):
+            sys.exit("\nError: %s exists and --call_genes reads it in preference to pangenomes.sam: remove it, or align without --sam\n" % stale)
+    elif not args.get('bowtie2') or not args.get('samtools'):
+        sys.exit("\nError: bowtie2 / samtools not found on PATH (needed for --align; the aligner is not part of this build)\n")
     bt2 = [args['bowtie2'], '--no-unal', '-x', os.path.join(temp, 'pangenomes')]
     if args['max_reads']:
         bt2 += ['-u', args['max_reads']]
@@ -146,6 +157,10 @@ def pangenome_align(args):
         bt2 += ['--interleaved', args['m1']]
     else:
         bt2 += ['-U', args['m1']]
+    if args.get('sam'):
+        _shell(args, ' '.join(str(x) for x in bt2 + ['-S', os.path.join(temp, 'pangenomes.sam')]))
+        print("  finished aligning")
+        return
     view = [args['samtools'], 'view', '--threads', args['threads'], '-b', '-', '>', os.path.join(temp, 'pangenomes.bam')]
     _shell(args, ' '.join(str(x) for x in bt2) + ' | ' + ' '.join(str(x) for x in view))
     print("  finished aligning")
@@ -267,11 +282,44 @@ def _count_below_the_species(args, species, genes, ctx, mine, owner, sl):
     return 0.0
 
 
+def _count_from_sam(args, species, genes, ctx, sam_path):
+    """genes.py:165-199 over the aligner's SAM text: the lines are parsed on the device and kept in file order (the order
+    `samtools view -b` would have given the BAM), the per-read facts, the filter and the per-gene sums follow there
+    (midas_genes_count_device) -- what comes down is the small columns and the per-gene numbers."""
+    try:
+        ref_names, ref_lens, refid, reads = abi.read_sam(sam_path, ctx, order='file')
+    except abi.MidasSnpsError as e:
+        sys.exit("\nError: could not read %s\n%s\n" % (sam_path, e.message))
+    _missing_gene_check(ref_names, refid, genes)
+    gene_ids = list(ref_names)
+    lengths = np.array([genes[n].length if n in genes else ref_lens[i] for i, n in enumerate(gene_ids)], dtype=np.int64)
+    try:
+        aligned, mapped, depth, ms = ctx.genes_count_device(_thresholds(args), reads, refid, lengths)
+    except abi.MidasSnpsError as e:
+        # (records without a reference are not counted: the index is the one the BAM of these lines would give)
+        where = " [read %d of the SAM]" % e.read_index if e.read_index >= 0 else ""
+        sys.exit("\nError: %s%s\n" % (e.message, where))
+    known = [k for k, n in enumerate(gene_ids) if n in genes]
+    fold_counts(species, genes, [gene_ids[k] for k in known], aligned[known], mapped[known], depth[known])
+    print("  total aligned reads: %s" % sum(sp.aligned_reads for sp in species.values()))
+    print("  total mapped reads: %s" % sum(sp.mapped_reads for sp in species.values()))
+    return ms
+
+
 def count_mapped_bp(args, species, genes, ctx, mine=None, owner=None):
     """genes.py:165-199 with the BAM pass on the device: native BAM decode, one midas_genes_count call.  `mine` (N > 1):
     the species this rank owns -- only reads on their genes are counted here; with `owner` (species -> rank) and a BAM whose
-    slices chain, every rank decodes only its slice (_count_below_the_species)."""
+    slices chain, every rank decodes only its slice (_count_below_the_species).  No pangenomes.bam but a pangenomes.sam
+    (--align --sam, or any aligner's SAM put there): _count_from_sam, one rank only."""
     bam_path = os.path.join(args['outdir'], 'genes', 'temp', 'pangenomes.bam')
+    sam_path = os.path.join(args['outdir'], 'genes', 'temp', 'pangenomes.sam')
+    if not os.path.isfile(bam_path) and os.path.isfile(sam_path):
+        ws = dist.world()[1]
+        # (every rank sees the same two files, so every rank takes this branch or none does: a BAM run's collectives are as they were)
+        if ws > 1:
+            dist.agree_or_exit("\nError: %d-rank runs need genes/temp/pangenomes.bam (the ranks' shares are slices of the BAM's blocks); only "
+                               "pangenomes.sam was found: run one rank, or turn it into a BAM\n" % ws)
+        return _count_from_sam(args, species, genes, ctx, sam_path)
     if mine is not None and owner is not None and hasattr(ctx, 'genes_terms'):
         sl = _slices_chain(bam_path, *dist.world())
         if sl is not None:

@@ -69,6 +69,8 @@ GENES_OPTION_GROUPS = [
         (['--build_db'], dict(action='store_true', help="concatenate the species' centroid genes and index them with bowtie2-build")),
         (['--align'], dict(action='store_true', help="map the reads with bowtie2 | samtools view")),
         (['--call_genes'], dict(action='store_true', dest='cov', help="reads, depth and copy number per gene (this is the GPU stage)")),
+        (['--sam'], dict(action='store_true', help="with --align, keep bowtie2's SAM as genes/temp/pangenomes.sam and skip samtools;\n"
+                                                   "--call_genes reads it when there is no pangenomes.bam (parsed on the GPU, in file order)")),
     ]),
     OPTION_GROUPS[1],
     ("Reads and aligner (for --align)", [
@@ -201,8 +203,8 @@ def check_arguments(program, args):
         die("Could not find species abundance profile: %s\n"
             "--species_topn / --species_cov need the output of `run_midas.py species`; use --species_id otherwise" % profile)
     have_fa, have_bam = (os.path.isfile(os.path.join(temp, f)) for f in (fa_name, bam_name))
-    if program == 'snps' and not have_bam:       # (--sam: the aligner's text stands in for the BAM)
-        have_bam = os.path.isfile(os.path.join(temp, 'genomes.sam'))
+    if not have_bam:       # (--sam: the aligner's text stands in for the BAM)
+        have_bam = os.path.isfile(os.path.join(temp, 'genomes.sam' if program == 'snps' else 'pangenomes.sam'))
     if args['align'] and not args['build_db'] and not have_fa:
         die("You've specified --align, but no database has been built\nTry running with --build_db")
     if args[last] and not args['align'] and not have_bam:
@@ -247,7 +249,7 @@ def print_arguments(program, args):
                   ('bowtie2', '--%s%s' % (args['speed'], '-local' if args['mode'] == 'local' else '')),
                   ('max reads', args['max_reads'] or 'all'), ('threads', args['threads'])]
         if args.get('sam'):
-            shown += [('alignments', 'snps/temp/genomes.sam (bowtie2 -S; no samtools)')]
+            shown += [('alignments', '%s (bowtie2 -S; no samtools)' % ('snps/temp/genomes.sam' if program == 'snps' else 'genes/temp/pangenomes.sam'))]
     if last[1]:
         shown += [(k, args[k]) for k in ('mapid', 'mapq', 'baseq', 'readq', 'aln_cov', 'trim') if k in args]
     text = "=== run_midas.py %s (MI355X) ===\n" % program + ''.join("%-18s %s\n" % (k + ':', v) for k, v in shown) + "===\n"
@@ -290,6 +292,8 @@ summary.txt                   per species: pangenome_size, covered_genes, fracti
                               genes), marker_coverage, aligned_reads, mapped_reads
 log.txt                       parameters and external commands of this run
 temp/                         pangenomes.fa, bowtie2 index, pangenomes.bam (deleted by --remove_temp)
+                              with --sam: pangenomes.sam, bowtie2's own output, in the BAM's place; --call_genes parses it
+                              on the GPU, in the order of its lines, when there is no pangenomes.bam
 
 Reads counted: identity >= --mapid, mean quality >= --readq, mapping quality >= --mapq, aligned fraction >= --aln_cov.
 Next step: merge_midas.py genes.
