@@ -906,6 +906,51 @@ int32_t midas_genes_compare_write_pairs(const char* path, const midas_genes_matr
                                         int64_t n_rows, const int64_t* count, const double* both, const double* either, const double* dist,
                                         char* err1024);
 
+/* ---- run_species.py: the aligner's m8 lines classified (midas/run/species.py:51-119) -----------------------------------------
+ * midas_species_classify: `text` (host memory) is the whole alignments.m8; it goes to the device chunk_bytes at a time and stays
+ *   there.  A line's fields are its runs of non-blanks; query, target, pid (float), aln (int), score (float, field 12) are used and
+ *   qlen = int() of the query's text after its last '_'.  pid and score are float() of their text, bit for bit: decoded on the
+ *   device when the literal has at most 15 significant digits and a decimal exponent within +-22, by the host's parser
+ *   otherwise.  The marker genes are gene_names[gene_name_off[g], gene_name_off[g + 1]) with their species and marker family
+ *   (indices); a line passes unless pid < marker_cutoff[family] or (double)aln / qlen < aln_cov.  Per query (equal names, wherever
+ *   the lines stand) the best hits are the passing lines whose score equals the query's maximum.  One best hit: out_uniq_reads /
+ *   out_uniq_aln [n_species] take the read and its aln.  More: the query enters the result's CSR -- queries in the order of their
+ *   first passing line, hits (species, aln) in line order -- for midas_species_assign.
+ *   MIDAS_SNPS_ERR_BAD_LAYOUT with the 1-based number of the EARLIEST bad line in out_stats16[5] and the reason in [4]: 1 fewer
+ *   than 12 fields, 2 a target that is no marker gene, 3 no usable qlen (zero included), 4 aln is no integer, 5 pid or score is no
+ *   number, 6 the family's cutoff is nan (none given), 7 the score is nan.  aln and qlen beyond 32 bits are reasons 4 and 3.
+ *   MIDAS_SNPS_ERR_UNSUPPORTED: a text beyond 4 GiB or 2^31 lines.
+ *   iparams4 = chunk_bytes (0: 64 MiB; rounded up to 16), hash_bits (0 or 64: the whole hash of the query name; fewer, for tests,
+ *   makes different names share a sort key -- the results do not change), dump (tests: the result keeps every line's decoded
+ *   values for midas_species_result_lines), 0.  out_stats16: [0] lines, [1] passing lines, [2] unique reads, [3] ambiguous reads,
+ *   [6] cells the host parsed, [7] chunks, [8] chunk_bytes in use, [9] hits of the ambiguous reads.  out_ms8 (nullable, host
+ *   clock): upload, line index, fields, lookup, filter + sort + group, best hits, download.
+ * midas_species_result_columns: indptr [ambiguous + 1], species and aln [hits].  _lines: per line pid, score, aln, qlen, species,
+ *   marker (-1: no marker gene) and pass.
+ * midas_species_assign (host only): the ambiguous reads given out one after another.  For a read with hits h_0..h_{k-1}:
+ *   counts[i] = inout_reads[species of h_i]; all zero: index below k from getrandbits(k.bit_length()) of the first generator,
+ *   redrawn until it is (random.sample(ids, 1)); else numpy's legacy choice with p = counts / sum: cdf = cumsum(p) / its last,
+ *   u = ((a >> 5) * 2^26 + (b >> 6)) / 2^53 of two words of the second generator, the index is the number of cdf entries <= u.
+ *   The drawn species gets the read and the aln of its FIRST hit in the list.  Both generators are MT19937: 624 words and the
+ *   position (random.getstate()[1], np.random.get_state()[1:3]).  out_draws2 (nullable): words drawn from the first generator,
+ *   doubles from the second.
+ * midas_species_parse_number (tests): kind 0 float() -> double, 1 int() -> int64, as the classify step takes a field;
+ *   *out_fast: the device's own decoder took it.                                                                              */
+typedef struct midas_species_result midas_species_result;
+int32_t midas_species_classify(midas_snps_ctx* ctx, const char* text, int64_t text_bytes, int32_t n_genes, const char* gene_names,
+                               const int64_t* gene_name_off, const int32_t* gene_species, const int32_t* gene_marker, int32_t n_species,
+                               int32_t n_markers, const double* marker_cutoff, double aln_cov, const int64_t* iparams4,
+                               int64_t* out_uniq_reads, int64_t* out_uniq_aln, int64_t* out_stats16, float* out_ms8,
+                               midas_species_result** out_result);
+int32_t midas_species_result_columns(const midas_species_result* r, int64_t* indptr, int32_t* species, int32_t* aln);
+int32_t midas_species_result_lines(const midas_species_result* r, double* pid, double* score, int32_t* aln, int32_t* qlen, int32_t* species,
+                                   int32_t* marker, uint8_t* pass);
+void midas_species_result_close(midas_species_result* r);
+int32_t midas_species_assign(int64_t n_queries, const int64_t* indptr, const int32_t* hit_species, const int32_t* hit_aln, int32_t n_species,
+                             const uint32_t* py_state624, int32_t py_pos, const uint32_t* np_state624, int32_t np_pos, int64_t* inout_reads,
+                             int64_t* inout_aln, int64_t* out_draws2);
+int32_t midas_species_parse_number(int32_t kind, const char* text, int64_t n, void* out, int32_t* out_fast);
+
 /* ---- the exchange between ranks (comm.cpp): RCCL itself, no process group ------------------------------------------------
  * One process per GPU; the only thing ranks exchange on this path is the per-species summary rows -- the reference's pool
  * workers return (species_id, aln_stats) through a pipe, midas/run/snps.py:225-241, midas/utility.py:81-107 -- plus, on the

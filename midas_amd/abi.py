@@ -367,6 +367,12 @@ def load_library(build_if_missing: bool = True):
         'midas_genes_compare_parse_cell': (i32, [C.c_char_p, i64, C.POINTER(C.c_double), C.POINTER(i32)]),
         'midas_genes_compare': (i32, [vp, vp, i64, i64, i32, i32, i32, i32, C.c_double] + [vp] * 9),
         'midas_genes_compare_write_pairs': (i32, [C.c_char_p, vp, i32, i32, i32, i64, vp, vp, vp, vp, C.c_char_p]),
+        'midas_species_classify': (i32, [vp, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp, C.POINTER(vp)]),
+        'midas_species_result_columns': (i32, [vp, vp, vp, vp]),
+        'midas_species_result_lines': (i32, [vp] * 8),
+        'midas_species_result_close': (None, [vp]),
+        'midas_species_assign': (i32, [i64, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp]),
+        'midas_species_parse_number': (i32, [i32, C.c_char_p, i64, vp, C.POINTER(i32)]),
     })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing: fail loudly
@@ -415,6 +421,50 @@ EXPORTED_SYMBOLS = [
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
                  'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_id_markers', 'midas_sites_track_markers',
                  'midas_sites_write_markers', 'midas_sites_write_pairs']
+
+
+# run_species.py (the m8 classify step and the serial assignment): bound above like the rest, listed by themselves
+SPECIES_SYMBOLS = ['midas_species_classify', 'midas_species_result_columns', 'midas_species_result_lines', 'midas_species_result_close',
+                   'midas_species_assign', 'midas_species_parse_number']
+SPECIES_PHASES = ('upload', 'line index', 'fields', 'lookup', 'filter + sort + group', 'best hits', 'download')
+SPECIES_REASONS = {1: 'fields', 2: 'target', 3: 'qlen', 4: 'aln', 5: 'number', 6: 'cutoff', 7: 'score nan'}
+
+
+def species_parse_number(text: bytes, kind: str = 'float'):
+    """float() / int() of an m8 field as the classify step takes it (midas_species_parse_number) -> (value, decoded by the
+    device's own decoder), or None when it is no number."""
+    lib = load_library()
+    fast = C.c_int32(0)
+    out = C.c_double(0) if kind == 'float' else C.c_int64(0)
+    if lib.midas_species_parse_number(0 if kind == 'float' else 1, text, len(text), C.byref(out), C.byref(fast)) != 0:
+        return None
+    return out.value, bool(fast.value)
+
+
+def mt_states(py_state=None, np_state=None):
+    """(624 words, position) of Python's and numpy's global generators, or of the given random.getstate() /
+    np.random.get_state() values."""
+    import random
+    ps = py_state if py_state is not None else random.getstate()
+    ns = np_state if np_state is not None else np.random.get_state()
+    return (np.array(ps[1][:624], np.uint32), int(ps[1][624])), (np.ascontiguousarray(ns[1], np.uint32), int(ns[2]))
+
+
+def species_assign(indptr, hit_species, hit_aln, reads, aln, py_state=None, np_state=None):
+    """midas_species_assign(): the ambiguous reads of Context.species_classify given out in order, starting from the per-species
+    `reads` and `aln` sums of the unique reads -> (reads, aln, (words drawn from Python's generator, doubles from numpy's)).
+    Needs no device.  The generators' states are read, not advanced."""
+    lib = load_library()
+    (pw, pp), (nw, npos) = mt_states(py_state, np_state)
+    ip = np.ascontiguousarray(indptr, np.int64)
+    hs, ha = np.ascontiguousarray(hit_species, np.int32), np.ascontiguousarray(hit_aln, np.int32)
+    r, a = np.array(reads, np.int64), np.array(aln, np.int64)
+    draws = np.zeros(2, np.int64)
+    p = lambda x: x.ctypes.data_as(C.c_void_p) if x.size else None
+    st = lib.midas_species_assign(ip.size - 1, p(ip), p(hs), p(ha), r.size, p(pw), pp, p(nw), npos, p(r), p(a), p(draws))
+    if st != 0:
+        raise MidasSnpsError(st, "midas_species_assign: " + lib.midas_snps_status_string(st).decode())
+    return r, a, (int(draws[0]), int(draws[1]))
 
 
 # the SAM decode (run_midas.py snps --sam, genes --sam): bound above like the rest, listed by themselves
@@ -1638,6 +1688,48 @@ class Context:
                    either=either, dist=dist)
         if dump:
             out['cells'] = cells[:, :n]
+        return out
+
+    def species_classify(self, text, gene_names, gene_species, gene_marker, n_species: int, marker_cutoff, aln_cov: float,
+                         chunk_bytes: int = 0, hash_bits: int = 0, dump: bool = False):
+        """midas_species_classify(): the lines of alignments.m8 (bytes or a uint8 array) against the marker genes gene_names
+        (list of bytes) with their species / marker-family indices.  -> dict(lines, passing, unique, ambiguous, uniq_reads and
+        uniq_aln int64 [n_species], indptr int64 [ambiguous + 1], hit_species and hit_aln int32, side_cells, chunks, chunk_bytes,
+        ms [8]; with dump: pid, score f64 and aln, qlen, species, marker int32 and passed uint8 per line).  A bad line raises
+        MidasSnpsError with .bad = (reason, 1-based line), the earliest one of the file."""
+        tx = np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        names = np.frombuffer(b''.join(gene_names), np.uint8)
+        off = np.zeros(len(gene_names) + 1, np.int64)
+        np.cumsum([len(g) for g in gene_names], out=off[1:])
+        gs, gm = np.ascontiguousarray(gene_species, np.int32), np.ascontiguousarray(gene_marker, np.int32)
+        cut = np.ascontiguousarray(marker_cutoff, np.float64)
+        S = int(n_species)
+        ur, ua = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        ip = np.array([chunk_bytes, hash_bits, 1 if dump else 0, 0], np.int64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        res = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_species_classify(self._h, p(tx), tx.size, len(gene_names), p(names), p(off), p(gs), p(gm), S, cut.size, p(cut),
+                                              float(aln_cov), p(ip), p(ur), p(ua), p(stats), p(ms), C.byref(res))
+        if st != 0:
+            try:
+                self._check(st)
+            except MidasSnpsError as e:
+                e.bad = (int(stats[4]), int(stats[5])) if stats[4] else None
+                raise
+        try:
+            n, n_amb, n_hits = int(stats[0]), int(stats[3]), int(stats[9])
+            indptr, hs, ha = np.zeros(n_amb + 1, np.int64), np.zeros(n_hits, np.int32), np.zeros(n_hits, np.int32)
+            self._check(self._lib.midas_species_result_columns(res, p(indptr), p(hs), p(ha)))
+            out = dict(lines=n, passing=int(stats[1]), unique=int(stats[2]), ambiguous=n_amb, uniq_reads=ur, uniq_aln=ua, indptr=indptr,
+                       hit_species=hs, hit_aln=ha, side_cells=int(stats[6]), chunks=int(stats[7]), chunk_bytes=int(stats[8]), ms=ms.tolist())
+            if dump:
+                cols = dict(pid=np.zeros(n, np.float64), score=np.zeros(n, np.float64), aln=np.zeros(n, np.int32), qlen=np.zeros(n, np.int32),
+                            species=np.zeros(n, np.int32), marker=np.zeros(n, np.int32), passed=np.zeros(n, np.uint8))
+                self._check(self._lib.midas_species_result_lines(res, *[p(cols[k]) for k in ('pid', 'score', 'aln', 'qlen', 'species', 'marker', 'passed')]))
+                out.update(cols)
+        finally:
+            self._lib.midas_species_result_close(res)
         return out
 
     def batch(self, contigs: ContigTable, reads: ReadsSoA) -> "Batch":

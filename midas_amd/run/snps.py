@@ -100,17 +100,55 @@ def _reference_bytes(parts):
     return np.frombuffer(b''.join(c.seq_bytes[lo:hi] for c, lo, hi in parts), dtype=np.uint8)
 
 
+def read_abundance(path):
+    """species/species_profile.txt -> [(species_id, coverage, relative_abundance)] in the order of its rows."""
+    if not os.path.isfile(path):
+        sys.exit("\nCould not locate species profile: %s\nTry rerunning with run_species.py" % path)
+    rows = []
+    with open(path) as handle:
+        fields = next(handle).rstrip('\n').split('\t')
+        for line in handle:
+            values = line.rstrip('\n').split('\t')
+            if len(values) == len(fields):
+                r = dict(zip(fields, values))
+                rows.append((r['species_id'], float(r['coverage']), float(r['relative_abundance'])))
+    return rows
+
+
 def select_species(args, per_species='rep_genomes'):
-    """Only --species_id can be honoured here: --species_cov / --species_topn read the abundance profile written by
-    `run_midas.py species` (midas/run/species.py:191-227), a pipeline outside this build."""
+    """The species to map to (midas/run/species.py:191-227): those of the profile with coverage >= --species_cov, the
+    --species_topn most abundant, the --species_id given -- whichever were asked for, intersected -- without the ids of
+    <db>/exclude.txt.  The reference's order is a set's; here it is the order of the profile's rows (--species_id alone: as
+    given)."""
     wanted = args.get('species_id')
-    if not wanted:
-        sys.exit("\nError: this build only selects species with --species_id "
-                 "(--species_cov/--species_topn need `run_midas.py species`, which is out of scope)\n")
-    for sp in wanted:
+    chosen = None
+    if args.get('species_topn') or args.get('species_cov'):
+        rows = read_abundance(os.path.join(args['outdir'], 'species', 'species_profile.txt'))
+        keep = set(r[0] for r in rows)
+        if args.get('species_cov'):
+            keep &= set(r[0] for r in rows if r[1] >= args['species_cov'])
+        if args.get('species_topn'):
+            keep &= set(r[0] for r in sorted(rows, key=lambda r: r[2], reverse=True)[:args['species_topn']])
+        if wanted:
+            keep &= set(wanted)
+        chosen = [r[0] for r in rows if r[0] in keep]
+    elif wanted:
+        chosen = list(wanted)
+    else:
+        sys.exit("\nError: no species sastisfied your selection criteria. \n")
+    exclude = os.path.join(args['db'], 'exclude.txt')
+    from_profile = bool(args.get('species_topn') or args.get('species_cov'))     # (--species_id alone: taken as given, as before)
+    if from_profile and os.path.isfile(exclude):
+        with open(exclude) as handle:
+            for line in handle:
+                if line.rstrip() in chosen:
+                    chosen.remove(line.rstrip())
+    if len(chosen) == 0:
+        sys.exit("\nError: no species sastisfied your selection criteria. \n")
+    for sp in chosen:
         if not os.path.isdir(os.path.join(args['db'], per_species, sp)):
             sys.exit("\nError: Species id not found in database: %s\n" % sp)
-    return list(wanted)
+    return chosen
 
 
 def initialize_species(args):

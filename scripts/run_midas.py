@@ -36,8 +36,8 @@ OPTION_GROUPS = [
     ]),
     ("Which species (for --build_db)", [
         (['-d'], dict(dest='db', default=os.environ.get('MIDAS_DB'), help="MIDAS reference database (default: $MIDAS_DB)")),
-        (['--species_cov'], dict(type=float, metavar='FLOAT', help="species whose genome coverage exceeds this (3.0); needs `run_midas.py species` output")),
-        (['--species_topn'], dict(type=int, metavar='INT', help="the N most abundant species; needs `run_midas.py species` output")),
+        (['--species_cov'], dict(type=float, metavar='FLOAT', help="species whose genome coverage exceeds this (3.0); needs run_species.py's output")),
+        (['--species_topn'], dict(type=int, metavar='INT', help="the N most abundant species; needs run_species.py's output")),
         (['--species_id'], dict(metavar='ID[,ID...]', help="these species, comma separated")),
     ]),
     ("Reads and aligner (for --align)", [
@@ -106,7 +106,7 @@ def get_program():
               "         (pileup on the MI355X); `run_midas.py snps -h` lists the options\n"
               "  genes  reads, depth and copy number of every gene of the species' pangenomes (read filter and per-gene\n"
               "         sums on the MI355X); `run_midas.py genes -h` lists the options\n\n"
-              "species is not part of this build.")
+              "species is not a command of this script: scripts/run_species.py OUT [options] serves it.")
         sys.exit(0)
     if word == 'species':
         die("'%s' is not part of this build (only the snps and genes paths are)" % word)
@@ -201,7 +201,7 @@ def check_arguments(program, args):
     profile = os.path.join(args['outdir'], 'species', 'species_profile.txt')
     if args['build_db'] and (args['species_topn'] or args['species_cov']) and not os.path.isfile(profile):
         die("Could not find species abundance profile: %s\n"
-            "--species_topn / --species_cov need the output of `run_midas.py species`; use --species_id otherwise" % profile)
+            "--species_topn / --species_cov need the output of run_species.py; use --species_id otherwise" % profile)
     have_fa, have_bam = (os.path.isfile(os.path.join(temp, f)) for f in (fa_name, bam_name))
     if not have_bam:       # (--sam: the aligner's text stands in for the BAM)
         have_bam = os.path.isfile(os.path.join(temp, 'genomes.sam' if program == 'snps' else 'pangenomes.sam'))
