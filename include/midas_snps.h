@@ -951,6 +951,39 @@ int32_t midas_species_assign(int64_t n_queries, const int64_t* indptr, const int
                              int64_t* inout_aln, int64_t* out_draws2);
 int32_t midas_species_parse_number(int32_t kind, const char* text, int64_t n, void* out, int32_t* out_fast);
 
+/* ---- merge_species.py: the samples' species profiles merged (midas/merge/species.py:28-88) ---------------------------------------
+ * midas_species_merge: profile_paths[s] is sample s's species/species_profile.txt; the library reads the files itself (host
+ *   threads, groups of whole files of at most chunk_bytes of text, a larger file by itself), parses them on the device and keeps
+ *   only the three [species][sample] matrices resident.  The species are species_ids[species_id_off[g], species_id_off[g + 1]),
+ *   distinct, in the row order of species_info.txt.  A profile's header names its columns (species_id, count_reads, coverage,
+ *   relative_abundance, anywhere; others are ignored); a line with another number of tab-separated fields than the header is
+ *   skipped; cells are float() / int() of the field.  Per species over the samples in order: np.mean (pairwise add-reduce, one
+ *   divide) and np.median of coverage and of relative abundance, each also as round(x, 2) of a numpy double (rint(x * 100) / 100),
+ *   prevalence = samples with coverage >= sample_depth, and the species' place in a stable descending sort by prevalence.
+ *   iparams4: chunk_bytes (0: 256 MiB), lds_bound (rows of at most this many samples are sorted in LDS, longer ones by the radix
+ *   sort; 0 and anything above: 4096), host threads (0: the CPU budget), 0.
+ *   out_stats16: [0] lines, [1] groups, [2] chunk_bytes, [3] cells the host's parser converted, [8] 1 = LDS rows, [9] lds_bound,
+ *   [11] bytes of text; after MIDAS_SNPS_ERR_BAD_LAYOUT (the message names file, line and species or column; it is the earliest
+ *   such line in the order of samples, then lines, a species without a line counting behind its profile's last line):
+ *   [4] reason (1-4 the header lacks species_id / count_reads / coverage / relative_abundance, 5 species not in species_ids,
+ *   6 species twice, 7-9 count_reads / coverage / relative_abundance does not convert, 10-11 coverage / relative_abundance not
+ *   finite, 12 count_reads beyond int64, 13 a species without a line), [5] sample, [6] 1-based line, [7] species (reason 13).
+ *   out_ms8: waiting for the readers, upload, index, fields, lookup + scatter, statistics, download.
+ * _result_matrices: coverage, abundance (fp64) and reads (int64), each [n_species][n_samples].  _result_stats: stats8
+ *   [8][n_species] = mean_coverage, median_coverage, mean_abundance, median_abundance, then the same four rounded; prevalence
+ *   [n_species]; order [n_species] = the species of every row of species_prevalence.txt.
+ * _result_write (host only): relative_abundance.txt, coverage.txt, count_reads.txt (header_line first, then a row a species:
+ *   its id and str() of every cell) and species_prevalence.txt into outdir.                                                        */
+typedef struct midas_species_merge_result midas_species_merge_result;
+int32_t midas_species_merge(midas_snps_ctx* ctx, int32_t n_samples, const char* const* profile_paths, int32_t n_species, const char* species_ids,
+                            const int64_t* species_id_off, double sample_depth, const int64_t* iparams4, int64_t* out_stats16, float* out_ms8,
+                            midas_species_merge_result** out_result);
+int32_t midas_species_merge_result_matrices(const midas_species_merge_result* r, double* coverage, double* abundance, int64_t* reads);
+int32_t midas_species_merge_result_stats(const midas_species_merge_result* r, double* stats8, int64_t* prevalence, int32_t* order);
+int32_t midas_species_merge_result_write(const midas_species_merge_result* r, const char* outdir, const char* header_line, int32_t threads,
+                                         char* err1024);
+void midas_species_merge_result_close(midas_species_merge_result* r);
+
 /* ---- the exchange between ranks (comm.cpp): RCCL itself, no process group ------------------------------------------------
  * One process per GPU; the only thing ranks exchange on this path is the per-species summary rows -- the reference's pool
  * workers return (species_id, aln_stats) through a pipe, midas/run/snps.py:225-241, midas/utility.py:81-107 -- plus, on the

@@ -373,6 +373,11 @@ def load_library(build_if_missing: bool = True):
         'midas_species_result_close': (None, [vp]),
         'midas_species_assign': (i32, [i64, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp]),
         'midas_species_parse_number': (i32, [i32, C.c_char_p, i64, vp, C.POINTER(i32)]),
+        'midas_species_merge': (i32, [vp, i32, vp, i32, vp, vp, C.c_double, vp, vp, vp, C.POINTER(vp)]),
+        'midas_species_merge_result_matrices': (i32, [vp, vp, vp, vp]),
+        'midas_species_merge_result_stats': (i32, [vp, vp, vp, vp]),
+        'midas_species_merge_result_write': (i32, [vp, C.c_char_p, C.c_char_p, i32, C.c_char_p]),
+        'midas_species_merge_result_close': (None, [vp]),
     })
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing: fail loudly
@@ -428,6 +433,14 @@ SPECIES_SYMBOLS = ['midas_species_classify', 'midas_species_result_columns', 'mi
                    'midas_species_assign', 'midas_species_parse_number']
 SPECIES_PHASES = ('upload', 'line index', 'fields', 'lookup', 'filter + sort + group', 'best hits', 'download')
 SPECIES_REASONS = {1: 'fields', 2: 'target', 3: 'qlen', 4: 'aln', 5: 'number', 6: 'cutoff', 7: 'score nan'}
+# merge_species.py (the species profiles merged): bound above like the rest, listed by themselves
+SPECIES_MERGE_SYMBOLS = ['midas_species_merge', 'midas_species_merge_result_matrices', 'midas_species_merge_result_stats',
+                         'midas_species_merge_result_write', 'midas_species_merge_result_close']
+SPECIES_MERGE_PHASES = ('read (wait)', 'upload', 'index', 'fields', 'lookup + scatter', 'statistics', 'download')
+SPECIES_MERGE_REASONS = {1: 'header species_id', 2: 'header count_reads', 3: 'header coverage', 4: 'header relative_abundance', 5: 'unknown species',
+                         6: 'species twice', 7: 'cell count_reads', 8: 'cell coverage', 9: 'cell relative_abundance', 10: 'non-finite coverage',
+                         11: 'non-finite relative_abundance', 12: 'count_reads range', 13: 'species missing'}
+SPECIES_MERGE_STATS = ('mean_coverage', 'median_coverage', 'mean_abundance', 'median_abundance')
 
 
 def species_parse_number(text: bytes, kind: str = 'float'):
@@ -1732,8 +1745,84 @@ class Context:
             self._lib.midas_species_result_close(res)
         return out
 
+    def species_merge(self, profile_paths, species_ids, sample_depth: float = 1.0, chunk_bytes: int = 0, lds_bound: int = 0, threads: int = 0):
+        """midas_species_merge(): the samples' species_profile.txt files (paths, in sample order) against the species ids of
+        species_info.txt (distinct, in row order).  -> SpeciesMerge: coverage, abundance fp64 and reads int64 [species][sample]; per
+        species mean_coverage, median_coverage, mean_abundance, median_abundance and rounded[...] of each, prevalence, order (the
+        species of every row of species_prevalence.txt); lines, groups, chunk_bytes, side_cells, lds_rows, ms [8]; .write(outdir,
+        sample_ids) writes the four files.  A bad profile raises MidasSnpsError naming file, line and species or column, with
+        .bad = (reason, sample, 1-based line): the earliest one in the order of samples, then lines."""
+        paths = [os.fsencode(q) for q in profile_paths]
+        ids = [s.encode() if isinstance(s, str) else bytes(s) for s in species_ids]
+        arr = (C.c_char_p * len(paths))(*paths)
+        names = np.frombuffer(b''.join(ids), np.uint8)
+        off = np.zeros(len(ids) + 1, np.int64)
+        np.cumsum([len(g) for g in ids], out=off[1:])
+        if names.size == 0:
+            names = np.zeros(1, np.uint8)
+        ip = np.array([chunk_bytes, lds_bound, threads, 0], np.int64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        res = C.c_void_p()
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        st = self._lib.midas_species_merge(self._h, len(paths), C.cast(arr, C.c_void_p), len(ids), p(names), p(off), float(sample_depth), p(ip), p(stats),
+                                           p(ms), C.byref(res))
+        if st != 0:
+            try:
+                self._check(st)
+            except MidasSnpsError as e:
+                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
+                raise
+        return SpeciesMerge(self._lib, res, len(ids), len(paths), stats, ms)
+
     def batch(self, contigs: ContigTable, reads: ReadsSoA) -> "Batch":
         return Batch(self, contigs, reads)
+
+
+class SpeciesMerge:
+    """What Context.species_merge returns: the matrices and the per-species numbers as arrays, and the writer of the four files."""
+
+    def __init__(self, lib, handle, n_species, n_samples, stats, ms):
+        self._lib, self._h = lib, handle
+        R, S = n_species, n_samples
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        try:
+            self.coverage, self.abundance, self.reads = np.zeros((R, S), np.float64), np.zeros((R, S), np.float64), np.zeros((R, S), np.int64)
+            st8, self.prevalence, self.order = np.zeros((8, R), np.float64), np.zeros(R, np.int64), np.zeros(R, np.int32)
+            for st in (lib.midas_species_merge_result_matrices(handle, p(self.coverage), p(self.abundance), p(self.reads)),
+                       lib.midas_species_merge_result_stats(handle, p(st8), p(self.prevalence), p(self.order))):
+                if st != 0:
+                    raise MidasSnpsError(st, "midas_species_merge_result: " + lib.midas_snps_status_string(st).decode())
+        except Exception:
+            self.close()
+            raise
+        self.rounded = {}
+        for k, name in enumerate(SPECIES_MERGE_STATS):
+            setattr(self, name, st8[k])
+            self.rounded[name] = st8[4 + k]
+        self.lines, self.groups, self.chunk_bytes, self.side_cells = int(stats[0]), int(stats[1]), int(stats[2]), int(stats[3])
+        self.lds_rows, self.text_bytes, self.ms = bool(stats[8]), int(stats[11]), ms.tolist()
+
+    def write(self, outdir, sample_ids, threads: int = 0):
+        """relative_abundance.txt, coverage.txt, count_reads.txt and species_prevalence.txt into outdir."""
+        err = C.create_string_buffer(1024)
+        header = '\t'.join(['species_id'] + list(sample_ids)) + '\n'
+        st = self._lib.midas_species_merge_result_write(self._h, os.fsencode(outdir), header.encode(), threads, err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode() or "midas_species_merge_result_write failed")
+
+    def close(self):
+        if self._h:
+            self._lib.midas_species_merge_result_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
 
 
 class Comm:

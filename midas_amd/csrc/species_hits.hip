@@ -69,54 +69,6 @@ __host__ __device__ inline unsigned long long sp_hash(const char* s, uint32_t n)
   return sp_mix(h);
 }
 
-// float(text) when the literal is [sign] digits [. digits] [e [sign] digits] with at most 15 significant digits and a decimal
-// exponent within +-22: the digits are an exact integer below 2^53 and 10^|e| is exact, so one multiply or divide rounds once
-__host__ __device__ inline bool sp_f64_fast(const char* s, uint32_t n, double* out) {
-  const double p10[23] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};
-  uint32_t i = 0;
-  bool neg = false;
-  if (i < n && (s[i] == '+' || s[i] == '-')) { neg = s[i] == '-'; ++i; }
-  unsigned long long m = 0;
-  int sig = 0, digits = 0, frac = 0;
-  bool dot = false;
-  for (; i < n; ++i) {
-    const char c = s[i];
-    if (c >= '0' && c <= '9') {
-      ++digits;
-      if (sig > 0 || c != '0') ++sig;
-      if (sig > 15) return false;
-      m = m * 10 + (unsigned)(c - '0');
-      if (dot) ++frac;
-    } else if (c == '.' && !dot) {
-      dot = true;
-    } else {
-      break;
-    }
-  }
-  if (digits == 0 || frac > 400) return false;
-  int ex = 0;
-  if (i < n) {
-    if (s[i] != 'e' && s[i] != 'E') return false;
-    ++i;
-    bool eneg = false;
-    if (i < n && (s[i] == '+' || s[i] == '-')) { eneg = s[i] == '-'; ++i; }
-    if (i >= n || n - i > 3) return false;
-    for (; i < n; ++i) {
-      if (s[i] < '0' || s[i] > '9') return false;
-      ex = ex * 10 + (s[i] - '0');
-    }
-    if (eneg) ex = -ex;
-  }
-  const int e10 = ex - frac;
-  double v = (double)m;
-  if (m != 0) {
-    if (e10 < -22 || e10 > 22) return false;
-    v = e10 >= 0 ? v * p10[e10] : v / p10[-e10];
-  }
-  *out = neg ? -v : v;
-  return true;
-}
-
 // int(text) for [sign] and up to nine digits
 __host__ __device__ inline bool sp_i32_fast(const char* s, uint32_t n, int32_t* out) {
   uint32_t i = 0;

@@ -4,7 +4,7 @@
 Drop-in for the `snps` and `genes` commands of the reference's scripts/merge_midas.py: same positional arguments, option
 names, defaults, presets and output files (<outdir>/<species>/snps_{info,freq,depth,summary}.txt, readme.txt;
 <outdir>/<species>/genes_{presabs,copynum,depth,reads,summary}.txt, readme.txt).  The option semantics are the
-reference's (scripts/merge_midas.py:84-146, 148-281); the `species` merge is not part of this build.  Under
+reference's (scripts/merge_midas.py:84-146, 148-281); the `species` merge is scripts/merge_species.py.  Under
 torch.distributed.run the species are dealt to the ranks (one GPU each).
 """
 
@@ -72,7 +72,7 @@ def get_program():
               "         freq/depth/info matrices (site arithmetic on the MI355X); `merge_midas.py snps -h` for options\n"
               "  genes  merge the per-sample gene tables of a species over its gene clusters, write the presence/absence,\n"
               "         copy-number, depth and read matrices (cluster sums on the MI355X); `merge_midas.py genes -h` for options\n\n"
-              "the species merge is not part of this build.")
+              "the species merge is a script of its own: merge_species.py OUT -i INPUT -t list|file|dir (`merge_species.py -h`).")
         sys.exit(0)
     if word == 'species':
         die("'%s' is not part of this build (only the snps and genes paths are)" % word)
@@ -169,7 +169,7 @@ def check_arguments(args):
         for d in args['indirs']:      # only listed directories are checked (scripts/merge_midas.py:320-331)
             if not os.path.isdir(d):
                 die("Specified input directory '%s' does not exist" % d)
-    if args.get('program') == 'genes':
+    if args.get('program') in ('genes', 'species'):       # (species: scripts/merge_species.py)
         for name in ('min_copy', 'sample_depth', 'max_samples'):       # scripts/merge_midas.py:295-298
             if args.get(name) and args[name] < 0:
                 die("--%s cannot be a negative value" % name)
