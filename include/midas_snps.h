@@ -259,6 +259,29 @@ int32_t midas_snps_set_pad_rule(midas_snps_ctx* ctx, int32_t rule);
  * file one rank writes.  The environment variable MIDAS_SNPS_ROW_CODER=host sets the default of new contexts.          */
 enum { MIDAS_SNPS_ROWS_DEVICE = 0, MIDAS_SNPS_ROWS_HOST = 1 };
 int32_t midas_snps_set_row_coder(midas_snps_ctx* ctx, int32_t coder);
+/* Who coded the parts midas_snps_batch_write_part has written on this context at the row coder's levels since it was created:
+ *   out3[0]  gzip members formatted and deflated by the kernel (counted when their part is in the file);
+ *   out3[1]  parts left to the host's formatter before the launch: a contig id longer than the kernel's 192 bytes;
+ *   out3[2]  parts left to it after the launch: a member came back with a status other than 0 (the arena was full).
+ * A part is one midas_snps_batch_write_part call.  midas_snps_rows_code counts nothing here (test aid; no reference counterpart). */
+int32_t midas_snps_row_coder_counts(const midas_snps_ctx* ctx, int64_t out3[3]);
+/* The row kernel's launch of midas_snps_batch_write_part on inputs of the caller's choosing: counts [n_sites * 4] and allele
+ * [n_sites] (any byte) go up, and member k -- rows site0[k] .. site0[k] + n_rows[k] - 1 of them, numbered from pos0[k], under the id
+ * ids[id_off[k], + id_len[k]) -- is handed to the kernel as given, a member the product never forms included (an id beyond 192
+ * bytes, no rows, more than 16 384): the kernel answers those with status 1.  Only what would read outside the arrays is refused
+ * here (MIDAS_SNPS_ERR_INVALID_ARG): sites of a member the kernel takes that are not in [0, n_sites), positions that pass 2^31 - 1,
+ * an id outside ids.  arena_bytes: the room for all streams together, 0 = the product's rule (10 bytes a row + 1 KiB a member +
+ * 4 KiB); grid_blocks: workgroups of the launch (never more than members), 0 = one per compute unit, as the product launches.
+ * Per member: out_status (0 coded; 1 not taken; 2 the arena was full), out_n_bytes, out_crc (CRC-32 of the member's text),
+ * out_text_len (status 0 and 2), out_arena_off (where its stream lay in the arena; -1 unless status 0).  The raw DEFLATE streams
+ * of the members with status 0 follow one another, in the members' order, in out_streams[0, *out_stream_bytes);
+ * MIDAS_SNPS_ERR_INVALID_ARG when out_cap is too small (the arena's size always suffices).  Same code as the product's path
+ * from the upload of the members to the streams' way down (test aid; no reference counterpart).                          */
+int32_t midas_snps_rows_code(midas_snps_ctx* ctx, int64_t n_sites, const uint32_t* counts, const uint8_t* allele, int32_t n_members,
+                             const int64_t* site0, const int64_t* pos0, const int32_t* n_rows, const int32_t* id_off,
+                             const int32_t* id_len, const uint8_t* ids, int64_t ids_bytes, int64_t arena_bytes, int32_t grid_blocks,
+                             uint32_t* out_status, uint32_t* out_n_bytes, uint32_t* out_crc, uint32_t* out_text_len,
+                             int64_t* out_arena_off, uint8_t* out_streams, int64_t out_cap, int64_t* out_stream_bytes);
 /* Re-run the device packer over the batch's resident BAM-native arrays (the arrays batch_create uploaded, unchanged):
  * per read the CIGAR walk into gap-free match segments (pysam get_aligned_pairs(matches_only=True), reached from
  * midas/run/snps.py:194-199), the clip structure (query_alignment_sequence, :145), floor(mean(query_qualities))

@@ -265,6 +265,8 @@ def load_library(build_if_missing: bool = True):
         'midas_snps_stream_rates': (i32, [vp, i64, i32, C.POINTER(C.c_double)]),
         'midas_snps_calibration_pass': (i32, [vp, i64]),
         'midas_snps_set_row_coder': (i32, [vp, i32]),
+        'midas_snps_row_coder_counts': (i32, [vp, vp]),
+        'midas_snps_rows_code': (i32, [vp, i64, vp, vp, i32] + [vp] * 6 + [i64, i64, i32] + [vp] * 6 + [i64, C.POINTER(i64)]),
         'midas_snps_copy_rate': (i32, [vp, i64, i32, C.POINTER(C.c_double)]),
         'midas_snps_batch_fetch_packed': (i32, [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]),
         'midas_snps_batch_pack_timing': (i32, [vp, i32, C.POINTER(C.c_float)]),
@@ -399,6 +401,7 @@ EXPORTED_SYMBOLS = [
     'midas_snps_batch_enable_timing', 'midas_snps_batch_timing', 'midas_snps_batch_time_pileup_only',
     'midas_snps_batch_stats_to_device', 'midas_snps_batch_pack', 'midas_snps_batch_fetch_packed',
     'midas_snps_batch_select_path', 'midas_snps_set_default_path', 'midas_snps_copy_rate', 'midas_snps_stream_rates', 'midas_snps_calibration_pass', 'midas_snps_set_pad_rule', 'midas_snps_set_row_coder',
+    'midas_snps_row_coder_counts', 'midas_snps_rows_code',
     'midas_snps_batch_pack_timing',
     'midas_bam_open', 'midas_bam_close', 'midas_bam_write', 'midas_bam_n_refs', 'midas_bam_ref', 'midas_bam_load', 'midas_bam_copy', 'midas_bam_columns',
     'midas_bam_open_slice', 'midas_bam_slice_facts', 'midas_bam_slice_marks', 'midas_bam_load_ranges',
@@ -1395,6 +1398,47 @@ class Context:
         """ROWS_DEVICE (default): Batch.write_part formats and deflates the rows in a kernel; ROWS_HOST: the host's
         formatter threads do (the file then equals write_table's byte for byte).  Same text either way."""
         self._check(self._lib.midas_snps_set_row_coder(self._h, int(coder)))
+
+    def row_coder_counts(self):
+        """Who coded the parts Batch.write_part wrote on this context (midas_snps_row_coder_counts): members coded by the kernel,
+        parts left to the host's formatter for a contig id beyond 192 bytes, parts left to it for a member the kernel declined."""
+        out = np.zeros(3, np.int64)
+        self._check(self._lib.midas_snps_row_coder_counts(self._h, out.ctypes.data_as(C.c_void_p)))
+        return {"members_on_device": int(out[0]), "parts_declined_id": int(out[1]), "parts_declined_status": int(out[2])}
+
+    def rows_code(self, counts, allele, members, arena_bytes: int = 0, grid_blocks: int = 0):
+        """The row kernel's launch of Batch.write_part on chosen inputs (midas_snps_rows_code).  counts [n_sites, 4] uint32,
+        allele [n_sites] uint8 (any byte), members: (site0, pos0, n_rows, id bytes) each, handed to the kernel as given;
+        arena_bytes 0: the product's rule, grid_blocks 0: one workgroup per compute unit.
+        -> one dict per member: status, n_bytes, crc, text_len, arena_off, stream (bytes; None unless status 0)."""
+        counts = np.ascontiguousarray(counts, np.uint32).reshape(-1, 4)
+        allele = np.ascontiguousarray(allele, np.uint8).reshape(-1)
+        n = len(members)
+        site0 = np.array([m[0] for m in members], np.int64)
+        pos0 = np.array([m[1] for m in members], np.int64)
+        n_rows = np.array([m[2] for m in members], np.int32)
+        id_len = np.array([len(m[3]) for m in members], np.int32)
+        id_off = (np.cumsum(id_len, dtype=np.int64) - id_len).astype(np.int32)
+        ids = np.frombuffer(b"".join(bytes(m[3]) for m in members) + b"\0", np.uint8)
+        rows = int(np.clip(n_rows.astype(np.int64), 0, 16384).sum())
+        cap = int(arena_bytes) if arena_bytes else rows * 10 + n * 1024 + 4096
+        st_, nb, crc, tl = (np.zeros(max(n, 1), np.uint32) for _ in range(4))
+        off = np.zeros(max(n, 1), np.int64)
+        streams = np.zeros(cap + 16, np.uint8)
+        got = C.c_int64(0)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.midas_snps_rows_code(self._h, allele.size, p(counts), p(allele), n, p(site0), p(pos0), p(n_rows), p(id_off),
+                                                   p(id_len), p(ids), ids.size - 1, int(arena_bytes), int(grid_blocks), p(st_), p(nb),
+                                                   p(crc), p(tl), p(off), p(streams), streams.size, C.byref(got)))
+        out, at = [], 0
+        for k in range(n):
+            stream = None
+            if st_[k] == 0:
+                stream = streams[at:at + int(nb[k])].tobytes()
+                at += int(nb[k])
+            out.append(dict(status=int(st_[k]), n_bytes=int(nb[k]), crc=int(crc[k]), text_len=int(tl[k]), arena_off=int(off[k]), stream=stream))
+        assert at == got.value
+        return out
 
     def copy_rate(self, nbytes: int = 1 << 30, reps: int = 10) -> float:
         """GB/s (read + written) of a device-to-device copy with the library's 16-bytes-per-lane copy kernel."""

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <memory>
 #include <mutex>
@@ -94,6 +95,10 @@ struct midas_snps_ctx {
   int row_coder = 0;      // MIDAS_SNPS_ROWS_DEVICE: who formats and deflates a batch's rows (midas_snps_set_row_coder)
   float sam_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // phases of the last midas_sam_load_device (midas_sam_decode_timing)
   float genes_ms[2] = {0, 0};                   // facts kernel, filter + sort + sums of the last midas_genes_count_device (midas_genes_count_timing)
+  // who coded the parts midas_snps_batch_write_part wrote at the row coder's levels (midas_snps_row_coder_counts): members coded by
+  // the kernel, parts left to the host's formatter before the launch (a contig id beyond the kernel's limit) and after it (a
+  // member came back with a status other than 0).  Several host threads may be writing one table each.
+  std::atomic<int64_t> rows_members_on_device{0}, rows_parts_declined_id{0}, rows_parts_declined_status{0};
   int default_path = 0;   // MIDAS_SNPS_PATH_AUTO: what batches created on this context take (midas_snps_set_default_path)
   // midas_snps_batch_write_part may be called from several host threads at once (one table each): the device part of a
   // call -- kernel, copies through the staging ring below -- is taken one at a time, the file writes run side by side

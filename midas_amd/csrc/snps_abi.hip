@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -3145,6 +3146,89 @@ struct DeviceBuf {      // freed on every way out
   ~DeviceBuf() { if (p) (void)hipFree(p); }
 };
 
+// The arena a launch of the row kernel gets: the tables of a 20x genome take ~4 bytes a row; ten a row and a header's worth per
+// member is room for any coverage seen so far, and a member that does not fit sends the part to the host's formatter.
+unsigned long long rows_arena_rule(int64_t rows, int64_t n_members) {
+  return (unsigned long long)rows * 10ull + (unsigned long long)n_members * 1024ull + 4096ull;
+}
+
+// What one launch of the row kernel leaves behind.
+struct CodedRows {
+  std::vector<RowsResult> results;     // one per member, in the members' order
+  unsigned long long used = 0;         // the arena's cursor after the launch (beyond arena_bytes when a member did not fit)
+  uint8_t* streams = nullptr;          // the arena's first min(used, arena_bytes) bytes: a member's stream is at its result's off
+  bool all_coded = false;              // every member came back with status 0
+  ~CodedRows() { free(streams); }      // (malloc: no zero fill)
+};
+
+// The device half of the row coder (rows_deflate.hip), the one launch behind midas_snps_batch_write_part and midas_snps_rows_code:
+// members and ids up, arena and cursor zeroed, the kernel over `grid_blocks` workgroups, results and streams down.  The members go to
+// the kernel as they are.  The streams of a launch in which some member was declined are copied only when `keep_declined` says so
+// (the table writer leaves such a part to the host's formatter and has no use for them).
+// Several host threads write one table each.  What they share is taken in turn, and as briefly as it can be: the context's
+// stream for the row kernel (device_mutex), then the pinned ring + the copy stream for the streams' way down (copy_mutex) --
+// table k's bytes cross the link while table k + 1 is formatted and deflated.  The allocations are nobody's turn.
+int32_t code_rows_on_device(midas_snps_ctx* ctx, const uint32_t* d_counts, const uint8_t* d_allele, const std::vector<RowsMember>& members,
+                            const std::vector<uint8_t>& ids, unsigned long long arena_bytes, int grid_blocks, bool keep_declined,
+                            CodedRows* out, const std::function<void(const char*)>& lap) {
+  const int64_t n_members = (int64_t)members.size();
+  out->results.assign((size_t)n_members, RowsResult{});
+  HIP_TRY(ctx, hipSetDevice(ctx->device));       // (the calling thread may never have talked to the device)
+  struct PooledBuf {      // one buffer (the context keeps a few between tables): | arena | members | results | cursor | ids |
+    midas_snps_ctx* ctx; void* p = nullptr; size_t bytes = 0;
+    ~PooledBuf() { if (p) ctx->row_buffers.give(p, bytes); }
+  } d_arena{ctx};
+  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t at_members = up256((size_t)arena_bytes), at_results = at_members + up256((size_t)n_members * sizeof(RowsMember)),
+               at_cursor = at_results + up256((size_t)n_members * sizeof(RowsResult)), at_ids = at_cursor + 256;
+  d_arena.p = ctx->row_buffers.take(at_ids + ids.size() + 16, &d_arena.bytes);
+  if (!d_arena.p) return fail(ctx, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "row coder: out of device memory for a table's coded rows");
+  uint8_t* const d_base = static_cast<uint8_t*>(d_arena.p);
+  struct Part { void* p; } d_members{d_base + at_members}, d_results{d_base + at_results}, d_cursor{d_base + at_cursor}, d_ids{d_base + at_ids};
+  lap("members + hipMalloc");
+  {
+  std::lock_guard<std::mutex> device_part(ctx->device_mutex);
+  hipStream_t s = ctx->stream;
+  HIP_TRY(ctx, hipMemcpyAsync(d_members.p, members.data(), (size_t)n_members * sizeof(RowsMember), hipMemcpyHostToDevice, s));
+  if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_ids.p, ids.data(), ids.size(), hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipMemsetAsync(d_arena.p, 0, (size_t)arena_bytes, s));
+  HIP_TRY(ctx, hipMemsetAsync(d_cursor.p, 0, 8, s));
+  RowsParams rp;
+  rp.counts = d_counts; rp.allele = d_allele;
+  rp.ids = static_cast<const uint8_t*>(d_ids.p);
+  rp.members = static_cast<const RowsMember*>(d_members.p);
+  rp.n_members = (int32_t)n_members;
+  rp.arena = static_cast<uint8_t*>(d_arena.p); rp.arena_bytes = arena_bytes;
+  rp.cursor = static_cast<unsigned long long*>(d_cursor.p);
+  rp.results = static_cast<RowsResult*>(d_results.p);
+  HIP_TRY(ctx, launch_rows_deflate(rp, grid_blocks, s));
+  HIP_TRY(ctx, hipMemcpyAsync(out->results.data(), d_results.p, (size_t)n_members * sizeof(RowsResult), hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(&out->used, d_cursor.p, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  lap("its turn, memset + kernel");
+  }
+  out->all_coded = out->used <= arena_bytes;
+  for (const RowsResult& r : out->results)
+    if (r.status != 0u) out->all_coded = false;
+  if (!out->all_coded && !keep_declined) return MIDAS_SNPS_OK;
+  const size_t down = (size_t)std::min(out->used, arena_bytes);
+  out->streams = static_cast<uint8_t*>(malloc(down + 16));
+  if (!out->streams) return fail(ctx, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "row coder: out of host memory");
+  {
+    hipStream_t cs = nullptr;
+    {
+      std::lock_guard<std::mutex> g(ctx->copy_mutex);
+      if (!ctx->copy_stream && hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->copy_stream = nullptr; }
+      cs = ctx->copy_stream;
+    }
+    // (the row kernel is over -- the stream was waited for above: the copy depends on nothing that is still running)
+    const int32_t cst = copy_to_host(ctx, out->streams, d_arena.p, down, cs);
+    if (cst != MIDAS_SNPS_OK) return cst;
+  }
+  lap("streams to host");
+  return MIDAS_SNPS_OK;      // (the device buffer goes back to the context here, before the caller writes its file: the next table takes it)
+}
+
 // The rows of the given contigs formatted and deflated on the device (rows_deflate.hip), framed and written by the host.
 // Returns MIDAS_SNPS_OK with *done = false when the device coder declines a member (a contig id beyond its limit, an arena
 // that turned out too small): the caller then takes the host's formatter for the whole part.
@@ -3167,7 +3251,7 @@ int32_t write_part_on_device(midas_snps_batch* b, const char* path, bool with_he
   std::vector<uint8_t> ids;
   for (int32_t k = 0; k < n_contigs; ++k) {
     const size_t id_off = ids.size(), id_len = strlen(ref_ids[k]);
-    if (id_len > 192) return MIDAS_SNPS_OK;
+    if (id_len > 192) { ctx->rows_parts_declined_id += 1; return MIDAS_SNPS_OK; }
     ids.insert(ids.end(), ref_ids[k], ref_ids[k] + id_len);
     for (int64_t lo = 0; lo < n_sites[k]; lo += kRowsPerMember) {
       RowsMember m;
@@ -3189,72 +3273,15 @@ int32_t write_part_on_device(midas_snps_batch* b, const char* path, bool with_he
   if (n_members > 0x7FFFFFFFll || ids.size() > 0x7FFFFFFFull) return MIDAS_SNPS_OK;
   int64_t rows = 0;
   for (const RowsMember& m : members) rows += m.n_rows;
-  // the tables of a 20x genome take ~4 bytes a row; ten a row and a header's worth per member is room for any coverage seen
-  // so far, and a member that does not fit sends the part to the host's formatter
-  const unsigned long long arena_bytes = (unsigned long long)rows * 10ull + (unsigned long long)n_members * 1024ull + 4096ull;
-  std::vector<RowsResult> results((size_t)n_members);
-  struct HostBuf { uint8_t* p = nullptr; ~HostBuf() { free(p); } } host;     // (malloc: no zero fill)
-  // Several host threads write one table each.  What they share is taken in turn, and as briefly as it can be: the context's
-  // stream for the row kernel (device_mutex), then the pinned ring + the copy stream for the streams' way down (copy_mutex) --
-  // table k's bytes cross the link while table k + 1 is formatted and deflated.  The allocations are nobody's turn.
-  HIP_TRY(ctx, hipSetDevice(ctx->device));       // (the calling thread may never have talked to the device)
-  struct PooledBuf {      // one buffer (the context keeps a few between tables): | arena | members | results | cursor | ids |
-    midas_snps_ctx* ctx; void* p = nullptr; size_t bytes = 0;
-    ~PooledBuf() { if (p) ctx->row_buffers.give(p, bytes); }
-  } d_arena{ctx};
-  auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t at_members = up256((size_t)arena_bytes), at_results = at_members + up256((size_t)n_members * sizeof(RowsMember)),
-               at_cursor = at_results + up256((size_t)n_members * sizeof(RowsResult)), at_ids = at_cursor + 256;
-  d_arena.p = ctx->row_buffers.take(at_ids + ids.size() + 16, &d_arena.bytes);
-  if (!d_arena.p) return fail(ctx, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "batch_write_part: out of device memory for a table's coded rows");
-  uint8_t* const d_base = static_cast<uint8_t*>(d_arena.p);
-  struct Part { void* p; } d_members{d_base + at_members}, d_results{d_base + at_results}, d_cursor{d_base + at_cursor}, d_ids{d_base + at_ids};
-  lap("members + hipMalloc");
-  unsigned long long used = 0;
-  {
-  std::lock_guard<std::mutex> device_part(ctx->device_mutex);
-  hipStream_t s = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(d_members.p, members.data(), (size_t)n_members * sizeof(RowsMember), hipMemcpyHostToDevice, s));
-  if (!ids.empty()) HIP_TRY(ctx, hipMemcpyAsync(d_ids.p, ids.data(), ids.size(), hipMemcpyHostToDevice, s));
-  HIP_TRY(ctx, hipMemsetAsync(d_arena.p, 0, (size_t)arena_bytes, s));
-  HIP_TRY(ctx, hipMemsetAsync(d_cursor.p, 0, 8, s));
-  RowsParams rp;
-  rp.counts = b->d_counts; rp.allele = b->d_allele;
-  rp.ids = static_cast<const uint8_t*>(d_ids.p);
-  rp.members = static_cast<const RowsMember*>(d_members.p);
-  rp.n_members = (int32_t)n_members;
-  rp.arena = static_cast<uint8_t*>(d_arena.p); rp.arena_bytes = arena_bytes;
-  rp.cursor = static_cast<unsigned long long*>(d_cursor.p);
-  rp.results = static_cast<RowsResult*>(d_results.p);
-  HIP_TRY(ctx, launch_rows_deflate(rp, ctx->prop.multiProcessorCount, s));
-  HIP_TRY(ctx, hipMemcpyAsync(results.data(), d_results.p, (size_t)n_members * sizeof(RowsResult), hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(&used, d_cursor.p, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  lap("its turn, memset + kernel");
-  }
-  for (const RowsResult& r : results)
-    if (r.status != 0u) return MIDAS_SNPS_OK;
-  if (used > arena_bytes) return MIDAS_SNPS_OK;
-  host.p = static_cast<uint8_t*>(malloc((size_t)used + 16));
-  if (!host.p) return fail(ctx, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "batch_write_part: out of host memory");
-  {
-    hipStream_t cs = nullptr;
-    {
-      std::lock_guard<std::mutex> g(ctx->copy_mutex);
-      if (!ctx->copy_stream && hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); ctx->copy_stream = nullptr; }
-      cs = ctx->copy_stream;
-    }
-    // (the row kernel is over -- the stream was waited for above: the copy depends on nothing that is still running)
-    const int32_t cst = copy_to_host(ctx, host.p, d_arena.p, (size_t)used, cs);
-    if (cst != MIDAS_SNPS_OK) return cst;
-  }
-  lap("streams to host");
-  ctx->row_buffers.give(d_arena.p, d_arena.bytes);       // (before the file is written: the next table takes it)
-  d_arena.p = nullptr;
+  CodedRows coded_rows;
+  const int32_t dst = code_rows_on_device(ctx, b->d_counts, b->d_allele, members, ids, rows_arena_rule(rows, n_members),
+                                          ctx->prop.multiProcessorCount, false, &coded_rows, lap);
+  if (dst != MIDAS_SNPS_OK) return dst;
+  if (!coded_rows.all_coded) { ctx->rows_parts_declined_status += 1; return MIDAS_SNPS_OK; }
   std::vector<CodedMember> coded((size_t)n_members);
   for (int64_t k = 0; k < n_members; ++k) {
-    const RowsResult& r = results[(size_t)k];
-    coded[(size_t)k] = CodedMember{host.p + r.off, r.n_bytes, r.crc, r.text_len, (uint32_t)members[(size_t)k].n_rows};
+    const RowsResult& r = coded_rows.results[(size_t)k];
+    coded[(size_t)k] = CodedMember{coded_rows.streams + r.off, r.n_bytes, r.crc, r.text_len, (uint32_t)members[(size_t)k].n_rows};
   }
   const int32_t st = write_coded_members(path, with_header, gz_level, n_members, coded.data(), threads, err);
   if (st != MIDAS_SNPS_OK) {
@@ -3262,10 +3289,72 @@ int32_t write_part_on_device(midas_snps_batch* b, const char* path, bool with_he
     return fail(ctx, st, err);
   }
   lap("frame + write");
+  ctx->rows_members_on_device += n_members;
   *done = true;
   return MIDAS_SNPS_OK;
 }
 }  // namespace
+
+int32_t midas_snps_row_coder_counts(const midas_snps_ctx* ctx, int64_t out3[3]) {
+  if (!ctx || !out3) return MIDAS_SNPS_ERR_INVALID_ARG;
+  out3[0] = ctx->rows_members_on_device.load();
+  out3[1] = ctx->rows_parts_declined_id.load();
+  out3[2] = ctx->rows_parts_declined_status.load();
+  return MIDAS_SNPS_OK;
+}
+
+int32_t midas_snps_rows_code(midas_snps_ctx* ctx, int64_t n_sites, const uint32_t* counts, const uint8_t* allele, int32_t n_members,
+                             const int64_t* site0, const int64_t* pos0, const int32_t* n_rows, const int32_t* id_off, const int32_t* id_len,
+                             const uint8_t* ids, int64_t ids_bytes, int64_t arena_bytes, int32_t grid_blocks, uint32_t* out_status,
+                             uint32_t* out_n_bytes, uint32_t* out_crc, uint32_t* out_text_len, int64_t* out_arena_off, uint8_t* out_streams,
+                             int64_t out_cap, int64_t* out_stream_bytes) {
+  if (!ctx || n_sites <= 0 || !counts || !allele || n_members <= 0 || !site0 || !pos0 || !n_rows || !id_off || !id_len || ids_bytes < 0 ||
+      (ids_bytes > 0 && !ids) || arena_bytes < 0 || grid_blocks < 0 || !out_status || !out_n_bytes || !out_crc || !out_text_len ||
+      !out_arena_off || out_cap < 0 || (out_cap > 0 && !out_streams) || !out_stream_bytes)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  // the kernel takes the members as they are; what is checked here is only that a member it WILL take (1..16 384 rows, an id within
+  // its limit) reads nothing outside the arrays it was given and numbers its rows below 2^31
+  std::vector<RowsMember> members((size_t)n_members);
+  int64_t rows = 0;
+  for (int32_t k = 0; k < n_members; ++k) {
+    if (id_len[k] < 0 || id_off[k] < 0 || (int64_t)id_off[k] + id_len[k] > ids_bytes)
+      return fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "rows_code: a member's id lies outside the ids");
+    if (n_rows[k] > 0 && n_rows[k] <= kRowsPerMember &&
+        (site0[k] < 0 || site0[k] + n_rows[k] > n_sites || pos0[k] < 0 || pos0[k] + n_rows[k] - 1 > 0x7FFFFFFFll))
+      return fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "rows_code: a member's sites or positions are out of range");
+    RowsMember& m = members[(size_t)k];
+    m.site0 = site0[k]; m.pos0 = pos0[k]; m.n_rows = n_rows[k]; m.id_off = id_off[k]; m.id_len = id_len[k]; m.pad = 0;
+    rows += std::min<int64_t>(std::max<int64_t>(n_rows[k], 0), kRowsPerMember);
+  }
+  const std::vector<uint8_t> id_bytes(ids, ids + ids_bytes);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuf d_counts, d_allele;
+  HIP_TRY(ctx, hipMalloc(&d_counts.p, (size_t)n_sites * 16));
+  HIP_TRY(ctx, hipMalloc(&d_allele.p, (size_t)n_sites));
+  {
+    std::lock_guard<std::mutex> g(ctx->device_mutex);
+    HIP_TRY(ctx, hipMemcpyAsync(d_counts.p, counts, (size_t)n_sites * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_allele.p, allele, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  CodedRows coded;
+  const int32_t st = code_rows_on_device(ctx, static_cast<const uint32_t*>(d_counts.p), static_cast<const uint8_t*>(d_allele.p), members, id_bytes,
+                                         arena_bytes ? (unsigned long long)arena_bytes : rows_arena_rule(rows, n_members),
+                                         grid_blocks ? grid_blocks : ctx->prop.multiProcessorCount, true, &coded, [](const char*) {});
+  if (st != MIDAS_SNPS_OK) return st;
+  int64_t at = 0;
+  for (int32_t k = 0; k < n_members; ++k) {
+    const RowsResult& r = coded.results[(size_t)k];
+    out_status[k] = r.status; out_n_bytes[k] = r.n_bytes; out_crc[k] = r.crc; out_text_len[k] = r.text_len;
+    out_arena_off[k] = r.status == 0u ? (int64_t)r.off : -1;
+    if (r.status != 0u) continue;
+    if (at + (int64_t)r.n_bytes > out_cap) return fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "rows_code: out_streams is too small for the streams");
+    memcpy(out_streams + at, coded.streams + r.off, r.n_bytes);
+    at += (int64_t)r.n_bytes;
+  }
+  *out_stream_bytes = at;
+  return MIDAS_SNPS_OK;
+}
 
 int32_t midas_snps_batch_write_part(midas_snps_batch* b, const char* path, int32_t with_header, int32_t n_contigs,
                                     const int32_t* contig_index, const char* const* ref_ids, int32_t gz_level, int32_t threads) {

@@ -16,7 +16,12 @@ pytestmark = pytest.mark.gpu
 THR = abi.Thresholds(mapid=94.0, mapq=20, baseq=30, readq=20, aln_cov=0.75)
 
 
-def _both(ctx, table, reads, names, tmp_path, tag, thr=THR, picks=None):
+def _members(n_sites):
+    """gzip members of a part whose contigs have these many sites: 16 384 rows each, a contig's last one the rest"""
+    return sum((int(n) + 16383) // 16384 for n in n_sites)
+
+
+def _both(ctx, table, reads, names, tmp_path, tag, thr=THR, picks=None, declined_for_id=False):
     b = ctx.batch(table, reads)
     b.run(thr)
     counts, allele, _ = b.fetch()
@@ -24,8 +29,17 @@ def _both(ctx, table, reads, names, tmp_path, tag, thr=THR, picks=None):
     pick = list(range(table.n_contigs)) if picks is None else picks
     dev, host = str(tmp_path / (tag + "_dev.gz")), str(tmp_path / (tag + "_host.gz"))
     ctx.set_row_coder(abi.ROWS_DEVICE)
+    before = ctx.row_coder_counts()
     b.write_part(dev, pick, [names[c] for c in pick], header=True, gz_level=4, threads=4)
+    after = ctx.row_coder_counts()
     b.close()
+    # who coded the part: every member the kernel, or -- for an id beyond its limit -- none of them, and nothing else happened
+    want = dict(before)
+    if declined_for_id:
+        want["parts_declined_id"] += 1
+    else:
+        want["members_on_device"] += _members(off[c + 1] - off[c] for c in pick)
+    assert after == want, (tag, before, after)
     abi.write_table(host, [names[c] for c in pick], [allele[off[c]:off[c + 1]] for c in pick],
                     [counts[off[c]:off[c + 1]] for c in pick], gz_level=4, threads=4)
     a, h = gzip.open(dev, "rb").read(), gzip.open(host, "rb").read()
@@ -85,7 +99,7 @@ def test_deep_and_empty_contigs_and_long_names(ctx, tmp_path):
                             ref=table.ref, n_species=1, ids=table.ids, species_ids=table.species_ids)
     names = ["a", "x" * 192, "Species_00001_contig_with_a_rather_long_name|and:odd=chars", "y" * 40]
     _both(ctx, table, sub, names, tmp_path, "deep")
-    _both(ctx, table, sub, ["a", "x" * 193, "b", "c"], tmp_path, "toolong")          # (host fallback: same text, and no error)
+    _both(ctx, table, sub, ["a", "x" * 193, "b", "c"], tmp_path, "toolong", declined_for_id=True)      # (host fallback: same text, and no error)
 
 
 def test_pieces_number_their_rows_from_the_origin(ctx, tmp_path):
@@ -96,10 +110,14 @@ def test_pieces_number_their_rows_from_the_origin(ctx, tmp_path):
     b = ctx.batch(pt, pr)
     b.run(THR)
     dev = str(tmp_path / "pieces_dev.gz")
+    before = ctx.row_coder_counts()
     b.write_part(dev, list(range(pt.n_contigs)), pt.ids, header=True, gz_level=4, threads=4)
+    coded = ctx.row_coder_counts()
+    assert coded == {**before, "members_on_device": before["members_on_device"] + _members(pt.length)}     # (every member the kernel's)
     ctx.set_row_coder(abi.ROWS_HOST)
     host = str(tmp_path / "pieces_host.gz")
     b.write_part(host, list(range(pt.n_contigs)), pt.ids, header=True, gz_level=4, threads=4)
     b.close()
     ctx.set_row_coder(abi.ROWS_DEVICE)
+    assert ctx.row_coder_counts() == coded                # (the host's coder was asked for: nothing was declined)
     assert gzip.open(dev, "rb").read() == gzip.open(host, "rb").read()
