@@ -898,7 +898,7 @@ hipError_t launch_bam_payload(const PayloadParams& p, int grid_blocks, hipStream
 
 // How many BGZF blocks fill the device ONCE with the decoder's workgroups (a lane a block, kW lanes a workgroup, as many
 // workgroups a CU as its LDS holds): the decoder is latency-bound, a launch takes about as long for one such wave of blocks as
-// for a tenth of it -- what a streamed decode's groups are sized by (snps_abi.hip device_decode_stream).
+// for a tenth of it -- what a streamed decode's groups are sized by (bam_device.hip device_decode_stream).
 long long bgzf_inflate_wave_blocks(int n_cu) {
   int occ = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, w64::bgzf_decode_kernel, w64::kW, 0) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 4; }

@@ -172,3 +172,12 @@ struct midas_snps_ctx {
   std::thread stage_thread;
   void stage_join() { if (stage_thread.joinable()) stage_thread.join(); }
 };
+
+// What the context's side (snps_abi.hip) lends the other translation units that implement entry points (bam_device.hip):
+// the flags of every page-locked allocation, the copies through the pinned staging ring, and hipFree as a handle's free_fn.
+namespace midas_ctx {
+extern const unsigned int kHostAllocFlags;
+int32_t copy_to_host(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t on = nullptr);
+int32_t copy_to_device_staged(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
+void device_free(void* p);
+}  // namespace midas_ctx

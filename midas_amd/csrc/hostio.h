@@ -23,7 +23,7 @@ struct RowFeed {
 int32_t write_rows_fed(const char* path, bool with_header, int32_t n_contigs, const char* const* ref_ids, const int64_t* n_sites,
                        int32_t gz_level, int32_t threads, const RowFeed& feed, char* err256, const int64_t* first_pos = nullptr);
 
-// Many raw DEFLATE streams inflated at once by somebody else than the host's threads (the device: snps_abi.hip).  The
+// Many raw DEFLATE streams inflated at once by somebody else than the host's threads (the device: bam_device.hip).  The
 // compressed bytes are given as segments that the streams' cpos count through back to back; upos are offsets into out.
 struct InflateJob { uint64_t cpos, upos; uint32_t clen, ulen; uint32_t crc, check_crc; };   // check_crc != 0: the inflated bytes' CRC-32 must be `crc`
 struct InflateSegment { const uint8_t* p; size_t n; };
@@ -49,7 +49,7 @@ int32_t bam_load_ranges_with(midas_bam* bam, const BlockInflater* inflater, int3
                              const int64_t* range_end, int64_t* n_reads, int64_t* seq_bytes, int64_t* qual_bytes,
                              int64_t* n_cigar, char* err256);
 
-// midas_bam_load_device (snps_abi.hip): the payload columns are cut on the device
+// midas_bam_load_device (bam_device.hip): the payload columns are cut on the device
 void bam_keep_payload_on_device(midas_bam* b);        // before midas_bam_load: decode everything but SEQ / QUAL / CIGAR
 const uint64_t* bam_record_offsets(const midas_bam* b, size_t* n);
 void bam_offsets(const midas_bam* b, const int64_t** seq_off, const int64_t** qual_off, const int64_t** cigar_off);
@@ -111,7 +111,7 @@ int32_t bam_decode_on_device(const char* path, const DeviceDecoder* dec, midas_b
                              int64_t* qual_bytes, int64_t* n_cigar, char* err256, int payload = 1);
 // a handle decoded with payload == 2: its device columns (nullptr: it is not such a handle), record count and array totals
 const ResidentReads* bam_resident(const midas_bam* b, int64_t* n_records, int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar);
-// midas_bam_resident_to_columns (snps_abi.hip): the handle's host columns for n records (false: out of memory); then the handle
+// midas_bam_resident_to_columns (bam_device.hip): the handle's host columns for n records (false: out of memory); then the handle
 // is as after midas_bam_load_device -- small columns in host memory, the three payload columns at the given device addresses,
 // `owner` (freed with the handle, besides what it holds already) keeping them alive
 bool bam_alloc_host_columns(midas_bam* b, int64_t n, HostColumns* c);

@@ -348,7 +348,7 @@ struct BamColumnsParams {
   int32_t* span;                                    // (nullable) reference span: the lengths of the record's M / D / N / = / X ops
   unsigned long long* bad_record;                   // min index of a record whose variable parts overrun its block_size or whose
                                                     // refID names no reference of the header (~0: none)
-  // A GROUP of a streamed decode (snps_abi.hip device_decode_stream): the records continue the columns of the groups before it --
+  // A GROUP of a streamed decode (bam_device.hip device_decode_stream): the records continue the columns of the groups before it --
   // the offsets' scans start at what those came to (entry [0] of this group = the last entry of the one before).
   long long base[4] = {0, 0, 0, 0};                 // seq_off, qual_off, cigar_off, unit_off
 };

@@ -4,7 +4,6 @@
 
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <thread>
 
 #include <cmath>
@@ -27,6 +26,7 @@
 #include <algorithm>
 
 using namespace midas;
+using namespace midas_ctx;
 
 // Page-locked host memory the device writes and host threads read: non-coherent (coarse-grained) allocations are ordinary
 // cached memory to the CPU -- the device's writes are visible once the stream has been synchronised, which every user
@@ -35,7 +35,7 @@ using namespace midas;
 #ifndef MIDAS_SNPS_HOST_ALLOC_FLAGS
 #define MIDAS_SNPS_HOST_ALLOC_FLAGS hipHostMallocNonCoherent
 #endif
-constexpr unsigned int kHostAllocFlags = MIDAS_SNPS_HOST_ALLOC_FLAGS;
+const unsigned int midas_ctx::kHostAllocFlags = MIDAS_SNPS_HOST_ALLOC_FLAGS;
 
 struct midas_snps_batch {
   midas_snps_ctx* ctx = nullptr;
@@ -246,7 +246,9 @@ __global__ __launch_bounds__(256) void copy_out_kernel(copy_u32x4* __restrict__ 
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += stride) __builtin_nontemporal_store(src[i], &dst[i]);
 }
 
-int32_t copy_to_host(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t on = nullptr) {
+}  // namespace
+
+int32_t midas_ctx::copy_to_host(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t on) {
   if (bytes == 0) return MIDAS_SNPS_OK;
   hipStream_t s = on ? on : ctx->stream;
   hipPointerAttribute_t at;
@@ -310,6 +312,7 @@ int32_t copy_to_host(midas_snps_ctx* ctx, void* dst, const void* src, size_t byt
   return MIDAS_SNPS_OK;
 }
 
+namespace {
 // Host bytes that are NOT page-locked (a mapped file, a malloc'd buffer) to the device through the context's pinned ring:
 // several threads copy a chunk into a slot while the slot before it crosses the link.  The runtime's own pageable path
 // stages through one thread: 14 GB/s out of a file mapping where this reaches the threads' copy rate.
@@ -344,7 +347,9 @@ bool parallel_pread(uint8_t* dst, int fd, size_t file_off, size_t n) {
   return bad == 0;
 }
 
-int32_t copy_to_device_staged(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s) {
+}  // namespace
+
+int32_t midas_ctx::copy_to_device_staged(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s) {
   constexpr size_t kChunk = midas_snps_ctx::kStageBytes;
   int src_fd = -1;
   size_t src_off = 0;
@@ -377,6 +382,9 @@ int32_t copy_to_device_staged(midas_snps_ctx* ctx, void* dst, const void* src, s
   return MIDAS_SNPS_OK;
 }
 
+void midas_ctx::device_free(void* p) { (void)hipFree(p); }
+
+namespace {
 // tile ranges are double-buffered by run parity: [rbinv0][rend0][rbinv1][rend1]
 // (each tile has three ranges, slots 3t..3t+2: see index_reads.hip)
 uint32_t* work_rbinv(midas_snps_batch* b, int par) { return reinterpret_cast<uint32_t*>(b->d_work) + (size_t)par * 6 * b->n_tiles; }
@@ -534,1440 +542,11 @@ int32_t midas_snps_copy_rate(midas_snps_ctx* ctx, int64_t bytes, int32_t reps, d
   return MIDAS_SNPS_OK;
 }
 
-namespace {
-// midas::BlockInflater over a context: the streams go to the device, one thread inflates each (bgzf_inflate.hip), the
-// inflated bytes come back through the staging ring.
-struct InflateUser {
-  midas_snps_ctx* ctx;
-  bool keep = false;            // leave the inflated stream on the device: `kept` (the caller frees it)
-  void* kept = nullptr;         // the arena; the inflated stream is at its start
-  size_t kept_bytes = 0;
-  uint8_t* scratch = nullptr;   // what lies behind the stream in the arena: dead once the call returns, the caller's to reuse
-  size_t scratch_bytes = 0;
-};
-int32_t device_inflate(void* user, const InflateSegment* segs, size_t n_segs, const InflateJob* jobs, size_t n_jobs, uint8_t* out,
-                       size_t out_bytes, int64_t* bad_job, char* err256) {
-  InflateUser* iu = static_cast<InflateUser*>(user);
-  midas_snps_ctx* ctx = iu->ctx;
-  if (bad_job) *bad_job = -1;
-  if (n_jobs == 0) return MIDAS_SNPS_OK;
-  size_t comp_bytes = 0;
-  for (size_t k = 0; k < n_segs; ++k) comp_bytes += segs[k].n;
-  for (size_t k = 0; k < n_jobs; ++k) {
-    if (jobs[k].cpos + jobs[k].clen > comp_bytes || jobs[k].upos + jobs[k].ulen > out_bytes) {
-      if (err256) snprintf(err256, 256, "device inflate: stream %lld lies outside the buffers", (long long)k);
-      return MIDAS_SNPS_ERR_INVALID_ARG;
-    }
-  }
-  auto hip_err = [&](hipError_t e, const char* what) {
-    if (err256) snprintf(err256, 256, "device inflate: %s: %s", what, hipGetErrorString(e));
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP;
-  };
-#define INF_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_err(e__, #call); } while (0)
-  std::lock_guard<std::mutex> g(ctx->device_mutex);
-  const bool trace = getenv("MIDAS_SNPS_TRACE") != nullptr;       // where the call spends its time, on stderr
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!trace) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[device inflate] %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
-    t_last = t;
-  };
-  INF_TRY(hipSetDevice(ctx->device));
-  // ONE allocation for everything the call needs (a hipMalloc / hipFree pair costs tens of milliseconds per gigabyte here, and
-  // the match lists' worst-case room alone is 2.7 bytes per output byte): | inflated | compressed | blocks | status | matches |
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  // Room for a stream's tokens and literals (bgzf_inflate.hip: a dword per match from the front, the literals from the end): as
-  // many bytes as the stream inflates to -- a BAM's block needs ~0.7 of that (8 000 tokens + 13 000 literals for 64 KiB), the
-  // bound is 4/3 (a match per three bytes) -- because device memory costs ~17 ms a gigabyte to allocate here and this is the
-  // second largest buffer.  A stream that needs more says so (kInflateMatchRoom) and is decoded again, with the bound's room,
-  // in a second small launch.  (InflateBlock counts the room in 8-byte units.)
-  std::vector<InflateBlock> blocks(n_jobs);
-  unsigned long long n_match_room = 0;
-  for (size_t k = 0; k < n_jobs; ++k) {
-    const uint32_t cap = jobs[k].ulen / 8u + 16u;
-    blocks[k] = InflateBlock{jobs[k].cpos, jobs[k].upos, n_match_room, jobs[k].clen, jobs[k].ulen, cap, 0u};
-    n_match_room += cap;
-  }
-  bool check = n_jobs > 0;       // the streams' CRC-32 is verified when every one of them brings it (BGZF blocks do)
-  for (size_t k = 0; k < n_jobs; ++k) check = check && jobs[k].check_crc != 0u;
-  const size_t at_out = 0, at_comp = up(out_bytes + 64), at_blocks = at_comp + up(comp_bytes + 512),
-               at_status = at_blocks + up(n_jobs * sizeof(InflateBlock)), at_crc = at_status + up(n_jobs * 8),
-               at_matches = at_crc + up(n_jobs * 4), arena_bytes = at_matches + up((size_t)n_match_room * 8);
-  struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } arena;
-  INF_TRY(hipMalloc(&arena.p, arena_bytes));
-  uint8_t* const base = static_cast<uint8_t*>(arena.p);
-  struct View { void* p; } d_out{base + at_out}, d_comp{base + at_comp}, d_blocks{base + at_blocks}, d_status{base + at_status},
-      d_crc{base + at_crc}, d_matches{base + at_matches};
-  hipStream_t s = ctx->stream;
-  size_t at = 0;
-  for (size_t k = 0; k < n_segs; ++k) {
-    if (segs[k].n) INF_TRY(hipMemcpyAsync(static_cast<uint8_t*>(d_comp.p) + at, segs[k].p, segs[k].n, hipMemcpyHostToDevice, s));
-    at += segs[k].n;
-  }
-  INF_TRY(hipMemsetAsync(static_cast<uint8_t*>(d_comp.p) + comp_bytes, 0, 512, s));
-  if (trace) { INF_TRY(hipStreamSynchronize(s)); lap("hipMalloc + streams up"); }
-  INF_TRY(hipMemcpyAsync(d_blocks.p, blocks.data(), n_jobs * sizeof(InflateBlock), hipMemcpyHostToDevice, s));
-  InflateParams ip;
-  ip.comp = static_cast<const uint8_t*>(d_comp.p);
-  ip.blocks = static_cast<const InflateBlock*>(d_blocks.p);
-  ip.n_blocks = (long long)n_jobs;
-  ip.out = static_cast<uint8_t*>(d_out.p);
-  ip.status = static_cast<uint32_t*>(d_status.p);
-  ip.n_matches = static_cast<uint32_t*>(d_status.p) + n_jobs;
-  ip.matches = static_cast<unsigned long long*>(d_matches.p);
-  ip.want_crc = nullptr;
-  std::vector<uint32_t> want;
-  if (check) {
-    want.resize(n_jobs);
-    for (size_t k = 0; k < n_jobs; ++k) want[k] = jobs[k].crc;
-    INF_TRY(hipMemcpyAsync(d_crc.p, want.data(), n_jobs * 4, hipMemcpyHostToDevice, s));
-    ip.want_crc = static_cast<const uint32_t*>(d_crc.p);
-  }
-  if (trace) {
-    INF_TRY(launch_bgzf_inflate(ip, s, 1));
-    INF_TRY(hipStreamSynchronize(s));
-    lap("decode kernel");
-    INF_TRY(launch_bgzf_inflate(ip, s, 2));
-    INF_TRY(hipStreamSynchronize(s));
-    lap("resolve kernel");
-  } else {
-    INF_TRY(launch_bgzf_inflate(ip, s));
-  }
-  std::vector<uint32_t> status(n_jobs);
-  INF_TRY(hipMemcpyAsync(status.data(), d_status.p, n_jobs * 4, hipMemcpyDeviceToHost, s));
-  INF_TRY(hipStreamSynchronize(s));
-  lap("kernel");
-  {   // the streams whose matches did not fit: again, with the bound's room
-    std::vector<size_t> again;
-    for (size_t k = 0; k < n_jobs; ++k)
-      if (status[k] == kInflateMatchRoom) again.push_back(k);
-    if (!again.empty()) {
-      std::vector<InflateBlock> b2(again.size());
-      unsigned long long room2 = 0;
-      for (size_t j = 0; j < again.size(); ++j) {
-        const InflateJob& q = jobs[again[j]];
-        const uint32_t cap = q.ulen / 3u + 1u;
-        b2[j] = InflateBlock{q.cpos, q.upos, room2, q.clen, q.ulen, cap, 0u};
-        room2 += cap;
-      }
-      Buf d_b2, d_s2, d_m2, d_c2;
-      std::vector<uint32_t> want2(again.size());
-      for (size_t j = 0; j < again.size(); ++j) want2[j] = jobs[again[j]].crc;
-      if (check) {
-        INF_TRY(hipMalloc(&d_c2.p, again.size() * 4));
-        INF_TRY(hipMemcpyAsync(d_c2.p, want2.data(), again.size() * 4, hipMemcpyHostToDevice, s));
-      }
-      INF_TRY(hipMalloc(&d_b2.p, b2.size() * sizeof(InflateBlock)));
-      INF_TRY(hipMalloc(&d_s2.p, b2.size() * 8));
-      INF_TRY(hipMalloc(&d_m2.p, (size_t)room2 * 8));
-      INF_TRY(hipMemcpyAsync(d_b2.p, b2.data(), b2.size() * sizeof(InflateBlock), hipMemcpyHostToDevice, s));
-      InflateParams ip2 = ip;
-      ip2.blocks = static_cast<const InflateBlock*>(d_b2.p);
-      ip2.n_blocks = (long long)b2.size();
-      ip2.status = static_cast<uint32_t*>(d_s2.p);
-      ip2.n_matches = static_cast<uint32_t*>(d_s2.p) + b2.size();
-      ip2.matches = static_cast<unsigned long long*>(d_m2.p);
-      ip2.want_crc = check ? static_cast<const uint32_t*>(d_c2.p) : nullptr;
-      INF_TRY(launch_bgzf_inflate(ip2, s));
-      std::vector<uint32_t> st2(b2.size());
-      INF_TRY(hipMemcpyAsync(st2.data(), d_s2.p, b2.size() * 4, hipMemcpyDeviceToHost, s));
-      INF_TRY(hipStreamSynchronize(s));
-      for (size_t j = 0; j < again.size(); ++j) status[again[j]] = st2[j];
-      lap("streams decoded again");
-    }
-  }
-#undef INF_TRY
-  for (size_t k = 0; k < n_jobs; ++k) {
-    if (status[k] != 0u) {
-      if (bad_job) *bad_job = (int64_t)k;
-      if (err256) snprintf(err256, 256, status[k] == kInflateCrc ? "CRC-32 mismatch (stream %lld: the inflated bytes are not the ones that were compressed)"
-                                                                 : "corrupt deflate data (stream %lld: code %u)", (long long)k, status[k]);
-      return MIDAS_SNPS_ERR_BAD_LAYOUT;
-    }
-  }
-  const int32_t st = copy_to_host(ctx, out, d_out.p, out_bytes);
-  if (st != MIDAS_SNPS_OK && err256) snprintf(err256, 256, "device inflate: results to host: %s", ctx->error_text().c_str());
-  lap("inflated bytes down");
-  if (st == MIDAS_SNPS_OK && iu->keep) {     // the caller takes the arena: the inflated stream, and everything behind it as scratch
-    iu->kept = arena.p; iu->kept_bytes = out_bytes; iu->scratch = base + at_comp; iu->scratch_bytes = arena_bytes - at_comp;
-    arena.p = nullptr;
-  }
-  return st;
-}
-}  // namespace
-
-int32_t midas_snps_inflate_blocks(midas_snps_ctx* ctx, const uint8_t* comp, int64_t comp_bytes, int64_t n_blocks,
-                                  const int64_t* cpos, const int32_t* clen, const int64_t* upos, const int32_t* ulen,
-                                  const uint32_t* crc, uint8_t* out, int64_t out_bytes, int64_t* bad_block) {
-  if (!ctx || comp_bytes < 0 || n_blocks < 0 || out_bytes < 0 || (n_blocks > 0 && (!comp || !cpos || !clen || !upos || !ulen || !out)))
-    return MIDAS_SNPS_ERR_INVALID_ARG;
-  std::vector<InflateJob> jobs((size_t)n_blocks);
-  for (int64_t k = 0; k < n_blocks; ++k) {
-    if (cpos[k] < 0 || clen[k] < 0 || upos[k] < 0 || ulen[k] < 0) return fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "inflate_blocks: negative offset or size");
-    jobs[(size_t)k] = InflateJob{(uint64_t)cpos[k], (uint64_t)upos[k], (uint32_t)clen[k], (uint32_t)ulen[k], crc ? crc[k] : 0u, crc ? 1u : 0u};
-  }
-  const InflateSegment seg{comp, (size_t)comp_bytes};
-  char err[256] = {0};
-  InflateUser iu{ctx};
-  const int32_t st = device_inflate(&iu, &seg, 1, jobs.data(), jobs.size(), out, (size_t)out_bytes, bad_block, err);
-  if (st != MIDAS_SNPS_OK) return fail(ctx, st, err);
-  return MIDAS_SNPS_OK;
-}
-
-int32_t midas_bam_open_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, char* err256) {
-  if (!ctx) return MIDAS_SNPS_ERR_INVALID_ARG;
-  InflateUser iu{ctx};
-  const BlockInflater inf{&iu, device_inflate};
-  return bam_open_with(path, &inf, out, err256);
-}
-
-namespace {
-void device_free(void* p) { (void)hipFree(p); }
-}
-
-// The decode with the host walking the records (the inflated stream comes down for that): what midas_bam_load_device falls back
-// to when the device cannot settle the record boundaries.
-static int32_t bam_load_device_host_walk(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
-                                         int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
-  if (!ctx || !path || !out) return MIDAS_SNPS_ERR_INVALID_ARG;
-  *out = nullptr;
-  InflateUser iu{ctx};
-  iu.keep = true;
-  const bool trace = getenv("MIDAS_SNPS_TRACE") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!trace) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[device decode] %-26s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
-    t_last = t;
-  };
-  struct Kept { InflateUser* u; ~Kept() { if (u->kept) (void)hipFree(u->kept); } } kept{&iu};       // (freed on every way out)
-  const BlockInflater inf{&iu, device_inflate};
-  midas_bam* b = nullptr;
-  int32_t st = bam_open_with(path, &inf, &b, err256);
-  if (st != MIDAS_SNPS_OK) return st;
-  struct Handle { midas_bam* b; ~Handle() { if (b) midas_bam_close(b); } } handle{b};
-  lap("open (map, inflate, header)");
-  bam_keep_payload_on_device(b);
-  int64_t n = 0, sb = 0, qb = 0, nc = 0;
-  st = midas_bam_load(b, &n, &sb, &qb, &nc, err256);        // the host walks the records and decodes the small columns
-  if (st != MIDAS_SNPS_OK) return st;
-  lap("host walk + small columns");
-  size_t n_off = 0;
-  const uint64_t* rec_off = bam_record_offsets(b, &n_off);
-  const int64_t *seq_off, *qual_off, *cigar_off;
-  bam_offsets(b, &seq_off, &qual_off, &cigar_off);
-  auto hip_err = [&](hipError_t e, const char* what) {
-    if (err256) snprintf(err256, 256, "device decode: %s: %s", what, hipGetErrorString(e));
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP;
-  };
-#define DEC_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_err(e__, #call); } while (0)
-  {
-    std::lock_guard<std::mutex> g(ctx->device_mutex);
-    DEC_TRY(hipSetDevice(ctx->device));
-    // the columns and the offsets the cut needs go where the compressed bytes and the match lists were (the arena's scratch is
-    // 2.7 x the stream, the columns 0.9 x): no second allocation
-    struct View { void* p = nullptr; } d_rec, d_so, d_qo, d_co, d_seq, d_qual, d_cig;
-    const size_t n1 = (size_t)n + 1;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t at = 0;
-    auto take = [&](View& v, size_t bytes) { v.p = iu.scratch + at; at += up(bytes); };
-    take(d_seq, (size_t)sb + 64); take(d_qual, (size_t)qb + 64); take(d_cig, (size_t)nc * 4 + 64);
-    take(d_rec, n1 * 8); take(d_so, n1 * 8); take(d_qo, n1 * 8); take(d_co, n1 * 8);
-    struct Own { void* p = nullptr; ~Own() { if (p) (void)hipFree(p); } } own;
-    if (at > iu.scratch_bytes) {      // (very short reads: more offsets than the scratch has room for -- a buffer of their own)
-      DEC_TRY(hipMalloc(&own.p, at));
-      const ptrdiff_t shift = static_cast<uint8_t*>(own.p) - iu.scratch;
-      for (View* v : {&d_seq, &d_qual, &d_cig, &d_rec, &d_so, &d_qo, &d_co}) v->p = static_cast<uint8_t*>(v->p) + shift;
-    }
-    hipStream_t s = ctx->stream;
-    lap("hipMalloc of the columns");
-    if (n > 0) DEC_TRY(hipMemcpyAsync(d_rec.p, rec_off, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_so.p, seq_off, n1 * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_qo.p, qual_off, n1 * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_co.p, cigar_off, n1 * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemsetAsync(static_cast<uint8_t*>(d_cig.p) + (size_t)nc * 4, 0, 64, s));
-    if (trace) { DEC_TRY(hipStreamSynchronize(s)); lap("offsets up"); }
-    PayloadParams pp;
-    pp.stream = static_cast<const uint8_t*>(iu.kept);
-    pp.rec_off = static_cast<const unsigned long long*>(d_rec.p);
-    pp.n_records = n;
-    pp.seq_off = static_cast<const long long*>(d_so.p);
-    pp.qual_off = static_cast<const long long*>(d_qo.p);
-    pp.cigar_off = static_cast<const long long*>(d_co.p);
-    pp.seq4 = static_cast<uint8_t*>(d_seq.p);
-    pp.qual = static_cast<uint8_t*>(d_qual.p);
-    pp.cigar = static_cast<uint32_t*>(d_cig.p);
-    DEC_TRY(launch_bam_payload(pp, ctx->prop.multiProcessorCount, s));
-    DEC_TRY(hipStreamSynchronize(s));
-    lap("payload kernel");
-    if (own.p) {                      // (the columns have their own buffer: the arena goes now)
-      bam_set_device_payload(b, d_seq.p, d_qual.p, d_cig.p, own.p, device_free);
-      own.p = nullptr;
-    } else {
-      bam_set_device_payload(b, d_seq.p, d_qual.p, d_cig.p, iu.kept, device_free);     // (the arena lives as long as the columns)
-      iu.kept = nullptr;
-    }
-  }
-  lap("free scratch");
-#undef DEC_TRY
-  if (n_reads) *n_reads = n;
-  if (seq_bytes) *seq_bytes = sb;
-  if (qual_bytes) *qual_bytes = qb;
-  if (n_cigar) *n_cigar = nc;
-  *out = b;
-  handle.b = nullptr;
-  return MIDAS_SNPS_OK;
-}
-
-
-namespace {
-struct ArenaLoan { std::shared_ptr<midas_arena_pool> pool; void* p; };
-void arena_loan_free(void* v) {
-  ArenaLoan* l = static_cast<ArenaLoan*>(v);
-  if (l) { l->pool->drop_twins(l->p); l->pool->give(l->p); delete l; }
-}
-
-// The streams of a decode whose matches did not fit their room (status kInflateMatchRoom): again, with the bound's room (a match
-// is at least three bytes), into the same output; their statuses replace the first pass's.
-hipError_t inflate_again(const InflateParams& ip, const std::vector<InflateBlock>& blocks, const std::vector<uint32_t>& want, std::vector<uint32_t>& status,
-                         hipStream_t s, bool* ran) {
-  *ran = false;
-  std::vector<size_t> again;
-  for (size_t k = 0; k < status.size(); ++k)
-    if (status[k] == kInflateMatchRoom) again.push_back(k);
-  if (again.empty()) return hipSuccess;
-  *ran = true;
-  std::vector<InflateBlock> b2(again.size());
-  std::vector<uint32_t> want2(again.size());
-  unsigned long long room2 = 0;
-  for (size_t j = 0; j < again.size(); ++j) {
-    const InflateBlock& q = blocks[again[j]];
-    const uint32_t cap = q.ulen / 3u + 1u;
-    b2[j] = InflateBlock{q.cpos, q.upos, room2, q.clen, q.ulen, cap, 0u};
-    want2[j] = want[again[j]];
-    room2 += cap;
-  }
-  struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } d_b2, d_s2, d_m2, d_c2;
-  hipError_t e;
-#define AG_TRY(call) do { e = (call); if (e != hipSuccess) return e; } while (0)
-  AG_TRY(hipMalloc(&d_b2.p, b2.size() * sizeof(InflateBlock)));
-  AG_TRY(hipMalloc(&d_s2.p, b2.size() * 8));
-  AG_TRY(hipMalloc(&d_m2.p, (size_t)room2 * 8));
-  AG_TRY(hipMalloc(&d_c2.p, b2.size() * 4));
-  AG_TRY(hipMemcpyAsync(d_b2.p, b2.data(), b2.size() * sizeof(InflateBlock), hipMemcpyHostToDevice, s));
-  AG_TRY(hipMemcpyAsync(d_c2.p, want2.data(), b2.size() * 4, hipMemcpyHostToDevice, s));
-  InflateParams ip2 = ip;
-  ip2.blocks = static_cast<const InflateBlock*>(d_b2.p);
-  ip2.n_blocks = (long long)b2.size();
-  ip2.status = static_cast<uint32_t*>(d_s2.p);
-  ip2.n_matches = static_cast<uint32_t*>(d_s2.p) + b2.size();
-  ip2.matches = static_cast<unsigned long long*>(d_m2.p);
-  ip2.want_crc = static_cast<const uint32_t*>(d_c2.p);
-  AG_TRY(launch_bgzf_inflate(ip2, s));
-  std::vector<uint32_t> st2(b2.size());
-  AG_TRY(hipMemcpyAsync(st2.data(), d_s2.p, b2.size() * 4, hipMemcpyDeviceToHost, s));
-  AG_TRY(hipStreamSynchronize(s));
-#undef AG_TRY
-  for (size_t j = 0; j < again.size(); ++j) status[again[j]] = st2[j];
-  return hipSuccess;
-}
-
-// ---- the streamed decode ------------------------------------------------------------------------------------------------------
-// A BAM of several device-fills of blocks (bgzf_inflate_wave_blocks), decoded RESIDENT group by group: the reference's loop over the
-// file (midas/run/snps.py:186-199 iterates the alignments as htslib inflates them, a block at a time) at the device's granularity.
-//   * a GROUP is a run of whole BGZF blocks -- one wave of the decoder's workgroups by default -- plus a few blocks behind it for
-//     the record that straddles its end; it wants the records that START inside it.  Where the chain of group g ends (the first
-//     record start at or behind its last wanted byte) is the exact first record of group g + 1: nothing is guessed behind group 0.
-//   * a group lives in a SLOT (inflated bytes | compressed bytes | block tables | match lists, the walk's tables over the dead
-//     ones); an uploader thread fills slot (g + 1) % S through the pinned ring on a stream of its own while the kernels of group g
-//     run on the context's -- the link and the decoder work at the same time.
-//   * what STAYS is written where it stays: every group's columns continue the ones before it (BamColumnsParams::base: the offset
-//     scans start at what the earlier groups came to), its records and their [cigar][seq][qual] runs go straight behind theirs
-//     in the direct layout.  Those arrays are sized from the first group's records per inflated byte (+ 3 %) and grown (a copy on
-//     the device) if a later group proves the estimate short.
-// Device memory: S slots of ~2.5 x a group's inflated bytes + the result (~1.1 x the file's inflated bytes), against ~2.3 x the
-// file's inflated bytes in one arena -- bounded by the group, not by the file, in everything but the result itself.
-// No inflated stream is kept: a handle decoded this way cuts its raw columns, if somebody asks for them, out of the direct layout
-// (PayloadParams::drec).  kStreamFallback: this BAM is not for the streamed decode (a record longer than the blocks a group
-// keeps behind its end) -- the caller decodes it in one arena.
-constexpr int32_t kStreamFallback = -1000;
-constexpr uint32_t kSideFirstEntries = 4096;                 // the side buffer's first room (layout.h DenseSide): grown by the group that needs more
-constexpr unsigned long long kSideFirstBytes = 1ull << 20;
-struct TwoBuffers { void* a; void* b; void* c; };
-void two_buffers_free(void* v) {
-  TwoBuffers* t = static_cast<TwoBuffers*>(v);
-  if (t->a) (void)hipFree(t->a);
-  if (t->b) (void)hipFree(t->b);
-  if (t->c) (void)hipFree(t->c);
-  delete t;
-}
-struct StreamColumns {       // the result's record arrays in ONE allocation, for `cap` records (+ 2: the offsets' last entry, the sentinel record)
-  uint8_t* p = nullptr;
-  size_t cap = 0, bytes = 0;
-  size_t at[11] = {0};        // rec, refid, pos, nm, l_seq, mapq, flag, seq_off, qual_off, cigar_off, unit_off
-  static constexpr size_t width(int k) { return k == 0 ? 16 : (k <= 4 ? 4 : (k == 5 ? 1 : (k == 6 ? 2 : 8))); }
-  void lay(size_t cap_records) {
-    cap = cap_records;
-    size_t o = 0;
-    for (int k = 0; k < 11; ++k) { at[k] = o; o += ((cap + 2) * width(k) + 255) & ~(size_t)255; }
-    bytes = o;
-  }
-  uint8_t* colp(int k) const { return p + at[k]; }
-};
-
-int32_t device_decode_stream(midas_snps_ctx* ctx, const uint8_t* comp_base, const InflateJob* jobs, DecodeSegment& sg, size_t group_blocks, int n_slots,
-                             const int64_t* ref_lens, int32_t n_ref, HostColumns (*alloc)(void*, int64_t), void* sink, DeviceDecodeResult* res,
-                             int64_t* bad_job, int64_t* bad_record, char* err256) {
-  auto hip_err = [&](hipError_t e, const char* what) {
-    if (err256) snprintf(err256, 256, "device decode (streamed): %s: %s", what, hipGetErrorString(e));
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP;
-  };
-#define DS_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_err(e__, #call); } while (0)
-  const bool trace = getenv("MIDAS_SNPS_TRACE") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto t_last = t_begin;
-  double laps[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // waited for the upload, inflate, walk, stitch, columns, direct, grow, tables
-  auto lap = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    laps[k] += std::chrono::duration<double, std::milli>(t - t_last).count();
-    t_last = t;
-  };
-  hipStream_t s = ctx->stream;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  constexpr size_t kTail = 8;                    // blocks kept behind a group's last: the record that straddles its end lies in them
-  const size_t j_lo = sg.job_lo, j_hi = sg.job_hi;
-  const size_t K = (j_hi - j_lo + group_blocks - 1) / group_blocks;
-  const uint64_t seg_limit = jobs[j_hi - 1].upos + jobs[j_hi - 1].ulen;
-  const uint64_t seg_stop = sg.stop < seg_limit ? sg.stop : seg_limit;
-  struct Group { size_t b_lo, b_hi, b_ext; uint64_t u_lo, stop; size_t comp, infl, room; };
-  std::vector<Group> groups(K);
-  size_t slot_bytes = 0;
-  for (size_t g = 0; g < K; ++g) {
-    Group& G = groups[g];
-    G.b_lo = j_lo + g * group_blocks;
-    G.b_hi = std::min(j_hi, G.b_lo + group_blocks);
-    G.b_ext = std::min(j_hi, G.b_hi + kTail);
-    G.u_lo = jobs[G.b_lo].upos;
-    G.stop = G.b_hi == j_hi ? seg_stop : std::min<uint64_t>(seg_stop, jobs[G.b_hi].upos);
-    G.comp = (size_t)(jobs[G.b_ext - 1].cpos + jobs[G.b_ext - 1].clen + 8 - jobs[G.b_lo].cpos);
-    G.infl = (size_t)(jobs[G.b_ext - 1].upos + jobs[G.b_ext - 1].ulen - G.u_lo);
-    G.room = 0;
-    for (size_t j = G.b_lo; j < G.b_ext; ++j) {
-      if (jobs[j].cpos < jobs[G.b_lo].cpos || jobs[j].upos < G.u_lo) { if (err256) snprintf(err256, 256, "device decode: block %lld lies outside the buffers", (long long)j); return MIDAS_SNPS_ERR_INVALID_ARG; }
-      G.room += jobs[j].ulen / 8u + 16u;
-    }
-    const size_t nj = G.b_ext - G.b_lo;
-    // (behind the inflated bytes: the dead compressed bytes, tables and match lists hold the walk's tables and the record offsets --
-    // 8 bytes a record of >= 36: a quarter of the inflated bytes at most)
-    const size_t behind = std::max(up(G.comp + 512) + up(nj * sizeof(InflateBlock)) + up(nj * 8) + up(nj * 4) + up(G.room * 8) + 256, G.infl / 3 + ((size_t)4 << 20) + up((size_t)(n_ref > 0 ? n_ref : 1) * 8));      // (slot_layout's regions, each rounded up by itself)
-    slot_bytes = std::max(slot_bytes, up(G.infl + 64) + behind);
-  }
-  if (n_slots > (int)K) n_slots = (int)K;
-  bool pooled = false;
-  void* arena_p = ctx->arena->take(slot_bytes * (size_t)n_slots, &pooled);
-  if (!arena_p) { if (err256) snprintf(err256, 256, "device decode (streamed): out of device memory (%.1f GB of slots)", (double)(slot_bytes * (size_t)n_slots) / 1e9); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-  struct Loan { std::shared_ptr<midas_arena_pool> pool; void* p; ~Loan() { if (p) pool->give(p); } } loan{ctx->arena, arena_p};
-  uint8_t* const arena = static_cast<uint8_t*>(arena_p);
-  const double slots_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  if (trace) fprintf(stderr, "[device decode] streamed: %zu groups of <= %zu blocks, %d slots of %.2f GB (allocated in %.1f ms)\n", K, group_blocks, n_slots,
-                     (double)slot_bytes / 1e9, slots_ms);
-  t_last = std::chrono::steady_clock::now();
-
-  // ---- the uploader: a group's bytes and tables up on its own stream, then the group's decoder / resolver / CRC kernels on one of
-  // two streams (groups alternate: the decoder is latency-bound -- ~25 ms a launch however few blocks -- and the next group's
-  // workgroups fill the CUs that this group's stragglers leave idle), its statuses down into pinned memory, an event behind them --
-  struct Pipe {
-    std::mutex m;
-    std::condition_variable cv;
-    long long launched = 0, decoded = 0;
-    bool abort = false;
-    int32_t status = MIDAS_SNPS_OK;
-    hipError_t hip = hipSuccess;
-    double busy_ms = 0;
-  } pipe;
-  struct GroupHost { std::vector<InflateBlock> blocks; std::vector<uint32_t> want; };
-  std::vector<GroupHost> host(K);
-  struct Streams {
-    hipStream_t up = nullptr, inf[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> ev;
-    uint32_t* status = nullptr;       // pinned: every group's block statuses
-    ~Streams() {
-      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-      if (up) (void)hipStreamDestroy(up);
-      for (hipStream_t q : inf) if (q) (void)hipStreamDestroy(q);
-      if (status) (void)hipHostFree(status);
-    }
-  } st;
-  DS_TRY(hipStreamCreateWithFlags(&st.up, hipStreamNonBlocking));
-  DS_TRY(hipStreamCreateWithFlags(&st.inf[0], hipStreamNonBlocking));
-  DS_TRY(hipStreamCreateWithFlags(&st.inf[1], hipStreamNonBlocking));
-  st.ev.assign(K, nullptr);
-  for (size_t g = 0; g < K; ++g) DS_TRY(hipEventCreateWithFlags(&st.ev[g], hipEventDisableTiming));
-  std::vector<size_t> status_at(K + 1, 0);
-  for (size_t g = 0; g < K; ++g) status_at[g + 1] = status_at[g] + (groups[g].b_ext - groups[g].b_lo);
-  DS_TRY(hipHostMalloc(reinterpret_cast<void**>(&st.status), status_at[K] * 4 + 64, kHostAllocFlags));
-  auto slot_layout = [&](const Group& G, size_t* at_comp, size_t* at_blocks, size_t* at_status, size_t* at_crc, size_t* at_matches) {
-    const size_t nj = G.b_ext - G.b_lo;
-    *at_comp = up(G.infl + 64); *at_blocks = *at_comp + up(G.comp + 512); *at_status = *at_blocks + up(nj * sizeof(InflateBlock));
-    *at_crc = *at_status + up(nj * 8); *at_matches = *at_crc + up(nj * 4);
-  };
-  auto inflate_params = [&](const Group& G, uint8_t* slot) {
-    size_t at_comp, at_blocks, at_status, at_crc, at_matches;
-    slot_layout(G, &at_comp, &at_blocks, &at_status, &at_crc, &at_matches);
-    const size_t nj = G.b_ext - G.b_lo;
-    InflateParams ip;
-    ip.comp = slot + at_comp;
-    ip.blocks = reinterpret_cast<const InflateBlock*>(slot + at_blocks);
-    ip.n_blocks = (long long)nj;
-    ip.out = slot;
-    ip.status = reinterpret_cast<uint32_t*>(slot + at_status);
-    ip.n_matches = reinterpret_cast<uint32_t*>(slot + at_status) + nj;
-    ip.matches = reinterpret_cast<unsigned long long*>(slot + at_matches);
-    ip.want_crc = reinterpret_cast<const uint32_t*>(slot + at_crc);
-    return ip;
-  };
-  std::thread uploader([&] {
-    (void)hipSetDevice(ctx->device);
-    for (size_t g = 0; g < K; ++g) {
-      {
-        std::unique_lock<std::mutex> lk(pipe.m);
-        pipe.cv.wait(lk, [&] { return pipe.abort || (long long)g < pipe.decoded + n_slots; });
-        if (pipe.abort) return;
-      }
-      const Group& G = groups[g];
-      uint8_t* slot = arena + (g % (size_t)n_slots) * slot_bytes;
-      const auto t0 = std::chrono::steady_clock::now();
-      const size_t nj = G.b_ext - G.b_lo;
-      GroupHost& H = host[g];
-      H.blocks.resize(nj);
-      H.want.resize(nj);
-      {
-        unsigned long long room = 0;
-        const uint64_t c0 = jobs[G.b_lo].cpos;
-        for (size_t j = 0; j < nj; ++j) {
-          const InflateJob& q = jobs[G.b_lo + j];
-          const uint32_t cap = q.ulen / 8u + 16u;
-          H.blocks[j] = InflateBlock{(unsigned long long)(q.cpos - c0), (unsigned long long)(q.upos - G.u_lo), room, q.clen, q.ulen, cap, 0u};
-          H.want[j] = q.crc;
-          room += cap;
-        }
-      }
-      size_t at_comp, at_blocks, at_status, at_crc, at_matches;
-      slot_layout(G, &at_comp, &at_blocks, &at_status, &at_crc, &at_matches);
-      int32_t ust = copy_to_device_staged(ctx, slot + at_comp, comp_base + jobs[G.b_lo].cpos, G.comp, st.up);
-      hipError_t e = hipSuccess;
-      if (ust == MIDAS_SNPS_OK) {
-        e = hipMemcpyAsync(slot + at_blocks, H.blocks.data(), nj * sizeof(InflateBlock), hipMemcpyHostToDevice, st.up);
-        if (e == hipSuccess) e = hipMemcpyAsync(slot + at_crc, H.want.data(), nj * 4, hipMemcpyHostToDevice, st.up);
-        if (e == hipSuccess) e = hipMemsetAsync(slot + at_comp + G.comp, 0, 512, st.up);
-        if (e == hipSuccess) e = hipStreamSynchronize(st.up);
-        if (e == hipSuccess) {
-          hipStream_t q = st.inf[g & 1];
-          const InflateParams ip = inflate_params(G, slot);
-          e = launch_bgzf_inflate(ip, q);
-          if (e == hipSuccess) e = hipMemcpyAsync(st.status + status_at[g], ip.status, nj * 4, hipMemcpyDeviceToHost, q);
-          if (e == hipSuccess) e = hipEventRecord(st.ev[g], q);
-        }
-        if (e != hipSuccess) { (void)hipGetLastError(); ust = e == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP; }
-      }
-      {
-        std::lock_guard<std::mutex> lk(pipe.m);
-        pipe.busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        if (ust != MIDAS_SNPS_OK) { pipe.status = ust; pipe.hip = e; pipe.abort = true; }
-        else pipe.launched = (long long)g + 1;
-      }
-      pipe.cv.notify_all();
-      if (ust != MIDAS_SNPS_OK) return;
-    }
-  });
-  struct Join {       // (every way out: the uploader is told to stop and waited for, the streams' work too)
-    Pipe& pipe; std::thread& t; Streams& st;
-    ~Join() {
-      { std::lock_guard<std::mutex> lk(pipe.m); pipe.abort = true; }
-      pipe.cv.notify_all();
-      if (t.joinable()) t.join();
-      for (hipStream_t q : st.inf) if (q) (void)hipStreamSynchronize(q);
-      (void)hipGetLastError();
-    }
-  } join{pipe, uploader, st};
-
-  // ---- the result's arrays ----------------------------------------------------------------------------------------------------------
-  StreamColumns cols;
-  struct Pay { uint8_t* p = nullptr; size_t cap_units = 0; } pay;
-  // the side buffer (layout.h DenseSide): the raw SEQ / QUAL of the reads the base bytes cannot give back -- none in most files;
-  // a group that finds no room is written again behind a buffer with room for all of its SEQ / QUAL
-  struct Side { DenseSide* p = nullptr; DenseSide h{}; } side;
-  struct Owned { StreamColumns& c; Pay& y; Side& z; bool keep = false; ~Owned() { if (!keep) { if (c.p) (void)hipFree(c.p); if (y.p) (void)hipFree(y.p); if (z.p) (void)hipFree(z.p); } } } owned{cols, pay, side};
-  auto grow_side = [&](uint32_t cap_entries, unsigned long long cap_bytes) -> int32_t {     // (what the groups so far kept moves along)
-    DenseSide* q = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), (size_t)dense_side_bytes(cap_entries, cap_bytes));
-    if (e != hipSuccess) return hip_err(e, "the side buffer");
-    DenseSide h = side.h;
-    h.flags &= ~kDenseSideOverflow;
-    h.cap_entries = cap_entries; h.cap_bytes = cap_bytes;
-    const unsigned long long n_ent = side.h.bump >> kDenseSideEntryShift, n_bytes = (side.h.bump & kDenseSideMaxField) << 3;
-    e = hipMemcpyAsync(q, &h, sizeof h, hipMemcpyHostToDevice, s);
-    if (side.p && n_ent > 0) {
-      if (e == hipSuccess) e = hipMemcpyAsync(dense_side_entries(q), dense_side_entries(side.p), n_ent * sizeof(DenseSideEntry), hipMemcpyDeviceToDevice, s);
-      if (e == hipSuccess) e = hipMemcpyAsync(reinterpret_cast<uint8_t*>(dense_side_entries(q) + cap_entries),
-                                              reinterpret_cast<uint8_t*>(dense_side_entries(side.p) + side.h.cap_entries), n_bytes, hipMemcpyDeviceToDevice, s);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (side.p) (void)hipFree(side.p);
-    side.p = q;
-    side.h = h;
-    return e == hipSuccess ? MIDAS_SNPS_OK : hip_err(e, "the side buffer moved");
-  };
-  {
-    const int32_t gs = grow_side(kSideFirstEntries, kSideFirstBytes);
-    if (gs != MIDAS_SNPS_OK) return gs;
-  }
-  long long N = 0;                                  // records so far
-  long long base[4] = {0, 0, 0, 0};                 // what the offset columns came to so far: SEQ bytes, QUAL bytes, CIGAR ops, payload units
-  const double span_total = (double)(seg_stop > sg.from ? seg_stop - sg.from : 1);
-  auto grow_columns = [&](size_t need) -> int32_t {       // room for `need` records
-    if (cols.p && need <= cols.cap) return MIDAS_SNPS_OK;
-    StreamColumns nc;
-    nc.lay(need);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nc.p), nc.bytes);
-    if (e != hipSuccess) return hip_err(e, "the records' arrays");
-    if (cols.p) {
-      for (int k = 0; k < 11; ++k) {
-        const size_t n = (size_t)N + (k == 0 || k >= 7 ? 1 : 0);
-        e = hipMemcpyAsync(nc.p + nc.at[k], cols.p + cols.at[k], n * StreamColumns::width(k), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { (void)hipFree(nc.p); return hip_err(e, "the records' arrays moved"); }
-      }
-      e = hipStreamSynchronize(s);
-      (void)hipFree(cols.p);
-      if (e != hipSuccess) { (void)hipFree(nc.p); return hip_err(e, "the records' arrays moved"); }
-    }
-    cols = nc;
-    return MIDAS_SNPS_OK;
-  };
-  auto grow_payload = [&](size_t need_units) -> int32_t {
-    if (pay.p && need_units <= pay.cap_units) return MIDAS_SNPS_OK;
-    uint8_t* q = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&q), need_units * 8 + 64);
-    if (e != hipSuccess) return hip_err(e, "the reads' payload");
-    if (pay.p) {
-      e = base[3] > 0 ? hipMemcpyAsync(q, pay.p, (size_t)base[3] * 8, hipMemcpyDeviceToDevice, s) : hipSuccess;
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      (void)hipFree(pay.p);
-      if (e != hipSuccess) { (void)hipFree(q); return hip_err(e, "the reads' payload moved"); }
-    }
-    pay.p = q;
-    pay.cap_units = need_units;
-    return MIDAS_SNPS_OK;
-  };
-
-  // ---- group by group -----------------------------------------------------------------------------------------------------------------
-  sg.first = ~0ull; sg.n_records = 0; sg.n_unmapped = 0; sg.first_unmapped = ~0ull; sg.end = seg_stop;
-  unsigned long long cur = sg.exact ? sg.from : ~0ull;       // GLOBAL buffer offset of the next record (~0: group 0 guesses it)
-  int regrown = 0, rounds_total = 0;
-  const unsigned long long kChunk = 32768ull;
-  for (size_t g = 0; g < K; ++g) {
-    const Group& G = groups[g];
-    uint8_t* const slot = arena + (g % (size_t)n_slots) * slot_bytes;
-    const size_t nj = G.b_ext - G.b_lo;
-    size_t at_comp, at_blocks, at_status, at_crc, at_matches;
-    slot_layout(G, &at_comp, &at_blocks, &at_status, &at_crc, &at_matches);
-    lap(7);
-    {
-      std::unique_lock<std::mutex> lk(pipe.m);
-      pipe.cv.wait(lk, [&] { return pipe.abort || pipe.launched > (long long)g; });
-      if (pipe.launched <= (long long)g) {
-        if (pipe.hip != hipSuccess) return hip_err(pipe.hip, "a group's blocks to the device and its decoder's launch");
-        if (err256) snprintf(err256, 256, "device decode (streamed): blocks to the device: %s", ctx->error_text().c_str());
-        return pipe.status != MIDAS_SNPS_OK ? pipe.status : MIDAS_SNPS_ERR_HIP;
-      }
-    }
-    lap(0);
-    DS_TRY(hipEventSynchronize(st.ev[g]));        // the group is inflated, resolved, checked; its statuses are down
-    const InflateParams ip = inflate_params(G, slot);
-    const std::vector<InflateBlock>& blocks = host[g].blocks;
-    const std::vector<uint32_t>& want = host[g].want;
-    std::vector<uint32_t> status(st.status + status_at[g], st.status + status_at[g] + nj);
-    {
-      bool again = false;
-      const hipError_t ae = inflate_again(ip, blocks, want, status, s, &again);
-      if (ae != hipSuccess) return hip_err(ae, "streams decoded again");
-    }
-    for (size_t k = 0; k < nj; ++k) {
-      if (status[k] != 0u) {
-        *bad_job = (int64_t)(G.b_lo + k);
-        if (err256) snprintf(err256, 256, "corrupt BGZF block %lld (code %u)", (long long)(G.b_lo + k), status[k]);
-        return MIDAS_SNPS_ERR_BAD_LAYOUT;
-      }
-    }
-    lap(1);
-    // ---- the record walk of the group: chunks over [from, stop) in the slot's own offsets -----------------------------------------
-    const unsigned long long l_limit = G.infl;
-    const unsigned long long l_stop = G.stop > G.u_lo ? (unsigned long long)(G.stop - G.u_lo) : 0ull;
-    unsigned long long l_from;
-    bool exact;
-    if (cur != ~0ull) { exact = true; l_from = cur >= G.u_lo ? cur - G.u_lo : 0ull; }
-    else { exact = false; l_from = g == 0 && sg.from >= G.u_lo ? (unsigned long long)(sg.from - G.u_lo) : 0ull; }
-    if (cur != ~0ull && cur < G.u_lo) {        // (cannot be: the chain of the group before ended at or behind this group's first byte)
-      if (err256) snprintf(err256, 256, "device decode (streamed): the record chain fell behind group %zu", g);
-      return MIDAS_SNPS_ERR_UNSUPPORTED;
-    }
-    std::vector<unsigned long long> h_lo, h_hi, h_stop, h_limit, h_start;
-    std::vector<uint8_t> h_forced;
-    for (unsigned long long lo = l_from; lo < l_stop; lo += kChunk) {
-      h_lo.push_back(lo); h_hi.push_back(lo + kChunk < l_stop ? lo + kChunk : l_stop); h_stop.push_back(l_stop); h_limit.push_back(l_limit);
-      const bool first = lo == l_from;
-      h_forced.push_back(first && exact ? 1 : 0);
-      h_start.push_back(first && exact ? l_from : ~0ull);
-    }
-    const long long n_chunks = (long long)h_lo.size();
-    uint8_t* const scratch = slot + at_comp;
-    const size_t scratch_bytes = slot_bytes - at_comp;
-    size_t at = 0;
-    auto take = [&](size_t bytes) -> uint8_t* { uint8_t* q = scratch + at; at += up(bytes); return at <= scratch_bytes ? q : nullptr; };
-    const size_t nc1 = (size_t)(n_chunks > 0 ? n_chunks : 1);
-    BamWalkParams wp;
-    wp.d = slot; wp.n_ref = n_ref; wp.n_chunks = n_chunks;
-    long long* d_ref_lens = reinterpret_cast<long long*>(take((size_t)(n_ref > 0 ? n_ref : 1) * 8));
-    unsigned long long* d_lo = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    unsigned long long* d_hi = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    unsigned long long* d_stop = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    unsigned long long* d_limit = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    uint8_t* d_forced = take(nc1);
-    wp.start = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    wp.end = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    wp.kept = reinterpret_cast<uint32_t*>(take(nc1 * 4));
-    wp.unmapped = reinterpret_cast<uint32_t*>(take(nc1 * 4));
-    wp.first_unmapped = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    wp.bad = reinterpret_cast<uint32_t*>(take(nc1 * 4));
-    unsigned long long* d_base = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-    long long* d_list = reinterpret_cast<long long*>(take(4096 * 8));
-    if (!d_list) { if (err256) snprintf(err256, 256, "device decode (streamed): a slot is too small for the walk"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-    wp.lo = d_lo; wp.hi = d_hi; wp.stop = d_stop; wp.limit = d_limit; wp.forced = d_forced; wp.ref_lens = d_ref_lens;
-    if (n_ref > 0) DS_TRY(hipMemcpyAsync(d_ref_lens, ref_lens, (size_t)n_ref * 8, hipMemcpyHostToDevice, s));
-    std::vector<unsigned long long> h_end(nc1), h_base(nc1), h_fu(nc1);
-    std::vector<uint32_t> h_kept(nc1), h_bad(nc1), h_unm(nc1);
-    if (n_chunks > 0) {
-      DS_TRY(hipMemcpyAsync(d_lo, h_lo.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(d_hi, h_hi.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(d_stop, h_stop.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(d_limit, h_limit.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(d_forced, h_forced.data(), (size_t)n_chunks, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(wp.start, h_start.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-      DS_TRY(launch_bam_walk(wp, nullptr, 0, s));
-      DS_TRY(hipMemcpyAsync(h_start.data(), wp.start, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(h_end.data(), wp.end, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(h_kept.data(), wp.kept, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(h_unm.data(), wp.unmapped, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(h_fu.data(), wp.first_unmapped, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(h_bad.data(), wp.bad, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipStreamSynchronize(s));
-    }
-    lap(2);
-    // stitch in order (device_decode_run's loop, one segment); a record that overruns the bytes the group keeps behind its end: not for
-    // this decode
-    unsigned long long lcur = exact ? l_from : ~0ull;
-    unsigned long long g_first = ~0ull;
-    long long g_records = 0;
-    for (size_t c = 0; c < (size_t)n_chunks;) {
-      if (lcur == ~0ull) {
-        if (h_start[c] == ~0ull) { h_kept[c] = 0u; h_unm[c] = 0u; ++c; continue; }
-        lcur = h_start[c];
-      }
-      if (lcur >= h_hi[c] || lcur + 4 > h_limit[c]) { h_kept[c] = 0u; h_unm[c] = 0u; h_start[c] = ~0ull; ++c; continue; }
-      if (h_start[c] == lcur) {
-        if (h_bad[c]) {
-          if (G.b_ext < j_hi) return kStreamFallback;       // (the group's own bytes end where the record goes on: the one-arena decode holds it whole)
-          *bad_record = -2;
-          return MIDAS_SNPS_ERR_BAD_LAYOUT;
-        }
-        if (g_first == ~0ull) g_first = lcur;
-        g_records += h_kept[c];
-        if (h_unm[c] && sg.first_unmapped == ~0ull) sg.first_unmapped = h_fu[c] + G.u_lo;
-        sg.n_unmapped += h_unm[c];
-        lcur = h_end[c];
-        ++c;
-        continue;
-      }
-      if (++rounds_total > 4096) {
-        if (err256) snprintf(err256, 256, "device decode: the record boundaries did not settle");
-        return MIDAS_SNPS_ERR_UNSUPPORTED;
-      }
-      const long long one = (long long)c;
-      DS_TRY(hipMemcpyAsync(wp.start + c, &lcur, 8, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(d_list, &one, 8, hipMemcpyHostToDevice, s));
-      DS_TRY(launch_bam_walk(wp, d_list, 1, s));
-      DS_TRY(hipMemcpyAsync(&h_end[c], wp.end + c, 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&h_kept[c], wp.kept + c, 4, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&h_unm[c], wp.unmapped + c, 4, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&h_fu[c], wp.first_unmapped + c, 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&h_bad[c], wp.bad + c, 4, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipStreamSynchronize(s));
-      h_start[c] = lcur;
-    }
-    if (lcur != ~0ull) {      // (else: a group that had to guess found no record boundary: the next one guesses too)
-      cur = lcur + G.u_lo;
-      sg.end = cur;
-    }
-    if (g_first != ~0ull && sg.first == ~0ull) sg.first = g_first + G.u_lo;
-    unsigned long long n_rec = 0;
-    for (long long c = 0; c < n_chunks; ++c) { h_base[(size_t)c] = n_rec; n_rec += h_kept[(size_t)c]; }
-    lap(3);
-    const long long n = (long long)n_rec;
-    if (n > 0) {
-      DS_TRY(hipMemcpyAsync(wp.start, h_start.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(wp.kept, h_kept.data(), (size_t)n_chunks * 4, hipMemcpyHostToDevice, s));
-      DS_TRY(hipMemcpyAsync(d_base, h_base.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-      // room in the result: from the records per inflated byte so far, + 3 %
-      if (!cols.p || (size_t)(N + n) > cols.cap) {
-        const double done = (double)(cur != ~0ull && cur > sg.from ? cur - sg.from : 1);
-        const double est = (double)(N + n) * std::max(1.0, span_total / done) * 1.03 + 4096.0;
-        if (cols.p) ++regrown;
-        const int32_t gst = grow_columns(std::max((size_t)(N + n), (size_t)est));
-        if (gst != MIDAS_SNPS_OK) return gst;
-        lap(6);
-      }
-      const size_t n1 = (size_t)n + 1;
-      unsigned long long* d_rec = reinterpret_cast<unsigned long long*>(take(n1 * 8));
-      unsigned long long* d_badrec = reinterpret_cast<unsigned long long*>(take(8));
-      long long* d_scan = reinterpret_cast<long long*>(take(bam_scan_scratch_bytes(n)));
-      if (!d_scan) { if (err256) snprintf(err256, 256, "device decode (streamed): a slot is too small for the record offsets"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-      BamColumnsParams cp;
-      cp.d = slot; cp.rec_off = d_rec; cp.n = n; cp.n_ref = n_ref;
-      cp.refid = reinterpret_cast<int32_t*>(cols.colp(1)) + N; cp.pos = reinterpret_cast<int32_t*>(cols.colp(2)) + N; cp.nm = reinterpret_cast<int32_t*>(cols.colp(3)) + N; cp.l_seq = reinterpret_cast<int32_t*>(cols.colp(4)) + N;
-      cp.mapq = reinterpret_cast<uint8_t*>(cols.colp(5)) + N; cp.flag = reinterpret_cast<uint16_t*>(cols.colp(6)) + N;
-      cp.seq_off = reinterpret_cast<long long*>(cols.colp(7)) + N; cp.qual_off = reinterpret_cast<long long*>(cols.colp(8)) + N; cp.cigar_off = reinterpret_cast<long long*>(cols.colp(9)) + N;
-      cp.unit_off = reinterpret_cast<long long*>(cols.colp(10)) + N;
-      cp.span = nullptr;
-      cp.bad_record = d_badrec;
-      for (int k = 0; k < 4; ++k) cp.base[k] = base[k];
-      DS_TRY(hipMemsetAsync(cp.bad_record, 0xFF, 8, s));
-      DS_TRY(launch_bam_offsets(wp, d_base, d_rec, s));
-      DS_TRY(launch_bam_columns(cp, d_scan, s));
-      unsigned long long h_bad_record = ~0ull;
-      long long ends[4] = {0, 0, 0, 0};
-      DS_TRY(hipMemcpyAsync(&h_bad_record, cp.bad_record, 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&ends[0], cp.seq_off + n, 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&ends[1], cp.qual_off + n, 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&ends[2], cp.cigar_off + n, 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipMemcpyAsync(&ends[3], cp.unit_off + n, 8, hipMemcpyDeviceToHost, s));
-      DS_TRY(hipStreamSynchronize(s));
-      lap(4);
-      if (h_bad_record != ~0ull) { *bad_record = (int64_t)h_bad_record + N; return MIDAS_SNPS_ERR_BAD_LAYOUT; }
-      if ((unsigned long long)ends[3] > kMaxDirectPayloadUnits) {
-        if (err256) snprintf(err256, 256, "device decode: %llu bytes of read payload exceed the 32 GiB the direct layout addresses", (unsigned long long)ends[3] * 8ull);
-        return MIDAS_SNPS_ERR_UNSUPPORTED;
-      }
-      if (!pay.p || (size_t)ends[3] > pay.cap_units) {
-        const double done = (double)(cur != ~0ull && cur > sg.from ? cur - sg.from : 1);
-        const double est = (double)ends[3] * std::max(1.0, span_total / done) * 1.03 + 65536.0;
-        if (pay.p) ++regrown;
-        const int32_t gst = grow_payload(std::max((size_t)ends[3], (size_t)std::min(est, (double)kMaxDirectPayloadUnits)));
-        if (gst != MIDAS_SNPS_OK) return gst;
-        lap(6);
-      }
-      BamDirectParams dp;
-      dp.stream = slot; dp.rec_off = d_rec; dp.n_records = n;
-      dp.pos = cp.pos; dp.nm = cp.nm; dp.unit_off = cp.unit_off;
-      dp.rec = reinterpret_cast<DirectRec*>(cols.colp(0)) + N; dp.payload = pay.p;
-      dp.read_base = N; dp.side_copy = 1;
-      // the most this group can reserve: every read an entry, its SEQ + QUAL (8-byte aligned) in data
-      const unsigned long long g_ent = (unsigned long long)n, g_bytes = (unsigned long long)(ends[0] - base[0]) + (unsigned long long)(ends[1] - base[1]) + 8ull * (unsigned long long)n;
-      for (int attempt = 0;; ++attempt) {
-        const unsigned long long n_ent = side.h.bump >> kDenseSideEntryShift, n_bytes = (side.h.bump & kDenseSideMaxField) << 3;
-        if (!dense_side_fits(n_ent + g_ent, (n_bytes + g_bytes) >> 3)) {       // (the bump's fields could carry: refuse, never lose a read)
-          if (err256) snprintf(err256, 256, "device decode (streamed): the exact copies of the reads the layout cannot hold exceed the side buffer's limits (%llu reads, %llu bytes)",
-                               n_ent + g_ent, n_bytes + g_bytes);
-          return MIDAS_SNPS_ERR_UNSUPPORTED;
-        }
-        dp.side = side.p;
-        DS_TRY(launch_bam_direct(dp, ctx->prop.multiProcessorCount, s));
-        DenseSide h{};
-        DS_TRY(hipMemcpyAsync(&h, side.p, sizeof h, hipMemcpyDeviceToHost, s));
-        DS_TRY(hipStreamSynchronize(s));
-        if (!(h.flags & kDenseSideOverflow)) { side.h = h; break; }
-        // no room for the group's exceptional reads: at least room for ALL of its reads' SEQ / QUAL behind what the groups before
-        // kept (twice the old room when that is more: a file of exceptional reads grows it a few times, not every group), and the
-        // group written again (the bump and the flags as they were in front of it)
-        if (attempt > 0) {
-          if (err256) snprintf(err256, 256, "device decode (streamed): group %zu found no room in a side buffer sized for all of its reads", g);
-          return MIDAS_SNPS_ERR_HIP;
-        }
-        const unsigned long long want_e = std::min(kDenseSideMaxField, std::max(n_ent + g_ent, 2ull * side.h.cap_entries));
-        const unsigned long long want_b = std::min(kDenseSideMaxField << 3, std::max(n_bytes + g_bytes, 2ull * side.h.cap_bytes));
-        const int32_t gs = grow_side((uint32_t)want_e, want_b);
-        if (gs != MIDAS_SNPS_OK) return gs;
-        if (trace) fprintf(stderr, "[device decode] streamed: group %zu: the side buffer grown to %llu reads, %llu bytes\n", g, want_e, want_b);
-      }
-      lap(5);
-      N += n;
-      for (int k = 0; k < 4; ++k) base[k] = ends[k];
-    }
-    {
-      std::lock_guard<std::mutex> lk(pipe.m);
-      pipe.decoded = (long long)g + 1;
-    }
-    pipe.cv.notify_all();
-    if (cur != ~0ull && cur >= seg_stop) break;       // (the wanted records end here: nothing of the groups behind is needed)
-  }
-  sg.n_records = N;
-  if (N == 0) {        // (no record at all: the caller's columns are empty; nothing stays on the device)
-    const HostColumns hc = alloc(sink, 0);
-    (void)hc;
-    res->n_records = 0; res->seq_bytes = 0; res->qual_bytes = 0; res->n_cigar = 0;
-    const int32_t g0 = grow_columns(1);
-    if (g0 != MIDAS_SNPS_OK) return g0;
-    const int32_t g1 = grow_payload(8);
-    if (g1 != MIDAS_SNPS_OK) return g1;
-    DS_TRY(hipMemsetAsync(cols.p, 0, cols.bytes, s));
-  }
-  DS_TRY(hipMemsetAsync(pay.p + (size_t)base[3] * 8, 0, 64, s));      // (a lane's 16-byte loads may overhang the last read)
-  {       // the uploader has nothing left to do: the ring is the copy-down's again
-    { std::lock_guard<std::mutex> lk(pipe.m); pipe.abort = true; }
-    pipe.cv.notify_all();
-    if (uploader.joinable()) uploader.join();
-    for (hipStream_t q : st.inf) DS_TRY(hipStreamSynchronize(q));
-  }
-  if (N > 0) {
-    const HostColumns hc = alloc(sink, N);
-    if (!hc.refid) { DS_TRY(hipStreamSynchronize(s)); return MIDAS_SNPS_OK; }
-    const int32_t dst = copy_to_host(ctx, hc.refid, reinterpret_cast<int32_t*>(cols.colp(1)), (size_t)N * 4);
-    if (dst != MIDAS_SNPS_OK) { if (err256) snprintf(err256, 256, "device decode: columns to host: %s", ctx->error_text().c_str()); return dst; }
-  }
-  DS_TRY(hipStreamSynchronize(s));
-  if (trace) {
-    const double total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    fprintf(stderr, "[device decode] streamed: %lld records in %.1f ms: waited for a group's launch %.1f (the uploader worked %.1f), for its decoder %.1f, walk %.1f, stitch %.1f, "
-                    "columns %.1f, direct layout %.1f, result grown %.1f (%d times), tables %.1f ms; %d chunk(s) walked again; result %.2f GB\n",
-            N, total_ms, laps[0], pipe.busy_ms, laps[1], laps[2], laps[3], laps[4], laps[5], laps[6], regrown, laps[7], rounds_total,
-            (double)(cols.bytes + pay.cap_units * 8) / 1e9);
-  }
-  res->n_records = N; res->seq_bytes = base[0]; res->qual_bytes = base[1]; res->n_cigar = base[2];
-  ResidentReads& rr = res->resident;
-  rr.rec = reinterpret_cast<DirectRec*>(cols.colp(0)); rr.payload = pay.p; rr.refid = reinterpret_cast<int32_t*>(cols.colp(1)); rr.pos = reinterpret_cast<int32_t*>(cols.colp(2)); rr.nm = reinterpret_cast<int32_t*>(cols.colp(3));
-  rr.l_seq = reinterpret_cast<int32_t*>(cols.colp(4)); rr.mapq = reinterpret_cast<uint8_t*>(cols.colp(5)); rr.flag = reinterpret_cast<uint16_t*>(cols.colp(6));
-  rr.seq_off = reinterpret_cast<int64_t*>(cols.colp(7)); rr.qual_off = reinterpret_cast<int64_t*>(cols.colp(8)); rr.cigar_off = reinterpret_cast<int64_t*>(cols.colp(9)); rr.unit_off = reinterpret_cast<int64_t*>(cols.colp(10));
-  rr.stream = nullptr; rr.rec_off = nullptr;       // (no inflated stream is kept: raw columns come out of the direct layout)
-  rr.payload_units = base[3];
-  rr.side = side.p;
-  rr.dense_flags = side.h.flags;
-  res->dev_owner = new TwoBuffers{cols.p, pay.p, side.p};
-  res->dev_free = two_buffers_free;
-  owned.keep = true;
-#undef DS_TRY
-  return MIDAS_SNPS_OK;
-}
-
-// DeviceDecoder::run (hostio.h): BGZF blocks of a BAM -- the whole file's, a rank's slice, or the runs that hold a rank's contigs --
-// decoded on the device: up, inflated, resolved and CRC-checked (bgzf_inflate.hip), records found and decoded (bam_walk.hip), SEQ /
-// QUAL / CIGAR cut out where the stream lies; the small columns are all that comes down.
-int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob* jobs, size_t n_jobs, uint64_t total, DecodeSegment* segs,
-                          size_t n_segs, const int64_t* ref_lens, int32_t n_ref, int payload, int extra, HostColumns (*alloc)(void*, int64_t),
-                          void* sink, DeviceDecodeResult* res, int64_t* bad_job, int64_t* bad_record, char* err256) {
-  midas_snps_ctx* ctx = static_cast<midas_snps_ctx*>(user);
-  *bad_job = -1;
-  *bad_record = -1;
-  auto hip_err = [&](hipError_t e, const char* what) {
-    if (err256) snprintf(err256, 256, "device decode: %s: %s", what, hipGetErrorString(e));
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP;
-  };
-#define DEC_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_err(e__, #call); } while (0)
-  std::lock_guard<std::mutex> g(ctx->device_mutex);
-  const bool trace = getenv("MIDAS_SNPS_TRACE") != nullptr;       // where the call spends its time, on stderr
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!trace) return;
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "[device decode] %-30s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
-    t_last = t;
-  };
-  DEC_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  // ---- a resident decode of ONE run of blocks that fills the device several times over: group by group (device_decode_stream) ----
-  if (payload == 2 && !extra && n_segs == 1 && segs[0].job_lo < segs[0].job_hi && segs[0].job_hi <= n_jobs) {
-    const size_t nb = segs[0].job_hi - segs[0].job_lo;
-    size_t group = 0;
-    int slots = 3;
-    const char* on = getenv("MIDAS_SNPS_DECODE_STREAM");
-    if (!on || atoi(on) != 0) {
-      // (half a device-fill of the decoder's workgroups a group: two groups' kernels run side by side, on alternating streams)
-      group = (size_t)std::max(64ll, bgzf_inflate_wave_blocks(ctx->prop.multiProcessorCount) / 2);
-      if (const char* e = getenv("MIDAS_SNPS_DECODE_GROUP_BLOCKS")) group = (size_t)std::max(1ll, atoll(e));
-      if (const char* e = getenv("MIDAS_SNPS_DECODE_SLOT_MB")) {        // a slot is ~2.5 x its blocks' inflated bytes (<= 64 KiB each)
-        const size_t cap_blocks = (size_t)std::max(16ll, atoll(e) * (1ll << 20) / (160ll << 10));
-        group = std::min(group, cap_blocks);
-      }
-      if (const char* e = getenv("MIDAS_SNPS_DECODE_SLOTS")) slots = std::max(1, std::min(4, atoi(e)));
-    }
-    if (group && nb > group + group / 4) {
-      const size_t K = (nb + group - 1) / group;
-      group = (nb + K - 1) / K;        // (equal groups, none above a wave)
-      const int32_t sst = device_decode_stream(ctx, comp_base, jobs, segs[0], group, slots, ref_lens, n_ref, alloc, sink, res, bad_job, bad_record, err256);
-      if (sst != kStreamFallback) return sst;
-      if (trace) fprintf(stderr, "[device decode] streamed decode gave up (a record longer than what a group keeps behind its end): one arena\n");
-      *bad_job = -1;
-      *bad_record = -1;
-    }
-  }
-  // ---- the compressed bytes: every segment's blocks are consecutive in the file, the segments go up back to back ----------
-  std::vector<size_t> seg_at(n_segs + 1, 0);      // where segment k's bytes start in the device's copy
-  for (size_t k = 0; k < n_segs; ++k) {
-    const DecodeSegment& sg = segs[k];
-    if (sg.job_lo >= sg.job_hi || sg.job_hi > n_jobs) { if (err256) snprintf(err256, 256, "device decode: empty segment"); return MIDAS_SNPS_ERR_INVALID_ARG; }
-    const size_t bytes = (size_t)(jobs[sg.job_hi - 1].cpos + jobs[sg.job_hi - 1].clen + 8 - jobs[sg.job_lo].cpos);
-    seg_at[k + 1] = seg_at[k] + bytes;
-  }
-  const size_t comp_bytes = seg_at[n_segs];
-  // ---- the arena: | inflated bytes | compressed bytes | blocks | status | crc | match lists |; everything behind the inflated
-  // bytes is scratch once the blocks are resolved, and the columns are laid over it
-  std::vector<InflateBlock> blocks(n_jobs);
-  std::vector<uint32_t> want(n_jobs);
-  unsigned long long n_match_room = 0;
-  for (size_t k = 0; k < n_segs; ++k) {
-    const uint64_t c0 = jobs[segs[k].job_lo].cpos;
-    for (size_t j = segs[k].job_lo; j < segs[k].job_hi; ++j) {
-      if (jobs[j].upos + jobs[j].ulen > total || jobs[j].cpos < c0) {
-        if (err256) snprintf(err256, 256, "device decode: block %lld lies outside the buffers", (long long)j);
-        return MIDAS_SNPS_ERR_INVALID_ARG;
-      }
-      const uint32_t cap = jobs[j].ulen / 8u + 16u;
-      blocks[j] = InflateBlock{(unsigned long long)(seg_at[k] + (jobs[j].cpos - c0)), jobs[j].upos, n_match_room, jobs[j].clen, jobs[j].ulen, cap, 0u};
-      want[j] = jobs[j].crc;
-      n_match_room += cap;
-    }
-  }
-  const size_t at_comp = up((size_t)total + 64), at_blocks = at_comp + up(comp_bytes + 512),
-               at_status = at_blocks + up(n_jobs * sizeof(InflateBlock)), at_crc = at_status + up(n_jobs * 8),
-               at_matches = at_crc + up(n_jobs * 4);
-  // (a BAM's columns are ~0.95 of its inflated bytes, the offsets and small columns ~0.2: the scratch must hold them too)
-  const size_t scratch_need = std::max(up(comp_bytes + 512) + up(n_jobs * sizeof(InflateBlock)) + up(n_jobs * 12) + up((size_t)n_match_room * 8),
-                                       (size_t)total + (size_t)total / 3 + ((size_t)16 << 20));
-  const size_t arena_bytes = at_comp + scratch_need;
-  bool pooled = false;
-  void* arena_p = ctx->arena->take(arena_bytes, &pooled);
-  if (!arena_p) { if (err256) snprintf(err256, 256, "device decode: out of device memory (%.1f GB)", (double)arena_bytes / 1e9); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-  struct Loan { std::shared_ptr<midas_arena_pool> pool; void* p; ~Loan() { if (p) pool->give(p); } } loan{ctx->arena, arena_p};
-  uint8_t* const base = static_cast<uint8_t*>(arena_p);
-  lap("arena");
-  // ---- blocks up, inflate, resolve, check ------------------------------------------------------------------------------------
-  DEC_TRY(hipMemcpyAsync(base + at_blocks, blocks.data(), n_jobs * sizeof(InflateBlock), hipMemcpyHostToDevice, s));
-  DEC_TRY(hipMemcpyAsync(base + at_crc, want.data(), n_jobs * 4, hipMemcpyHostToDevice, s));
-  DEC_TRY(hipMemsetAsync(base + at_comp + comp_bytes, 0, 512, s));
-  InflateParams ip;
-  ip.comp = base + at_comp;
-  ip.blocks = reinterpret_cast<const InflateBlock*>(base + at_blocks);
-  ip.n_blocks = (long long)n_jobs;
-  ip.out = base;
-  ip.status = reinterpret_cast<uint32_t*>(base + at_status);
-  ip.n_matches = reinterpret_cast<uint32_t*>(base + at_status) + n_jobs;
-  ip.matches = reinterpret_cast<unsigned long long*>(base + at_matches);
-  ip.want_crc = reinterpret_cast<const uint32_t*>(base + at_crc);
-  auto upload = [&](size_t dev_lo, size_t dev_hi) -> int32_t {      // the bytes [dev_lo, dev_hi) of the device's copy, segment by segment
-    for (size_t k = 0; k < n_segs; ++k) {
-      const size_t lo = std::max(dev_lo, seg_at[k]), hi = std::min(dev_hi, seg_at[k + 1]);
-      if (lo >= hi) continue;
-      const int32_t cst = copy_to_device_staged(ctx, base + at_comp + lo, comp_base + jobs[segs[k].job_lo].cpos + (lo - seg_at[k]), hi - lo, s);
-      if (cst != MIDAS_SNPS_OK) { if (err256) snprintf(err256, 256, "device decode: blocks to the device: %s", ctx->error_text().c_str()); return cst; }
-    }
-    return MIDAS_SNPS_OK;
-  };
-  // (Inflating a first group of blocks while the next group's bytes go up -- four groups, a stream each -- was built and
-  // measured: 216 ms against 188 ms for the whole decode of configs[2]'s BAM on the same box.  The copy threads and the
-  // link are slowed by the running kernels by more than the overlap wins.  One upload, one launch.)
-  {
-    const int32_t ust = upload(0, comp_bytes);
-    if (ust != MIDAS_SNPS_OK) return ust;
-  }
-  if (trace) {      // (phase by phase, each waited for)
-    DEC_TRY(hipStreamSynchronize(s)); lap("blocks up");
-    DEC_TRY(launch_bgzf_inflate(ip, s, 1)); DEC_TRY(hipStreamSynchronize(s)); lap("  inflate kernel");
-    DEC_TRY(launch_bgzf_inflate(ip, s, 2 | 8)); DEC_TRY(hipStreamSynchronize(s)); lap("  resolve kernel");
-    DEC_TRY(launch_bgzf_inflate(ip, s, 4)); DEC_TRY(hipStreamSynchronize(s)); lap("  crc kernel");
-  } else {
-    DEC_TRY(launch_bgzf_inflate(ip, s));
-  }
-  std::vector<uint32_t> status(n_jobs);
-  DEC_TRY(hipMemcpyAsync(status.data(), ip.status, n_jobs * 4, hipMemcpyDeviceToHost, s));
-  DEC_TRY(hipStreamSynchronize(s));
-  lap("blocks up, inflate, resolve, crc");
-  {   // the streams whose matches did not fit: again, with the bound's room
-    bool again = false;
-    const hipError_t ae = inflate_again(ip, blocks, want, status, s, &again);
-    if (ae != hipSuccess) return hip_err(ae, "streams decoded again");
-    if (again) lap("streams decoded again");
-  }
-  for (size_t k = 0; k < n_jobs; ++k) {
-    if (status[k] != 0u) {
-      *bad_job = (int64_t)k;
-      if (err256) snprintf(err256, 256, "corrupt BGZF block %lld (code %u)", (long long)k, status[k]);
-      return MIDAS_SNPS_ERR_BAD_LAYOUT;
-    }
-  }
-  // ---- the record walk: chunks of at most 32 KiB, laid out segment by segment over [from, stop) ---------------------------
-  const unsigned long long kChunk = 32768ull;
-  std::vector<unsigned long long> h_lo, h_hi, h_stop, h_limit, h_start;
-  std::vector<uint8_t> h_forced;
-  std::vector<size_t> seg_chunk(n_segs + 1, 0);
-  for (size_t k = 0; k < n_segs; ++k) {
-    const DecodeSegment& sg = segs[k];
-    const unsigned long long limit = jobs[sg.job_hi - 1].upos + jobs[sg.job_hi - 1].ulen;
-    const unsigned long long stop = sg.stop < limit ? sg.stop : limit;
-    for (unsigned long long lo = sg.from; lo < stop; lo += kChunk) {
-      h_lo.push_back(lo); h_hi.push_back(lo + kChunk < stop ? lo + kChunk : stop); h_stop.push_back(stop); h_limit.push_back(limit);
-      const bool first = lo == sg.from;
-      h_forced.push_back(first && sg.exact ? 1 : 0);
-      h_start.push_back(first && sg.exact ? sg.from : ~0ull);
-    }
-    seg_chunk[k + 1] = h_lo.size();
-  }
-  const long long n_chunks = (long long)h_lo.size();
-  uint8_t* const scratch = base + at_comp;
-  const size_t scratch_bytes = arena_bytes - at_comp;
-  size_t at = 0;
-  auto take = [&](size_t bytes) -> uint8_t* { uint8_t* q = scratch + at; at += up(bytes); return at <= scratch_bytes ? q : nullptr; };
-  const size_t nc1 = (size_t)(n_chunks > 0 ? n_chunks : 1);
-  BamWalkParams wp;
-  wp.d = base; wp.n_ref = n_ref; wp.n_chunks = n_chunks;
-  long long* d_ref_lens = reinterpret_cast<long long*>(take((size_t)(n_ref > 0 ? n_ref : 1) * 8));
-  unsigned long long* d_lo = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  unsigned long long* d_hi = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  unsigned long long* d_stop = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  unsigned long long* d_limit = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  uint8_t* d_forced = take(nc1);
-  wp.start = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  wp.end = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  wp.kept = reinterpret_cast<uint32_t*>(take(nc1 * 4));
-  wp.unmapped = reinterpret_cast<uint32_t*>(take(nc1 * 4));
-  wp.first_unmapped = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  wp.bad = reinterpret_cast<uint32_t*>(take(nc1 * 4));
-  unsigned long long* d_base = reinterpret_cast<unsigned long long*>(take(nc1 * 8));
-  long long* d_list = reinterpret_cast<long long*>(take(4096 * 8));
-  if (!d_list) { if (err256) snprintf(err256, 256, "device decode: the arena is too small for the walk"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-  wp.lo = d_lo; wp.hi = d_hi; wp.stop = d_stop; wp.limit = d_limit; wp.forced = d_forced; wp.ref_lens = d_ref_lens;
-  if (n_ref > 0) DEC_TRY(hipMemcpyAsync(d_ref_lens, ref_lens, (size_t)n_ref * 8, hipMemcpyHostToDevice, s));
-  std::vector<unsigned long long> h_end(nc1), h_base(nc1), h_fu(nc1);
-  std::vector<uint32_t> h_kept(nc1), h_bad(nc1), h_unm(nc1);
-  if (n_chunks > 0) {
-    DEC_TRY(hipMemcpyAsync(d_lo, h_lo.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_hi, h_hi.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_stop, h_stop.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_limit, h_limit.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_forced, h_forced.data(), (size_t)n_chunks, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(wp.start, h_start.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(launch_bam_walk(wp, nullptr, 0, s));
-    DEC_TRY(hipMemcpyAsync(h_start.data(), wp.start, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s));
-    DEC_TRY(hipMemcpyAsync(h_end.data(), wp.end, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s));
-    DEC_TRY(hipMemcpyAsync(h_kept.data(), wp.kept, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s));
-    DEC_TRY(hipMemcpyAsync(h_unm.data(), wp.unmapped, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s));
-    DEC_TRY(hipMemcpyAsync(h_fu.data(), wp.first_unmapped, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, s));
-    DEC_TRY(hipMemcpyAsync(h_bad.data(), wp.bad, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, s));
-    DEC_TRY(hipStreamSynchronize(s));
-  }
-  lap("walk (guesses)");
-  // stitch every segment in order; a chunk whose guess the chain does not hit is walked again from where the chain stands
-  int rounds = 0;
-  for (size_t k = 0; k < n_segs; ++k) {
-    DecodeSegment& sg = segs[k];
-    sg.first = ~0ull; sg.n_records = 0; sg.n_unmapped = 0; sg.first_unmapped = ~0ull;
-    unsigned long long cur = sg.exact ? sg.from : ~0ull;
-    const unsigned long long limit = jobs[sg.job_hi - 1].upos + jobs[sg.job_hi - 1].ulen;
-    sg.end = sg.stop < limit ? sg.stop : limit;
-    for (size_t c = seg_chunk[k]; c < seg_chunk[k + 1];) {
-      if (cur == ~0ull) {            // (a guessed first record: the first chunk that found a boundary gives it)
-        if (h_start[c] == ~0ull) { h_kept[c] = 0u; h_unm[c] = 0u; ++c; continue; }
-        cur = h_start[c];
-      }
-      if (cur >= h_hi[c] || cur + 4 > h_limit[c]) { h_kept[c] = 0u; h_unm[c] = 0u; h_start[c] = ~0ull; ++c; continue; }   // no record starts in this chunk
-      if (h_start[c] == cur) {
-        if (h_bad[c]) { *bad_record = -2; return MIDAS_SNPS_ERR_BAD_LAYOUT; }
-        if (sg.first == ~0ull) sg.first = cur;
-        sg.n_records += h_kept[c];
-        if (h_unm[c] && sg.first_unmapped == ~0ull) sg.first_unmapped = h_fu[c];
-        sg.n_unmapped += h_unm[c];
-        cur = h_end[c];
-        ++c;
-        continue;
-      }
-      if (++rounds > 4096) {
-        if (err256) snprintf(err256, 256, "device decode: the record boundaries did not settle");
-        return MIDAS_SNPS_ERR_UNSUPPORTED;
-      }
-      const long long one = (long long)c;
-      DEC_TRY(hipMemcpyAsync(wp.start + c, &cur, 8, hipMemcpyHostToDevice, s));
-      DEC_TRY(hipMemcpyAsync(d_list, &one, 8, hipMemcpyHostToDevice, s));
-      DEC_TRY(launch_bam_walk(wp, d_list, 1, s));
-      DEC_TRY(hipMemcpyAsync(&h_end[c], wp.end + c, 8, hipMemcpyDeviceToHost, s));
-      DEC_TRY(hipMemcpyAsync(&h_kept[c], wp.kept + c, 4, hipMemcpyDeviceToHost, s));
-      DEC_TRY(hipMemcpyAsync(&h_unm[c], wp.unmapped + c, 4, hipMemcpyDeviceToHost, s));
-      DEC_TRY(hipMemcpyAsync(&h_fu[c], wp.first_unmapped + c, 8, hipMemcpyDeviceToHost, s));
-      DEC_TRY(hipMemcpyAsync(&h_bad[c], wp.bad + c, 4, hipMemcpyDeviceToHost, s));
-      DEC_TRY(hipStreamSynchronize(s));
-      h_start[c] = cur;
-    }
-    if (cur != ~0ull) sg.end = cur;
-  }
-  if (rounds && trace) fprintf(stderr, "[device decode] %d chunk(s) walked again\n", rounds);
-  unsigned long long n_rec = 0;
-  for (long long c = 0; c < n_chunks; ++c) { h_base[(size_t)c] = n_rec; n_rec += h_kept[(size_t)c]; }
-  if (n_chunks > 0) {
-    DEC_TRY(hipMemcpyAsync(wp.start, h_start.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(wp.kept, h_kept.data(), (size_t)n_chunks * 4, hipMemcpyHostToDevice, s));
-    DEC_TRY(hipMemcpyAsync(d_base, h_base.data(), (size_t)n_chunks * 8, hipMemcpyHostToDevice, s));
-  }
-  lap("stitch");
-  const long long n = (long long)n_rec;
-  const size_t n1 = (size_t)n + 1;
-  unsigned long long* d_rec = reinterpret_cast<unsigned long long*>(take(n1 * 8));
-  BamColumnsParams cp;
-  cp.d = base; cp.rec_off = d_rec; cp.n = n; cp.n_ref = n_ref;
-  cp.refid = reinterpret_cast<int32_t*>(take(n1 * 4)); cp.pos = reinterpret_cast<int32_t*>(take(n1 * 4));
-  cp.nm = reinterpret_cast<int32_t*>(take(n1 * 4)); cp.l_seq = reinterpret_cast<int32_t*>(take(n1 * 4));
-  cp.mapq = take(n1); cp.flag = reinterpret_cast<uint16_t*>(take(n1 * 2));
-  cp.seq_off = reinterpret_cast<long long*>(take(n1 * 8)); cp.qual_off = reinterpret_cast<long long*>(take(n1 * 8));
-  cp.cigar_off = reinterpret_cast<long long*>(take(n1 * 8));
-  cp.span = extra ? reinterpret_cast<int32_t*>(take(n1 * 4)) : nullptr;
-  cp.unit_off = payload == 2 ? reinterpret_cast<long long*>(take(n1 * 8)) : nullptr;
-  cp.bad_record = reinterpret_cast<unsigned long long*>(take(8));
-  long long* d_scan = reinterpret_cast<long long*>(take(bam_scan_scratch_bytes(n)));
-  if (!d_scan) { if (err256) snprintf(err256, 256, "device decode: the arena is too small for the columns"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-  DEC_TRY(hipMemsetAsync(cp.bad_record, 0xFF, 8, s));
-  DEC_TRY(launch_bam_offsets(wp, d_base, d_rec, s));
-  DEC_TRY(launch_bam_columns(cp, d_scan, s));
-  unsigned long long h_bad_record = ~0ull;
-  long long ends[4] = {0, 0, 0, 0};
-  DEC_TRY(hipMemcpyAsync(&h_bad_record, cp.bad_record, 8, hipMemcpyDeviceToHost, s));
-  DEC_TRY(hipMemcpyAsync(&ends[0], cp.seq_off + n, 8, hipMemcpyDeviceToHost, s));
-  DEC_TRY(hipMemcpyAsync(&ends[1], cp.qual_off + n, 8, hipMemcpyDeviceToHost, s));
-  DEC_TRY(hipMemcpyAsync(&ends[2], cp.cigar_off + n, 8, hipMemcpyDeviceToHost, s));
-  if (cp.unit_off) DEC_TRY(hipMemcpyAsync(&ends[3], cp.unit_off + n, 8, hipMemcpyDeviceToHost, s));
-  DEC_TRY(hipStreamSynchronize(s));
-  lap("offsets, columns, scans");
-  if (h_bad_record != ~0ull) { *bad_record = (int64_t)h_bad_record; return MIDAS_SNPS_ERR_BAD_LAYOUT; }
-  const int64_t sb = ends[0], qb = ends[1], nc = ends[2];
-  if (payload == 2) {
-    // ---- resident: the records in the pileup kernel's own layout, ONE copy of every record's [cigar][seq][qual] run; every
-    // column stays where it was decoded and only refID comes down (the host groups the records by contig with it) -------------
-    const unsigned long long units = (unsigned long long)ends[3];
-    if (units > kMaxDirectPayloadUnits) {
-      if (err256) snprintf(err256, 256, "device decode: %llu bytes of read payload exceed the 32 GiB the direct layout addresses", units * 8ull);
-      return MIDAS_SNPS_ERR_UNSUPPORTED;
-    }
-    DirectRec* d_drec = reinterpret_cast<DirectRec*>(take((n1 + 1) * sizeof(DirectRec)));
-    uint8_t* d_pay = take((size_t)units * 8 + 64);
-    if (!d_pay) { if (err256) snprintf(err256, 256, "device decode: the arena is too small for the direct layout"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-    DEC_TRY(hipMemsetAsync(d_pay + (size_t)units * 8, 0, 64, s));       // (a lane's 16-byte loads may overhang the last read)
-    // (the inflated stream stays: raw columns are cut out of it, the side buffer only collects the producer's flags)
-    DenseSide* d_side = reinterpret_cast<DenseSide*>(take(sizeof(DenseSide)));
-    if (!d_side) { if (err256) snprintf(err256, 256, "device decode: the arena is too small for the direct layout"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-    DEC_TRY(hipMemsetAsync(d_side, 0, sizeof(DenseSide), s));
-    BamDirectParams dp;
-    dp.stream = base; dp.rec_off = d_rec; dp.n_records = n;
-    dp.pos = cp.pos; dp.nm = cp.nm; dp.unit_off = cp.unit_off;
-    dp.rec = d_drec; dp.payload = d_pay;
-    dp.side = d_side; dp.read_base = 0; dp.side_copy = 0;
-    DEC_TRY(launch_bam_direct(dp, ctx->prop.multiProcessorCount, s));
-    DenseSide h_side{};
-    DEC_TRY(hipMemcpyAsync(&h_side, d_side, sizeof h_side, hipMemcpyDeviceToHost, s));
-    const HostColumns hc = alloc(sink, n);
-    if (!hc.refid) { DEC_TRY(hipStreamSynchronize(s)); return MIDAS_SNPS_OK; }      // (the caller reports its own out-of-memory)
-    if (n > 0) {
-      const int32_t dst = copy_to_host(ctx, hc.refid, cp.refid, (size_t)n * 4);
-      if (dst != MIDAS_SNPS_OK) { if (err256) snprintf(err256, 256, "device decode: columns to host: %s", ctx->error_text().c_str()); return dst; }
-    }
-    DEC_TRY(hipStreamSynchronize(s));
-    lap("direct layout, refID down");
-    res->n_records = n; res->seq_bytes = sb; res->qual_bytes = qb; res->n_cigar = nc;
-    ResidentReads& rr = res->resident;
-    rr.rec = d_drec; rr.payload = d_pay; rr.refid = cp.refid; rr.pos = cp.pos; rr.nm = cp.nm; rr.l_seq = cp.l_seq; rr.mapq = cp.mapq; rr.flag = cp.flag;
-    rr.seq_off = reinterpret_cast<int64_t*>(cp.seq_off); rr.qual_off = reinterpret_cast<int64_t*>(cp.qual_off);
-    rr.cigar_off = reinterpret_cast<int64_t*>(cp.cigar_off); rr.unit_off = reinterpret_cast<int64_t*>(cp.unit_off);
-    rr.stream = base; rr.rec_off = reinterpret_cast<const uint64_t*>(d_rec);
-    rr.payload_units = (int64_t)units;
-    rr.dense_flags = h_side.flags;
-    res->dev_owner = new ArenaLoan{loan.pool, loan.p};       // everything lives in the arena: it stays lent until the handle is closed
-    res->dev_free = arena_loan_free;
-    loan.p = nullptr;
-    return MIDAS_SNPS_OK;
-  }
-  // ---- SEQ / QUAL / CIGAR cut out of the stream, behind everything taken so far ---------------------------------------------
-  uint8_t *d_seq = nullptr, *d_qual = nullptr, *d_cig = nullptr;
-  struct Own { void* p = nullptr; ~Own() { if (p) (void)hipFree(p); } } own;
-  if (payload) {
-    d_seq = take((size_t)sb + 64);
-    d_qual = take((size_t)qb + 64);
-    d_cig = take((size_t)nc * 4 + 64);
-    if (!d_cig) {       // (the scratch cannot hold them: a buffer of their own)
-      const size_t need = up((size_t)sb + 64) + up((size_t)qb + 64) + up((size_t)nc * 4 + 64);
-      DEC_TRY(hipMalloc(&own.p, need));
-      d_seq = static_cast<uint8_t*>(own.p);
-      d_qual = d_seq + up((size_t)sb + 64);
-      d_cig = d_qual + up((size_t)qb + 64);
-    }
-    DEC_TRY(hipMemsetAsync(d_cig + (size_t)nc * 4, 0, 64, s));
-    PayloadParams pp;
-    pp.stream = base;
-    pp.rec_off = d_rec;
-    pp.n_records = n;
-    pp.seq_off = cp.seq_off; pp.qual_off = cp.qual_off; pp.cigar_off = cp.cigar_off;
-    pp.seq4 = d_seq; pp.qual = d_qual; pp.cigar = reinterpret_cast<uint32_t*>(d_cig);
-    // (Launched on a stream of its own so that the small columns go down the link while it runs: measured, 24.5 ms against
-    // 20.3 ms one behind the other -- the copy kernels and this one slow each other by more than the overlap wins.)
-    DEC_TRY(launch_bam_payload(pp, ctx->prop.multiProcessorCount, s));
-  }
-  // ---- the small columns down ---------------------------------------------------------------------------------------------
-  const HostColumns hc = alloc(sink, n);
-  if (!hc.cigar_off) { DEC_TRY(hipStreamSynchronize(s)); return MIDAS_SNPS_OK; }      // (the caller reports its own out-of-memory)
-  auto down = [&](void* dst, const void* src, size_t bytes) -> int32_t { return bytes && dst ? copy_to_host(ctx, dst, src, bytes) : MIDAS_SNPS_OK; };
-  int32_t st = MIDAS_SNPS_OK;
-  const std::pair<void*, std::pair<const void*, size_t>> cols[] = {
-      {hc.refid, {cp.refid, (size_t)n * 4}}, {hc.pos, {cp.pos, (size_t)n * 4}}, {hc.nm, {cp.nm, (size_t)n * 4}}, {hc.l_seq, {cp.l_seq, (size_t)n * 4}},
-      {hc.mapq, {cp.mapq, (size_t)n}}, {hc.flag, {cp.flag, (size_t)n * 2}}, {hc.seq_off, {cp.seq_off, n1 * 8}}, {hc.qual_off, {cp.qual_off, n1 * 8}},
-      {hc.cigar_off, {cp.cigar_off, n1 * 8}}, {extra ? hc.span : nullptr, {cp.span, (size_t)n * 4}}, {extra ? hc.rec_off : nullptr, {d_rec, (size_t)n * 8}}};
-  for (const auto& c : cols) {
-    st = down(c.first, c.second.first, c.second.second);
-    if (st != MIDAS_SNPS_OK) { if (err256) snprintf(err256, 256, "device decode: columns to host: %s", ctx->error_text().c_str()); return st; }
-  }
-  DEC_TRY(hipStreamSynchronize(s));
-  lap("payload cut, small columns down");
-#undef DEC_TRY
-  res->n_records = n; res->seq_bytes = sb; res->qual_bytes = qb; res->n_cigar = nc;
-  res->dev_seq = d_seq; res->dev_qual = d_qual; res->dev_cigar = d_cig;
-  if (!payload) return MIDAS_SNPS_OK;       // (the arena goes back with `loan`)
-  if (own.p) {        // the columns have a buffer of their own: the arena goes back now
-    res->dev_owner = own.p;
-    res->dev_free = device_free;
-    own.p = nullptr;
-  } else {            // the columns live in the arena: it stays lent until the handle is closed
-    // (and with them the small columns the host has just been given: a batch made from those host arrays need not send them up
-    // again -- midas_arena_pool::find_twin, midas_snps_batch_create)
-    for (const auto& c : cols)
-      if (c.first && c.second.first != static_cast<const void*>(d_rec)) loan.pool->add_twin(c.first, c.second.first, c.second.second, loan.p);
-    res->dev_owner = new ArenaLoan{loan.pool, loan.p};
-    res->dev_free = arena_loan_free;
-    loan.p = nullptr;
-  }
-  return MIDAS_SNPS_OK;
-}
-}  // namespace
-
-int32_t midas_bam_load_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
-                              int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
-  if (!ctx || !path || !out) return MIDAS_SNPS_ERR_INVALID_ARG;
-  const DeviceDecoder dec{ctx, device_decode_run};
-  const int32_t st = bam_decode_on_device(path, &dec, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
-  if (st != MIDAS_SNPS_ERR_UNSUPPORTED) return st;
-  return bam_load_device_host_walk(path, ctx, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);      // (boundaries not settled: the host walks)
-}
-
-int32_t midas_bam_load_resident(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* sum_l_seq, char* err256) {
-  if (!ctx || !path || !out) return MIDAS_SNPS_ERR_INVALID_ARG;
-  const DeviceDecoder dec{ctx, device_decode_run};
-  int64_t qb = 0;
-  const int32_t st = bam_decode_on_device(path, &dec, out, n_reads, nullptr, &qb, nullptr, err256, 2);
-  if (sum_l_seq) *sum_l_seq = qb;       // (QUAL holds one byte per base)
-  return st;
-}
-
-int32_t midas_bam_load_ranges_resident(midas_bam* bam, midas_snps_ctx* ctx, int32_t n_ranges, const int64_t* range_begin,
-                                       const int64_t* range_end, int64_t* n_reads, int64_t* sum_l_seq, char* err256) {
-  if (!bam || !ctx) return MIDAS_SNPS_ERR_INVALID_ARG;
-  const DeviceDecoder dec{ctx, device_decode_run};
-  int64_t qb = 0;
-  const int32_t st = bam_load_ranges_on_device(bam, &dec, n_ranges, range_begin, range_end, n_reads, nullptr, &qb, nullptr, err256, 2);
-  if (sum_l_seq) *sum_l_seq = qb;
-  return st;
-}
-
-int32_t midas_bam_is_resident(const midas_bam* bam) { return bam_resident(bam, nullptr, nullptr, nullptr, nullptr) ? 1 : 0; }
-
-// The fall-back of a resident handle: the three payload columns cut out of the inflated stream it still holds (a buffer of
-// their own), the small columns brought down -- afterwards the handle answers midas_bam_columns as after midas_bam_load_device.
-int32_t midas_bam_resident_to_columns(midas_bam* bam, midas_snps_ctx* ctx, int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
-  if (!bam || !ctx) return MIDAS_SNPS_ERR_INVALID_ARG;
-  int64_t n = 0, sb = 0, qb = 0, nc = 0;
-  const midas::ResidentReads* rr = bam_resident(bam, &n, &sb, &qb, &nc);
-  if (!rr) { if (err256) snprintf(err256, 256, "the BAM handle holds no device-resident records"); return MIDAS_SNPS_ERR_INVALID_ARG; }
-  if (seq_bytes) *seq_bytes = sb;
-  if (qual_bytes) *qual_bytes = qb;
-  if (n_cigar) *n_cigar = nc;
-  if (midas_bam_payload_on_device(bam)) return MIDAS_SNPS_OK;         // (done before)
-  auto hip_err = [&](hipError_t e, const char* what) {
-    if (err256) snprintf(err256, 256, "resident BAM to columns: %s: %s", what, hipGetErrorString(e));
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP;
-  };
-#define RC_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hip_err(e__, #call); } while (0)
-  std::lock_guard<std::mutex> g(ctx->device_mutex);
-  RC_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t at_q = up((size_t)sb + 64), at_c = at_q + up((size_t)qb + 64), bytes = at_c + up((size_t)nc * 4 + 64);
-  struct Own { void* p = nullptr; ~Own() { if (p) (void)hipFree(p); } } own;
-  RC_TRY(hipMalloc(&own.p, bytes));
-  uint8_t* base = static_cast<uint8_t*>(own.p);
-  RC_TRY(hipMemsetAsync(base + sb, 0, 64, s));
-  RC_TRY(hipMemsetAsync(base + at_q + qb, 0, 64, s));
-  RC_TRY(hipMemsetAsync(base + at_c + (size_t)nc * 4, 0, 64, s));
-  PayloadParams pp;
-  pp.stream = rr->stream;
-  pp.rec_off = reinterpret_cast<const unsigned long long*>(rr->rec_off);
-  if (!rr->stream) {      // (a streamed decode: out of the direct layout, the side buffer's exact copies over the decoded bytes)
-    pp.stream = rr->payload; pp.drec = static_cast<const DirectRec*>(rr->rec);
-    pp.side = static_cast<const DenseSide*>(rr->side); pp.side_first = 0;
-  }
-  pp.n_records = n;
-  pp.seq_off = reinterpret_cast<const long long*>(rr->seq_off); pp.qual_off = reinterpret_cast<const long long*>(rr->qual_off);
-  pp.cigar_off = reinterpret_cast<const long long*>(rr->cigar_off);
-  pp.seq4 = base; pp.qual = base + at_q; pp.cigar = reinterpret_cast<uint32_t*>(base + at_c);
-  RC_TRY(launch_bam_payload(pp, ctx->prop.multiProcessorCount, s));
-  HostColumns hc{};
-  if (!bam_alloc_host_columns(bam, n, &hc)) { if (err256) snprintf(err256, 256, "resident BAM to columns: out of host memory"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
-  const size_t n1 = (size_t)n + 1;
-  const std::pair<void*, std::pair<const void*, size_t>> cols[] = {
-      {hc.pos, {rr->pos, (size_t)n * 4}}, {hc.nm, {rr->nm, (size_t)n * 4}}, {hc.l_seq, {rr->l_seq, (size_t)n * 4}}, {hc.mapq, {rr->mapq, (size_t)n}},
-      {hc.flag, {rr->flag, (size_t)n * 2}}, {hc.seq_off, {rr->seq_off, n1 * 8}}, {hc.qual_off, {rr->qual_off, n1 * 8}}, {hc.cigar_off, {rr->cigar_off, n1 * 8}}};
-  for (const auto& c : cols) {
-    if (!c.second.second) continue;
-    const int32_t st = copy_to_host(ctx, c.first, c.second.first, c.second.second);
-    if (st != MIDAS_SNPS_OK) { if (err256) snprintf(err256, 256, "resident BAM to columns: %s", ctx->error_text().c_str()); return st; }
-  }
-  // (refID is in the handle's host memory already, and stays there: the caller holds views of it)
-  RC_TRY(hipStreamSynchronize(s));
-#undef RC_TRY
-  bam_resident_became_columns(bam, base, base + at_q, base + at_c, own.p, device_free);
-  own.p = nullptr;
-  return MIDAS_SNPS_OK;
-}
-
 int32_t midas_snps_copy_from_device(midas_snps_ctx* ctx, void* dst, const void* src, int64_t bytes) {
   if (!ctx || bytes < 0 || (bytes > 0 && (!dst || !src))) return MIDAS_SNPS_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> g(ctx->device_mutex);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   return copy_to_host(ctx, dst, src, (size_t)bytes);
-}
-
-int32_t midas_bam_load_ranges_device(midas_bam* bam, midas_snps_ctx* ctx, int32_t n_ranges, const int64_t* range_begin,
-                                     const int64_t* range_end, int64_t* n_reads, int64_t* seq_bytes, int64_t* qual_bytes,
-                                     int64_t* n_cigar, char* err256) {
-  if (!ctx) return MIDAS_SNPS_ERR_INVALID_ARG;
-  const DeviceDecoder dec{ctx, device_decode_run};
-  const int32_t st = bam_load_ranges_on_device(bam, &dec, n_ranges, range_begin, range_end, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
-  if (st != MIDAS_SNPS_ERR_UNSUPPORTED) return st;
-  InflateUser iu{ctx};       // (boundaries not settled on the device: its inflater, the host's walk)
-  const BlockInflater inf{&iu, device_inflate};
-  return bam_load_ranges_with(bam, &inf, n_ranges, range_begin, range_end, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
-}
-
-int32_t midas_bam_open_slice_device(const char* path, int32_t slice, int32_t n_slices, midas_snps_ctx* ctx, midas_bam** out, char* err256) {
-  if (!ctx) return MIDAS_SNPS_ERR_INVALID_ARG;
-  const DeviceDecoder dec{ctx, device_decode_run};
-  return bam_open_slice_with(path, slice, n_slices, &dec, out, err256);
 }
 
 int32_t midas_snps_set_row_coder(midas_snps_ctx* ctx, int32_t coder) {

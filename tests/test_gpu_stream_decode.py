@@ -1,4 +1,4 @@
-"""The streamed device decode (snps_abi.hip device_decode_stream): a BAM of several device-fills of BGZF blocks decoded resident
+"""The streamed device decode (bam_device.hip device_decode_stream): a BAM of several device-fills of BGZF blocks decoded resident
 GROUP BY GROUP -- upload of group g + 1 under the kernels of group g, the columns and the direct layout of every group written
 behind those of the groups before it -- instead of in one arena of ~2.3 x the file's inflated bytes.  The reference streams the
 file record by record behind pysam.AlignmentFile (midas/run/snps.py:186-199): however the device cuts the file up, the records,
@@ -7,14 +7,16 @@ their order and every count must be those of the one-arena decode and of the hos
 The groups are forced small here (MIDAS_SNPS_DECODE_GROUP_BLOCKS) so that a BAM of a few hundred blocks is many groups: records
 that straddle group borders at every border, one / two / three slots, the result's arrays grown after a first estimate that is
 short, unmapped records, a damaged block in a late group, a record longer than what a group keeps behind its end (the decode
-falls back to one arena), ranges of a rank."""
+falls back to one arena), ranges of a rank; and blocks that need the inflater's second pass, through every decode path."""
 import os
+import struct
 
 import numpy as np
 import pytest
 
 from midas_amd import abi, bam, synth
 from oracle import c_oracle
+from tests import deflate_tokens
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -218,3 +220,95 @@ def test_a_ranks_range_is_streamed_too(ctx, tmp_path, monkeypatch, capfd):
         assert total == host.n_reads
         np.testing.assert_array_equal(np.concatenate(got_refid), refid_h)
         np.testing.assert_array_equal(np.concatenate(got_pos), host.pos)
+
+
+def _bgzf_blocks(blob):
+    """(offset of the DEFLATE stream, its length, the inflated length, its CRC-32) of every BGZF block of a file but the empty last one"""
+    out, p = [], 0
+    while p < len(blob):
+        size = int.from_bytes(blob[p + 16:p + 18], "little") + 1
+        crc, isize = struct.unpack("<II", blob[p + size - 8:p + size])
+        if isize:
+            out.append((p + 18, size - 26, isize, crc))
+        p += size
+    return out
+
+
+def _columns_of_stream(data):
+    """an inflated BAM walked record by record on the host, in Python: the columns of abi._SOA_DTYPES"""
+    l_text, = struct.unpack_from("<i", data, 4)
+    p = 8 + l_text
+    n_ref, = struct.unpack_from("<i", data, p)
+    p += 4
+    for _ in range(n_ref):
+        l_name, = struct.unpack_from("<i", data, p)
+        p += 8 + l_name
+    cols = {k: [] for k in ("pos", "mapq", "flag", "nm", "l_seq")}
+    seq4, qual, cigar = [], [], []
+    while p < len(data):
+        size, _refid, pos, l_name, mapq, _bin, n_cig, flag, l_seq = struct.unpack_from("<iiiBBHHHI", data, p)
+        q = p + 36 + l_name
+        cigar.append(np.frombuffer(data, "<u4", n_cig, q))
+        q += 4 * n_cig
+        seq4.append(np.frombuffer(data, np.uint8, (l_seq + 1) // 2, q))
+        q += (l_seq + 1) // 2
+        qual.append(np.frombuffer(data, np.uint8, l_seq, q))
+        q += l_seq
+        assert data[q:q + 3] == b"NMC"          # (the writer's first tag)
+        for k, v in zip(cols, (pos, mapq, flag, data[q + 3], l_seq)):
+            cols[k].append(v)
+        p += 4 + size
+    off = lambda parts: np.concatenate([[0], np.cumsum([len(x) for x in parts])]).astype(np.int64)
+    return dict(cols, seq_off=off(seq4), qual_off=off(qual), cigar_off=off(cigar), seq4=np.concatenate(seq4), qual=np.concatenate(qual),
+                cigar=np.concatenate(cigar))
+
+
+def test_blocks_that_need_the_second_inflate_pass_through_every_decode(ctx, tmp_path, monkeypatch, capfd):
+    """Read names of many short tokens from a small dictionary make blocks of almost nothing but short matches: more than the
+    decoder's first-pass room for them (bgzf_inflate.hip: 4 + matches + ceil(literals / 4) dwords against 2 * (ulen / 8 + 16)), so
+    the blocks are decoded again with the bound's room -- by the inflater on its own, by the one-arena decode (which says so in its
+    trace) and, group by group, by the streamed decode.  Whatever the path, the columns are the host decode's."""
+    contigs, reads = synth.make_dataset(n_species=1, contigs_per_species=2, contig_len=20000, n_reads=3000, read_len=20, seed=211)
+    rng = np.random.default_rng(3)
+    alphabet = np.frombuffer(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+-", np.uint8)
+    words = alphabet[rng.integers(0, 64, (400, 3))]
+    names = [words[rng.integers(0, 400, 84)].tobytes().decode() for _ in range(reads.n_reads)]
+    path = _bam_of(tmp_path, contigs, reads, name="names.bam", names=names)
+    blob = open(path, "rb").read()
+    blocks = _bgzf_blocks(blob)
+    assert len(blocks) == 16
+    # the fixture's guard, on the host: the tokens of every block counted against the first-pass room
+    over = 0
+    for at, clen, ulen, _ in blocks:
+        tokens = deflate_tokens.parse(blob[at:at + clen]).tokens
+        matches = sum(1 for t in tokens if type(t) is tuple)
+        over += 4 + matches + (len(tokens) - matches + 3) // 4 > 2 * (ulen // 8 + 16)
+    assert over >= 1, over
+    _, _, refid_h, host = abi.read_bam(path)
+
+    def same(got, what):
+        for k in abi._SOA_DTYPES:
+            np.testing.assert_array_equal(getattr(host, k), got[k] if isinstance(got, dict) else getattr(got, k), err_msg="%s: %s" % (what, k))
+
+    monkeypatch.setenv("MIDAS_SNPS_TRACE", "1")
+    monkeypatch.setenv("MIDAS_SNPS_DECODE_STREAM", "0")
+    _, _, refid_a, arena = abi.read_bam(path, ctx, resident=True)
+    err = capfd.readouterr().err
+    assert "[device decode] streams decoded again" in err, err         # the second pass ran
+    assert not any(ln.startswith("[device decode] streamed:") for ln in err.splitlines())
+    np.testing.assert_array_equal(refid_h, refid_a)
+    same(ctx.fetch_payload(arena), "one arena")
+    monkeypatch.setenv("MIDAS_SNPS_DECODE_STREAM", "1")
+    monkeypatch.setenv("MIDAS_SNPS_DECODE_GROUP_BLOCKS", "4")
+    monkeypatch.setenv("MIDAS_SNPS_DECODE_SLOTS", "2")
+    _, _, refid_s, res = abi.read_bam(path, ctx, resident=True)
+    assert _streamed(capfd) >= 3
+    np.testing.assert_array_equal(refid_h, refid_s)
+    same(ctx.fetch_payload(res), "streamed")
+    _, _, refid_d, dev = abi.read_bam(path, ctx)
+    np.testing.assert_array_equal(refid_h, refid_d)
+    same(dev, "inflated on the device, walked by the host")
+    upos = np.concatenate([[0], np.cumsum([b[2] for b in blocks])])
+    out = ctx.inflate_blocks(blob, [b[0] for b in blocks], [b[1] for b in blocks], upos[:-1], [b[2] for b in blocks], int(upos[-1]),
+                             crc=[b[3] for b in blocks])
+    same(_columns_of_stream(bytes(out[:int(upos[-1])])), "inflate_blocks")
