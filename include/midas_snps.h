@@ -637,7 +637,9 @@ int32_t midas_snps_table_copy(const midas_snps_table* table, uint32_t* counts, c
  * Replaces, for every genomic site of a species at once, GenomicSite.__init__/compute_pooled_counts,
  * call_alleles, compute_per_sample_mafs, compute_prevalence and flag
  * (midas/merge/snps.py:13-114, driven from build_sharded_tables :324-364).  Annotation (:116-174) and the
- * text emission (:176-201) stay on the host.  Inputs are the samples' per-site count tables -- exactly what
+ * info line stay on the host; the rows of snps_freq.txt / snps_depth.txt (:196-201) are formatted on the device
+ * by midas_merge_sites_tables, or on the host from midas_merge_sites' arrays (midas_merge_write_matrix).
+ * Inputs are the samples' per-site count tables -- exactly what
  * the pileup stage emits -- and each sample's mean_coverage (midas/merge/merge.py:18-21).          */
 typedef struct midas_merge_params {
   double allele_freq;   /* args['allele_freq']: freq >= allele_freq counts an allele as present (0.01)   */
@@ -665,6 +667,30 @@ int32_t midas_merge_sites(midas_snps_ctx* ctx, const midas_merge_params* params,
 int32_t midas_merge_write_matrix(const char* path, const char* header_line, int64_t n_keep, const int64_t* keep,
                                  int32_t n_samples, int64_t n_sites, const uint32_t* depth,
                                  const uint32_t* minor_count, int32_t threads, int64_t site_id_base, char* err256);
+
+/* midas_merge_write_matrix with the rows formatted on the device: the host arrays go up, the text comes down through the
+ * context's pinned ring and is written by one writer thread beside the formatting of the next batch.  Same arguments (no threads: there is no pool), the same
+ * bytes in the file.  Written under a temporary name and renamed on success: an error leaves nothing at `path`.  Stricter
+ * than the host writer where the device needs it: every keep[r] must lie in [0, n_sites), site_id_base >= 0, a minor count
+ * above its (non-zero) depth is MIDAS_SNPS_ERR_INVALID_ARG, and kept rows out of ascending order are taken only while the
+ * arrays fit one upload (MIDAS_SNPS_ERR_UNSUPPORTED otherwise).  The text is formatted in batches below a cap
+ * (MIDAS_SNPS_MERGE_TEXT_MB, default 256; fractions allowed).  out_format_ms (nullable): device time of the formatter.   */
+int32_t midas_merge_write_matrix_device(midas_snps_ctx* ctx, const char* path, const char* header_line, int64_t n_keep,
+                                        const int64_t* keep, int32_t n_samples, int64_t n_sites, const uint32_t* depth,
+                                        const uint32_t* minor_count, int64_t site_id_base, float* out_format_ms);
+
+/* midas_merge_sites and both matrices in one call: depth and minor_count never come down -- per chunk of sites the kept
+ * ones (flag == 0) are compacted on the device and the rows of snps_freq.txt (freq_path) and snps_depth.txt (depth_path)
+ * formatted from the resident arrays; the text travels through the pinned ring while the next batch is formatted.  Both
+ * files: header_line, then the rows, site_id = site_id_base + site + 1; written under temporary names and renamed on
+ * success -- on any error neither exists.  out_calls / out_count_samples / out_pooled as midas_merge_sites;
+ * *out_n_keep = rows written to each table; out_kernel_ms: the merge kernel alone; out_format_ms: compaction + formatter
+ * (both nullable).  MIDAS_MERGE_ERR_ZERO_MEAN_DEPTH is reported as by midas_merge_sites.                                */
+int32_t midas_merge_sites_tables(midas_snps_ctx* ctx, const midas_merge_params* params, int32_t n_samples, int64_t n_sites,
+                                 const uint32_t* const* sample_counts, const double* mean_depth, const char* freq_path,
+                                 const char* depth_path, const char* header_line, int64_t site_id_base, uint8_t* out_calls,
+                                 uint32_t* out_count_samples, uint64_t* out_pooled, int64_t* out_n_keep, float* out_kernel_ms,
+                                 float* out_format_ms);
 
 /* snps_info.txt of merge_midas.py snps: GenomicSite.annotate + fetch_ref_codon + the info line of GenomicSite.write
  * (midas/merge/snps.py:116-195) with utility.translate / index_replace (midas/utility.py:306-332) for the kept sites.

@@ -305,6 +305,9 @@ def load_library(build_if_missing: bool = True):
         'midas_snps_write_rows': (i32, [C.c_char_p, i32, C.c_char_p, i64, vp, vp, i32, i32, C.c_char_p]),
         'midas_merge_write_info': (i32, [C.c_char_p, C.c_char_p, i64, vp, vp, vp, vp, vp, vp, vp, i32, i64, C.c_char_p]),
         'midas_merge_write_matrix': (i32, [C.c_char_p, C.c_char_p, i64, vp, i32, i64, vp, vp, i32, i64, C.c_char_p]),
+        'midas_merge_write_matrix_device': (i32, [vp, C.c_char_p, C.c_char_p, i64, vp, i32, i64, vp, vp, i64, C.POINTER(C.c_float)]),
+        'midas_merge_sites_tables': (i32, [vp, C.POINTER(MergeParams), i32, i64, C.POINTER(vp), vp, C.c_char_p, C.c_char_p, C.c_char_p, i64,
+                                           vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         'midas_snps_table_open_range': (i32, [C.c_char_p, i64, i64, i32, C.POINTER(vp), C.c_char_p]),
         'midas_snps_table_count_rows': (i32, [C.c_char_p, C.POINTER(i64), C.c_char_p]),
         'midas_snps_write_table': (i32, [C.c_char_p, i32, vp, vp, vp, vp, i32, i32, C.c_char_p]),
@@ -415,7 +418,7 @@ EXPORTED_SYMBOLS = [
     'midas_snps_table_open', 'midas_snps_table_open_range', 'midas_snps_table_count_rows', 'midas_snps_table_close', 'midas_snps_table_rows', 'midas_snps_table_key_bytes',
     'midas_snps_table_copy', 'midas_merge_sites', 'midas_genes_count', 'midas_genes_terms', 'midas_genes_sum', 'midas_merge_write_info',
     'midas_genes_count_device', 'midas_genes_count_timing',
-    'midas_merge_write_matrix',
+    'midas_merge_write_matrix', 'midas_merge_write_matrix_device', 'midas_merge_sites_tables',
     'midas_bam_open_share',
     'midas_comm_device_key', 'midas_comm_probe', 'midas_comm_unique_id', 'midas_comm_create', 'midas_comm_destroy', 'midas_comm_all_gather', 'midas_comm_all_to_all_v',
     'midas_genes_merge_map_open', 'midas_genes_merge_map_n_clusters', 'midas_genes_merge_map_n_genes', 'midas_genes_merge_map_columns',
@@ -604,6 +607,28 @@ def write_merge_matrix(path: str, header_line: str, keep: np.ndarray, depth: np.
                                       mc.ctypes.data_as(C.c_void_p) if mc is not None else None, int(threads), int(site_id_base), err)
     if st != 0:
         raise MidasSnpsError(st, err.value.decode())
+
+
+def write_merge_matrix_device(ctx, path: str, header_line: str, keep: np.ndarray, depth: np.ndarray, minor_count=None,
+                              site_id_base: int = 0) -> float:
+    """write_merge_matrix with the rows formatted on ctx's device (midas_merge_write_matrix_device): the same file, byte for
+    byte.  Stricter than the host writer where the device needs it (MidasSnpsError): every keep[r] in [0, n_sites),
+    site_id_base >= 0, no minor count above its non-zero depth, kept rows ascending unless the arrays fit one upload chunk
+    (none of which merge_sites' outputs can violate).  -> device time of the formatter, ms."""
+    keep = np.ascontiguousarray(keep, dtype=np.int64)
+    depth = np.ascontiguousarray(depth, dtype=np.uint32)
+    S, n = depth.shape
+    mc = None
+    if minor_count is not None:
+        mc = np.ascontiguousarray(minor_count, dtype=np.uint32)
+        assert mc.shape == depth.shape
+    ms = C.c_float(0)
+    st = ctx._lib.midas_merge_write_matrix_device(ctx._h, path.encode(), header_line.encode(), keep.shape[0],
+                                                  keep.ctypes.data_as(C.c_void_p), S, n, depth.ctypes.data_as(C.c_void_p),
+                                                  mc.ctypes.data_as(C.c_void_p) if mc is not None else None, int(site_id_base),
+                                                  C.byref(ms))
+    ctx._check(st)
+    return float(ms.value)
 
 
 def count_snps_rows(path: str) -> int:
@@ -1566,6 +1591,29 @@ class Context:
                                          p(out['depth']), p(out['minor_count']), C.byref(ms))
         self._check(st)
         out['kernel_ms'] = float(ms.value)
+        return out
+
+    def merge_sites_tables(self, prm: "MergeParams", sample_counts, mean_depth, freq_path: str, depth_path: str, header_line: str,
+                           site_id_base: int = 0):
+        """midas_merge_sites_tables(): merge_sites with snps_freq.txt / snps_depth.txt written from the device -- depth and
+        minor_count stay there.  -> dict(major, minor, snp_type, flag, count_samples, pooled[n,4] u64, n_keep, kernel_ms,
+        format_ms)"""
+        S = len(sample_counts)
+        arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in sample_counts]
+        n = arrs[0].shape[0]
+        assert all(a.shape == (n, 4) for a in arrs)
+        ptrs = (C.c_void_p * S)(*[a.ctypes.data for a in arrs])
+        md = np.ascontiguousarray(mean_depth, dtype=np.float64)
+        calls = np.empty((n, 4), np.uint8)
+        out = dict(major=calls[:, 0], minor=calls[:, 1], snp_type=calls[:, 2], flag=calls[:, 3],
+                   count_samples=np.empty(n, np.uint32), pooled=np.empty((n, 4), np.uint64))
+        ms, fms, kept = C.c_float(0), C.c_float(0), C.c_int64(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        st = self._lib.midas_merge_sites_tables(self._h, C.byref(prm), S, n, ptrs, p(md), freq_path.encode(), depth_path.encode(),
+                                                header_line.encode(), int(site_id_base), p(calls), p(out['count_samples']),
+                                                p(out['pooled']), C.byref(kept), C.byref(ms), C.byref(fms))
+        self._check(st)
+        out['n_keep'], out['kernel_ms'], out['format_ms'] = int(kept.value), float(ms.value), float(fms.value)
         return out
 
     def genes_merge(self, cluster, copy, depth, reads, n_clusters: int, min_copy: float, group_samples: int = 0):

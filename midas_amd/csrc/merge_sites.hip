@@ -2,15 +2,20 @@
 // (/root/reference/midas/merge/snps.py:13-114): pooled counts, major/minor allele call, snp_type,
 // per-sample depth / minor-allele count, prevalence and the site flag.  One thread per site, streaming over the
 // samples' count tables ([sample][site][A,C,G,T] u32, i.e. exactly what the pileup stage emits): HBM-bound,
-// 16 B read + 8 B written per (site, sample), 40 B of per-site results.  Annotation and text emission stay on the host.
+// 16 B read + 8 B written per (site, sample), 40 B of per-site results.  midas_merge_sites_tables formats the two matrices'
+// rows from those results where they lie (merge_rows.hip); annotation and snps_info.txt stay on the host.
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdio>
+#include <cstdlib>
+#include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/midas_snps.h"
 #include "ctx_internal.h"
+#include "merge_rows.h"
 
 namespace {
 
@@ -349,6 +354,32 @@ SampleLimit sample_limits(double mean_depth, double site_ratio, int site_depth) 
   return l;
 }
 
+// the kernel form for n_samples (see above) on the context's stream
+void launch_merge_kernel(midas_snps_ctx* ctx, const MergeKParams& k, long long m, int n_samples, bool shallow) {
+  const int grid = (int)((m + 255) / 256 < 4096 ? (m + 255) / 256 : 4096);
+  const dim3 g(grid > 0 ? grid : 1), b(256);
+#ifndef MIDAS_MERGE_TWO_PASS
+  if (n_samples <= kRegsUpTo) {     // rows in registers: every count row is read once
+    hipLaunchKernelGGL(regs_kernel_for(n_samples, std::make_integer_sequence<int, kRegsUpTo>{}), g, b, 0, ctx->stream, k);
+  } else if (n_samples <= 128 && kRegsUpTo >= 64 && shallow) {   // the same with a byte per count
+    hipLaunchKernelGGL(bytes_kernel_for(n_samples, std::make_integer_sequence<int, 8>{}), g, b, 0, ctx->stream, k);
+  } else {
+#endif
+  if (n_samples >= kSplitFrom) {
+    // waves per site group: enough that the rows resident between the passes stay below ~100 MB
+    const long long n_tiles = (m + 63) / 64;
+    const dim3 tg((unsigned)(n_tiles < 16384 ? (n_tiles > 0 ? n_tiles : 1) : 16384));
+    if (n_samples < 2 * kSplitFrom) hipLaunchKernelGGL(merge_sites_split_kernel<4>, tg, dim3(256), 0, ctx->stream, k);
+    else if (n_samples < 4 * kSplitFrom) hipLaunchKernelGGL(merge_sites_split_kernel<8>, tg, dim3(512), 0, ctx->stream, k);
+    else hipLaunchKernelGGL(merge_sites_split_kernel<16>, tg, dim3(1024), 0, ctx->stream, k);
+  } else {
+    hipLaunchKernelGGL(merge_sites_kernel, g, b, 0, ctx->stream, k);
+  }
+#ifndef MIDAS_MERGE_TWO_PASS   // (developer variants: the round-1 kernels, for A/B runs)
+  }
+#endif
+}
+
 int32_t mfail(midas_snps_ctx* ctx, int32_t st, const char* what, hipError_t e) {
   char buf[384];
   snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
@@ -419,29 +450,8 @@ extern "C" int32_t midas_merge_sites(midas_snps_ctx* ctx, const midas_merge_para
     k.count_samples = d_cs; k.pooled = d_pool; k.depth = d_depth; k.minor_count = d_mc; k.err = d_err;
     k.n_sites = (uint32_t)m; k.n_samples = n_samples; k.snp_types = prm->snp_types;
     k.allele_freq = prm->allele_freq; k.site_prev = prm->site_prev;
-    const int grid = (int)((m + 255) / 256 < 4096 ? (m + 255) / 256 : 4096);
     M_TRY(hipEventRecord(e0, ctx->stream));
-    const dim3 g(grid > 0 ? grid : 1), b(256);
-#ifndef MIDAS_MERGE_TWO_PASS
-    if (n_samples <= kRegsUpTo) {     // rows in registers: every count row is read once
-      hipLaunchKernelGGL(regs_kernel_for(n_samples, std::make_integer_sequence<int, kRegsUpTo>{}), g, b, 0, ctx->stream, k);
-    } else if (n_samples <= 128 && kRegsUpTo >= 64 && shallow) {   // the same with a byte per count
-      hipLaunchKernelGGL(bytes_kernel_for(n_samples, std::make_integer_sequence<int, 8>{}), g, b, 0, ctx->stream, k);
-    } else {
-#endif
-    if (n_samples >= kSplitFrom) {
-      // waves per site group: enough that the rows resident between the passes stay below ~100 MB
-      const long long n_tiles = (m + 63) / 64;
-      const dim3 tg((unsigned)(n_tiles < 16384 ? (n_tiles > 0 ? n_tiles : 1) : 16384));
-      if (n_samples < 2 * kSplitFrom) hipLaunchKernelGGL(merge_sites_split_kernel<4>, tg, dim3(256), 0, ctx->stream, k);
-      else if (n_samples < 4 * kSplitFrom) hipLaunchKernelGGL(merge_sites_split_kernel<8>, tg, dim3(512), 0, ctx->stream, k);
-      else hipLaunchKernelGGL(merge_sites_split_kernel<16>, tg, dim3(1024), 0, ctx->stream, k);
-    } else {
-      hipLaunchKernelGGL(merge_sites_kernel, g, b, 0, ctx->stream, k);
-    }
-#ifndef MIDAS_MERGE_TWO_PASS   // (developer variants: the round-1 kernels, for A/B runs)
-    }
-#endif
+    launch_merge_kernel(ctx, k, m, n_samples, shallow);
     M_TRY(hipGetLastError());
     M_TRY(hipEventRecord(e1, ctx->stream));
     M_TRY(hipMemcpyAsync(out_calls + lo * 4, d_b, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -473,4 +483,137 @@ extern "C" int32_t midas_merge_sites(midas_snps_ctx* ctx, const midas_merge_para
   for (void* q : dev) (void)hipFree(q);
   if (out_kernel_ms) *out_kernel_ms = total_ms;
   return status;
+}
+
+// midas_merge_sites with the two matrices written from the device: per chunk the same uploads and the same kernel, then the
+// chunk's kept sites compacted and both tables' rows formatted from the resident depth / minor_count arrays (merge_rows.hip)
+// -- those never come down; their text does, through the pinned ring, a file-writing thread behind it.
+extern "C" int32_t midas_merge_sites_tables(midas_snps_ctx* ctx, const midas_merge_params* prm, int32_t n_samples, int64_t n_sites,
+                                            const uint32_t* const* sample_counts, const double* mean_depth, const char* freq_path,
+                                            const char* depth_path, const char* header_line, int64_t site_id_base,
+                                            uint8_t* out_calls, uint32_t* out_count_samples, uint64_t* out_pooled,
+                                            int64_t* out_n_keep, float* out_kernel_ms, float* out_format_ms) {
+  if (!ctx || !prm || n_samples <= 0 || n_sites < 0 || !sample_counts || !mean_depth || !freq_path || !depth_path || !header_line ||
+      site_id_base < 0 || !out_calls || !out_count_samples || !out_pooled || !out_n_keep)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  ctx->clear_error();
+  ctx->err_read = -1;
+  *out_n_keep = 0;
+  if (out_kernel_ms) *out_kernel_ms = 0.f;
+  if (out_format_ms) *out_format_ms = 0.f;
+  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  std::lock_guard<std::mutex> ring(ctx->copy_mutex);      // the text's way down owns the pinned ring for the whole call
+  std::vector<void*> dev;
+  M_TRY(hipSetDevice(ctx->device));
+  long long chunk = (long long)((4ull << 30) / (16ull * (unsigned long long)n_samples));
+  if (chunk < 1024) chunk = 1024;
+  if (chunk > kMaxChunkSites) chunk = kMaxChunkSites;
+  if (const char* e = getenv("MIDAS_SNPS_MERGE_CHUNK_SITES")) {      // developer knob: chunk borders with small inputs
+    const long long v = atoll(e);
+    if (v > 0 && v < chunk) chunk = v;
+  }
+  if (chunk > n_sites) chunk = n_sites > 0 ? n_sites : 1;
+  bool shallow = true;
+  for (int s = 0; s < n_samples; ++s) shallow = shallow && mean_depth[s] <= 64.0;
+  std::vector<SampleLimit> limits((size_t)n_samples);
+  for (int s = 0; s < n_samples; ++s) limits[(size_t)s] = sample_limits(mean_depth[s], prm->site_ratio, prm->site_depth);
+  midas::MergeTextFile freq_file, depth_file;
+  if (!freq_file.open(freq_path, header_line)) { ctx->set_error(std::string("cannot open ") + freq_path + " for writing"); return MIDAS_SNPS_ERR_INVALID_ARG; }
+  if (!depth_file.open(depth_path, header_line)) { ctx->set_error(std::string("cannot open ") + depth_path + " for writing"); return MIDAS_SNPS_ERR_INVALID_ARG; }
+  midas::MergeTextSink sink(ctx);
+  midas::MergeRowFormatter fmt(ctx, n_samples);
+  int32_t status = sink.start();
+  if (status != MIDAS_SNPS_OK) return status;
+  if ((status = fmt.prepare(chunk, true)) != MIDAS_SNPS_OK) return status;
+  uint32_t* d_counts = nullptr; SampleLimit* d_md = nullptr; uint32_t* d_b = nullptr; uint32_t* d_cs = nullptr;
+  unsigned long long* d_pool = nullptr; uint32_t* d_depth = nullptr; uint32_t* d_mc = nullptr; unsigned long long* d_err = nullptr;
+  M_TRY(hipMalloc(&d_counts, (size_t)chunk * n_samples * 16)); dev.push_back(d_counts);
+  M_TRY(hipMalloc(&d_md, (size_t)n_samples * sizeof(SampleLimit))); dev.push_back(d_md);
+  M_TRY(hipMalloc(&d_b, (size_t)chunk * 4)); dev.push_back(d_b);
+  M_TRY(hipMalloc(&d_cs, (size_t)chunk * 4)); dev.push_back(d_cs);
+  M_TRY(hipMalloc(&d_pool, (size_t)chunk * 32)); dev.push_back(d_pool);
+  M_TRY(hipMalloc(&d_depth, (size_t)chunk * n_samples * 4)); dev.push_back(d_depth);
+  M_TRY(hipMalloc(&d_mc, (size_t)chunk * n_samples * 4)); dev.push_back(d_mc);
+  M_TRY(hipMalloc(&d_err, 8)); dev.push_back(d_err);
+  M_TRY(hipMemcpy(d_md, limits.data(), (size_t)n_samples * sizeof(SampleLimit), hipMemcpyHostToDevice));
+  struct Events {      // (destroyed on every way out)
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  } ev;
+  M_TRY(hipEventCreate(&ev.a));
+  M_TRY(hipEventCreate(&ev.b));
+  const hipEvent_t e0 = ev.a, e1 = ev.b;
+  float total_ms = 0.f;
+  double upload_s = 0, results_s = 0, rows_s = 0;
+  long long n_keep = 0;
+  for (long long lo = 0; lo < n_sites && status == MIDAS_SNPS_OK; lo += chunk) {
+    const long long m = (n_sites - lo) < chunk ? (n_sites - lo) : chunk;
+    double t0 = now();
+    for (int s = 0; s < n_samples; ++s)
+      M_TRY(hipMemcpyAsync(d_counts + (size_t)s * m * 4, sample_counts[s] + (size_t)lo * 4, (size_t)m * 16,
+                           hipMemcpyHostToDevice, ctx->stream));
+    M_TRY(hipMemsetAsync(d_err, 0xFF, 8, ctx->stream));
+    M_TRY(hipStreamSynchronize(ctx->stream));
+    upload_s += now() - t0;
+    t0 = now();
+    MergeKParams k;
+    k.counts = d_counts; k.limit = d_md;
+    k.calls = d_b;
+    k.count_samples = d_cs; k.pooled = d_pool; k.depth = d_depth; k.minor_count = d_mc; k.err = d_err;
+    k.n_sites = (uint32_t)m; k.n_samples = n_samples; k.snp_types = prm->snp_types;
+    k.allele_freq = prm->allele_freq; k.site_prev = prm->site_prev;
+    M_TRY(hipEventRecord(e0, ctx->stream));
+    launch_merge_kernel(ctx, k, m, n_samples, shallow);
+    M_TRY(hipGetLastError());
+    M_TRY(hipEventRecord(e1, ctx->stream));
+    M_TRY(hipMemcpyAsync(out_calls + lo * 4, d_b, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    M_TRY(hipMemcpyAsync(out_count_samples + lo, d_cs, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    M_TRY(hipMemcpyAsync(out_pooled + lo * 4, d_pool, (size_t)m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned long long err = ~0ull;
+    M_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, ctx->stream));
+    M_TRY(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    M_TRY(hipEventElapsedTime(&ms, e0, e1));
+    total_ms += ms;
+    results_s += now() - t0;
+    if (err != ~0ull) {
+      char buf[200];
+      ctx->err_read = (int64_t)(lo + (long long)err);
+      snprintf(buf, sizeof buf, "site %lld: a sample with mean_coverage 0 reached site_depth/mean_depth "
+               "(reference: ZeroDivisionError in compute_prevalence)", (long long)ctx->err_read + 1);
+      ctx->set_error(buf);
+      status = MIDAS_MERGE_ERR_ZERO_MEAN_DEPTH;
+      break;
+    }
+    t0 = now();
+    const uint32_t* d_keep = nullptr;
+    long long kept = 0;
+    status = fmt.compact(d_b, (uint32_t)m, &d_keep, &kept);
+    if (status == MIDAS_SNPS_OK)
+      status = fmt.emit(d_depth, d_mc, (uint32_t)m, d_keep, kept, (long long)site_id_base + lo, &sink, &freq_file);
+    if (status == MIDAS_SNPS_OK)
+      status = fmt.emit(d_depth, nullptr, (uint32_t)m, d_keep, kept, (long long)site_id_base + lo, &sink, &depth_file);
+    rows_s += now() - t0;
+    n_keep += kept;
+  }
+  double t0 = now();
+  const bool written = sink.finish();
+  const double tail_s = now() - t0;
+  for (void* q : dev) (void)hipFree(q);
+  if (out_kernel_ms) *out_kernel_ms = total_ms;
+  if (out_format_ms) *out_format_ms = fmt.format_ms;
+  if (status != MIDAS_SNPS_OK) return status;       // (the files' destructors remove what was written)
+  bool both = written && freq_file.commit();
+  if (both && !depth_file.commit()) { (void)remove(freq_path); both = false; }      // neither table, not one of the two
+  if (!both) {
+    ctx->set_error(std::string("write failed on ") + freq_path + " / " + depth_path);
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  }
+  *out_n_keep = (int64_t)n_keep;
+  if (getenv("MIDAS_SNPS_TRACE"))
+    fprintf(stderr, "[merge tables] upload %.3f s, kernel %.3f ms, per-site results down %.3f s, rows %.3f s (format %.3f ms on the device, "
+            "text down %.3f s, waiting for the file writer in between), file write %.3f s on the writer thread (%.3f s of it after the last batch), "
+            "%lld bytes of text, %lld kept rows\n", upload_s, total_ms, results_s, rows_s, fmt.format_ms, sink.copy_s, sink.write_s, tail_s,
+            sink.bytes, n_keep);
+  return MIDAS_SNPS_OK;
 }

@@ -4,8 +4,9 @@ Mirrors /root/reference/midas/merge/snps.py: same outputs (<outdir>/<species>/sn
 readme.txt), same site numbering and filters.  What changes underneath: the per-site cross-sample arithmetic of
 GenomicSite (pooled counts, allele calls, per-sample depth/MAF, prevalence, flag -- :13-114) runs on the GPU for all
 sites of a species at once (midas_merge_sites in include/midas_snps.h); the temporary acgt_counts matrices and the
-per-thread shard files of the reference are not needed.  Annotation (:116-174) and text emission (:176-201) stay on
-the host and touch only the sites that survive the filters.  No CPU fallback for the arithmetic.
+per-thread shard files of the reference are not needed.  The rows of snps_freq.txt / snps_depth.txt (:196-201) can be formatted
+on the GPU as well (midas_merge_sites_tables, MIDAS_SNPS_MERGE_WRITERS=device); annotation (:116-174) and snps_info.txt stay on the host and touch only
+the sites that survive the filters.  No CPU fallback for the arithmetic.
 """
 
 import os
@@ -76,18 +77,29 @@ def merge_species(species, args, ctx, row_range=None, part=None):
         genes = genes_job.result()
     n = counts[0].shape[0]
     prm = abi.MergeParams.from_args(args)
+    # snps_freq.txt / snps_depth.txt: one number per (kept site, sample).  By default the per-sample arrays come down and host
+    # threads format them.  MIDAS_SNPS_MERGE_WRITERS=device, on a context that offers merge_sites_tables, formats both tables'
+    # rows on the device, from the arrays where the merge kernel leaves them: the same bytes, measured faster, but not by more
+    # than the run-to-run spread (profiles/merge_snps_e2e.txt), so it is not the default.
+    on_device = hasattr(ctx, 'merge_sites_tables') and os.environ.get('MIDAS_SNPS_MERGE_WRITERS', 'host') == 'device'
+    threads = int(args.get('threads', 1) or 1)
+    freq_path, depth_path = outdir + '/snps_freq.txt' + suffix, outdir + '/snps_depth.txt' + suffix
     try:
-        res = ctx.merge_sites(prm, counts, species.sample_depth)
+        if on_device:
+            res = ctx.merge_sites_tables(prm, counts, species.sample_depth, freq_path, depth_path, header, site_id_base=base)
+        else:
+            res = ctx.merge_sites(prm, counts, species.sample_depth)
     except abi.MidasSnpsError as e:
         if e.status == abi.ERR_MERGE_ZERO_MEAN_DEPTH and e.read_index >= 0 and base:
             sys.exit("\nError: %s [row %d of the species' tables]\n" % (e.message, base + e.read_index + 1))
         sys.exit("\nError: %s\n" % e.message)
     keep = np.nonzero(res['flag'] == 0)[0]
-    # snps_freq.txt / snps_depth.txt: one number per (kept site, sample) -- formatted natively
-    threads = int(args.get('threads', 1) or 1)
-    abi.write_merge_matrix(outdir + '/snps_freq.txt' + suffix, header, keep, res['depth'], res['minor_count'], threads=threads,
-                           site_id_base=base)
-    abi.write_merge_matrix(outdir + '/snps_depth.txt' + suffix, header, keep, res['depth'], None, threads=threads, site_id_base=base)
+    if on_device:
+        if res['n_keep'] != len(keep):
+            sys.exit("\nError: %d rows written to snps_freq.txt / snps_depth.txt, %d sites kept\n" % (res['n_keep'], len(keep)))
+    else:
+        abi.write_merge_matrix(freq_path, header, keep, res['depth'], res['minor_count'], threads=threads, site_id_base=base)
+        abi.write_merge_matrix(depth_path, header, keep, res['depth'], None, threads=threads, site_id_base=base)
     # snps_info.txt: annotation of the kept sites (the reference's forward cursor over the sorted genes, codon
     # degeneracy) + the per-site calls, formatted natively
     abi.write_merge_info(outdir + '/snps_info.txt' + suffix, info_header, keep, keys, key_off, res, genes.genes,
