@@ -37,7 +37,7 @@ __device__ __forceinline__ uint32_t rd16(const uint8_t* p) { return *reinterpret
 constexpr unsigned long long kNone = ~0ull;
 constexpr int kChain = 4;
 
-// Could an alignment record start at d + u?  (The host's plausible_bytes, hostio.cpp.)  *bs = its block_size.
+// Could an alignment record start at d + u?  (The host's plausible_bytes, bam_parse.h.)  *bs = its block_size.
 __device__ bool plausible(const BamWalkParams& p, unsigned long long u, unsigned long long total, uint32_t* bs_out) {
   if (u + 36 > total) return false;
   const uint8_t* r = p.d + u;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void bam_offsets_kernel(BamWalkParams p, const 
   }
 }
 
-// NM:i (any integer width) from the aux block, or -1 (hostio.cpp find_nm)
+// NM:i (any integer width) from the aux block, or -1 (bam_host.cpp find_nm)
 __device__ int32_t find_nm(const uint8_t* a, const uint8_t* end) {
   while (a + 3 <= end) {
     const char t0 = (char)a[0], t1 = (char)a[1], ty = (char)a[2];

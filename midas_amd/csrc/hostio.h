@@ -57,7 +57,7 @@ void bam_set_device_payload(midas_bam* b, void* seq4, void* qual, void* cigar, v
 
 // midas_bam_load_device, everything on the device (bam_device.hip): the file's BGZF blocks go up, are inflated and checked
 // there, the records are found, their columns decoded and SEQ / QUAL / CIGAR cut out where the stream lies -- what comes down
-// is the small columns (refID, pos, mapq, flag, NM, l_seq, the three CSR offset arrays).  hostio.cpp reads the file, builds
+// is the small columns (refID, pos, mapq, flag, NM, l_seq, the three CSR offset arrays).  bam_host.cpp reads the file, builds
 // the block table, parses the header (the first blocks, inflated by the host) and hands the device part to `dec`.
 struct HostColumns {
   int32_t *refid, *pos, *nm, *l_seq; uint8_t* mapq; uint16_t* flag; int64_t *seq_off, *qual_off, *cigar_off;

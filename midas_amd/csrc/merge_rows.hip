@@ -1,6 +1,6 @@
 // `merge_midas.py snps` on MI355X: the rows of snps_freq.txt / snps_depth.txt formatted on the device, from the per-sample
 // depth / minor-count arrays where merge_sites.hip leaves them ([sample][site] u32), into the very bytes
-// midas_merge_write_matrix (hostio.cpp) writes: `site_id \t v[0] \t ... \t v[S-1] \n` per kept site, v = str(depth) or
+// midas_merge_write_matrix (tables_host.cpp) writes: `site_id \t v[0] \t ... \t v[S-1] \n` per kept site, v = str(depth) or
 // '{0:.3g}'.format(float(minor) / depth if depth > 0 else 0.0) (merge_fmt.h: integers, no printf).
 //
 //   compact   flag byte of the calls word == 0 -> scan -> the kept sites of the chunk, in order

@@ -1,6 +1,6 @@
 """Hand-assembles tests/golden/spec_fixture.bam byte by byte from the tables of the SAM/BAM specification (SAMv1 sections
 4.1 "The BGZF compression format" and 4.2 "The BAM format") with nothing but struct and zlib -- it imports NOTHING from
-midas_amd, so the decoder under test (midas_amd/csrc/hostio.cpp) and the writer the other tests use (midas_amd/bam.py) cannot
+midas_amd, so the decoder under test (midas_amd/csrc/bam_host.cpp) and the writer the other tests use (midas_amd/bam.py) cannot
 share a misreading of the spec.  The expected columns are written next to it (spec_fixture.json) from the same literals.
 
 What the file exercises: records that straddle BGZF block borders (blocks are cut every 97 bytes of the stream), a

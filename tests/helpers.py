@@ -340,3 +340,19 @@ def border_conditions(reads, lane_bases, max_len, oracle_counts, oracle_stats):
     assert int(oracle_counts.sum()) > 0
     aligned, mapped = int(oracle_stats[:, 0].sum()), int(oracle_stats[:, 1].sum())
     assert aligned == len(reads) and 10 * mapped >= 9 * aligned, (aligned, mapped)
+
+
+LONG_HEADER_BYTES = 276265
+
+
+def long_header_bam(path):
+    """A BAM whose header is longer than one BGZF block: 4 contigs with 4 000 reads, and 4 000 read-less references behind them --
+    276 265 bytes of header, five blocks, so that a reader that takes twice as many blocks every round goes round four times.
+    -> (names, lengths) as written."""
+    from midas_amd import synth
+    contigs, reads = synth.make_dataset(n_species=1, contigs_per_species=4, n_reads=4000, seed=11)
+    refid = np.repeat(np.arange(4, dtype=np.int32), np.diff(contigs.read_begin))
+    names = list(contigs.ids) + ["empty_reference_%05d" % k for k in range(4000)]
+    lens = [int(x) for x in contigs.length] + [99996 + k for k in range(4000)]
+    abi.write_bam(path, names, lens, refid, reads)
+    return names, lens

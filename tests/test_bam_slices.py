@@ -137,3 +137,46 @@ def test_local_block_tables_of_the_ranks_chain_and_find_the_shares_of_the_full_w
             assert ei.value.status == abi.ERR_INVALID_ARG
         for s in local + full:
             s.close()
+
+
+def test_a_header_longer_than_one_block_through_every_opener(tmp_path):
+    """The header's reader takes the file's first blocks, twice as many every round; here the header is five blocks long.  The whole-file
+    decode, the slices, the shares over the whole block table and the shares over local tables must read the same references and
+    the same first record offset from it; the slices chain, and every share begins where some reference's records begin."""
+    from tests import helpers as H
+    path = str(tmp_path / "long_header.bam")
+    names, lens = H.long_header_bam(path)
+    got_names, got_lens, rid, full = abi.read_bam(path)
+    assert got_names == names and got_lens == lens and len(names) == 4004
+    assert full.n_reads == 4000 and np.array_equal(np.unique(rid), np.arange(4))
+    size = os.path.getsize(path)
+    for n in (1, 3):
+        sl = [abi.BamSlice(path, k, n) for k in range(n)]
+        shares = [abi.BamShare(path, k, n) for k in range(n)]
+        local = [abi.BamShare.open_local(path, k, n) for k in range(n)]
+        walks = np.array([s.walk for s in local])
+        assert walks[0, 0] == 0 and (walks[:-1, 1] == walks[1:, 0]).all() and walks[-1, 1] == size
+        for k in range(n):
+            local[k].locate(int(walks[:k, 2].sum()), int(walks[:, 2].sum()))
+        for s in sl + shares + local:
+            assert s.ref_names == names and s.ref_lens == lens
+            assert s.rec_begin == H.LONG_HEADER_BYTES
+        assert sl[0].first == H.LONG_HEADER_BYTES and sl[-1].end == sl[-1].total
+        for k in range(n - 1):
+            assert sl[k].end == sl[k + 1].first
+        assert np.array_equal(sum(s.ref_reads for s in sl), np.bincount(rid, minlength=len(names)))
+        # where every reference's records begin, as the whole-file decode sees them: its records are back to back behind the header
+        first = _global_first(sl, len(names))
+        rec_bytes = 4 + 32 + np.array([len("r%d" % i) + 1 for i in range(full.n_reads)]) + 4 * np.diff(full.cigar_off) + np.diff(full.seq_off) + \
+            np.diff(full.qual_off) + np.where(full.nm < 0, 0, np.where(full.nm < 256, 4, 7)) + 6
+        starts = H.LONG_HEADER_BYTES + np.concatenate([[0], np.cumsum(rec_bytes)])
+        assert starts[-1] == sl[0].total
+        ref_first = starts[np.searchsorted(rid, np.arange(4))]
+        assert np.array_equal(first[:4], ref_first) and (first[4:] == -1).all()
+        borders = set(int(x) for x in ref_first) | {int(sl[0].total)}
+        for a, b in zip(shares, local):
+            assert (a.first, a.total, a.rec_begin) == (b.first, b.total, b.rec_begin)
+            assert a.first in borders and a.total == sl[0].total
+        assert shares[0].first == H.LONG_HEADER_BYTES
+        for s in sl + shares + local:
+            s.close()

@@ -1,4 +1,4 @@
-"""The library's FASTA reader (midas_fasta_load, hostio.cpp) against midas_amd/fasta.py -- the restatement of
+"""The library's FASTA reader (midas_fasta_load, fasta_host.cpp) against midas_amd/fasta.py -- the restatement of
 `Bio.SeqIO.parse(infile, 'fasta')` + `str(rec.seq).upper()` at midas/run/snps.py:59-62 that the host used to read the genomes
 with: the same records (ids, sequences, order) for every oddity a FASTA file can hold, plain and gzip, many files at once."""
 import gzip

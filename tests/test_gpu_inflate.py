@@ -256,9 +256,56 @@ def _same_decode(ctx, path):
     return host
 
 
+def test_a_header_longer_than_one_block_on_the_device_paths(ctx, tmp_path):
+    """The five-block header of tests/helpers.py long_header_bam through every opener that hands work to the device: the whole file
+    with the payload on the device and resident, the slices walked there, and a rank's ranges decoded there, resident too.  Columns
+    and facts must be the host decode's."""
+    from tests import helpers as H
+    path = str(tmp_path / "long_header.bam")
+    names, lens = H.long_header_bam(path)
+    host = _same_decode(ctx, path)
+    names_h, lens_h, refid_h, _ = abi.read_bam(path)
+    assert names_h == names and lens_h == lens
+    names_r, lens_r, refid_r, res = abi.read_bam(path, ctx, resident=True)
+    assert names_r == names and lens_r == lens and res.n_reads == host.n_reads == 4000
+    np.testing.assert_array_equal(refid_h, refid_r)
+    down = ctx.fetch_payload(res)
+    for k in abi._SOA_DTYPES:
+        np.testing.assert_array_equal(getattr(host, k), getattr(down, k), err_msg="resident " + k)
+    for n in (1, 3):
+        on_host = [abi.BamSlice(path, k, n) for k in range(n)]
+        on_dev = [abi.BamSlice(path, k, n, ctx=ctx) for k in range(n)]
+        for a, b in zip(on_host, on_dev):
+            assert b.ref_names == names and b.ref_lens == lens and b.rec_begin == H.LONG_HEADER_BYTES
+            assert (a.first, a.end, a.sorted, a.first_ref, a.last_ref, a.rec_begin, a.total) == (b.first, b.end, b.sorted, b.first_ref, b.last_ref, b.rec_begin, b.total)
+            for f in ("ref_reads", "ref_bases", "ref_first"):
+                np.testing.assert_array_equal(getattr(a, f), getattr(b, f), err_msg=f)
+            ma, mb = a.marks(), b.marks()
+            assert ma[:3] == mb[:3]
+            np.testing.assert_array_equal(ma[3], mb[3])
+            np.testing.assert_array_equal(ma[4], mb[4])
+        # references 1 and 2 as one range, reference 3 to the file's end
+        first = on_host[0].ref_first.copy()
+        for s in on_host[1:]:
+            m = (s.ref_first >= 0) & ((first < 0) | (s.ref_first < first))
+            first[m] = s.ref_first[m]
+        ranges = [(int(first[1]), int(first[3])), (int(first[3]), on_host[0].total)]
+        sel = refid_h >= 1
+        want_refid, want = abi.BamSlice(path, 0, 1).load_ranges(ranges)
+        np.testing.assert_array_equal(want_refid, refid_h[sel])
+        for resident in (False, True):
+            got_refid, got = abi.BamSlice(path, n // 2, n, ctx=ctx).load_ranges(ranges, ctx=ctx, resident=resident)
+            np.testing.assert_array_equal(np.array(got_refid), refid_h[sel])
+            cols = ctx.fetch_payload(got)
+            for k in abi._SOA_DTYPES:
+                np.testing.assert_array_equal(getattr(want, k), getattr(cols, k), err_msg="ranges %s resident=%s" % (k, resident))
+        for s in on_host + on_dev:
+            s.close()
+
+
 def test_the_device_record_walk_is_the_hosts(ctx, tmp_path):
     """midas_bam_load_device finds the records, decodes their columns and NM and cuts SEQ / QUAL / CIGAR on the device
-    (bam_walk.hip); the host's walk (hostio.cpp) is the yardstick.  The spec-assembled fixture; records that span several BGZF
+    (bam_walk.hip); the host's walk (bam_host.cpp) is the yardstick.  The spec-assembled fixture; records that span several BGZF
     blocks and several walk chunks (1 000 bp reads behind 150 bp ones); records without NM, without SEQ, with NM of every
     integer width; unmapped records (refID -1) between mapped ones; and QUAL bytes that spell well-formed records exactly where
     the walk's chunks begin, so that guesses are wrong and the stitching has to walk those chunks again."""

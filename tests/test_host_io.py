@@ -45,7 +45,7 @@ def _rewrite_bgzf(src, dst, edit):
 
 def test_large_bam_goes_through_the_parallel_record_walk(tmp_path):
     """Above a few MB of inflated records the decoder finds record boundaries inside the stream and walks the pieces on
-    all cores, stitched in order (hostio.cpp walk_records): the result must be the serial walk's, i.e. what was written --
+    all cores, stitched in order (bam_host.cpp walk_records): the result must be the serial walk's, i.e. what was written --
     also when bytes that look like a run of records sit inside a read's qualities, and when the stream is cut short."""
     contigs, reads = synth.make_dataset(n_species=2, contigs_per_species=3, contig_len=40000, n_reads=50000, seed=21, var_len=True)
     refid = np.repeat(np.arange(contigs.n_contigs, dtype=np.int32), np.diff(contigs.read_begin))
@@ -65,7 +65,7 @@ def test_large_bam_goes_through_the_parallel_record_walk(tmp_path):
 
 
 def test_block_table_walked_in_pieces_is_the_serial_walk(tmp_path, monkeypatch):
-    """A large BAM's BGZF block table is walked by several threads, each from a GUESSED block start (hostio.cpp bgzf_walk_file):
+    """A large BAM's BGZF block table is walked by several threads, each from a GUESSED block start (bgzf_host.cpp bgzf_walk_file):
     believed only if every piece's walk ends on the next piece's guess.  Forced on for a small file here: the decode must be
     what was written -- also when the guess lands in a block whose payload holds bytes that look like a block header (a stored
     block carrying a copy of a real header: the guess starts a chain there that does not hit the next piece's start, and one
@@ -162,7 +162,7 @@ def test_record_walk_is_not_fooled_by_bytes_that_look_like_records(tmp_path):
         p += 4 + int(np.frombuffer(raw, '<i4', 1, p)[0])
     starts = np.array(starts)
     from midas_amd import utility
-    nt = min(utility.cpu_budget(), 128)            # the library's own thread budget (hostio.cpp hw_threads)
+    nt = min(utility.cpu_budget(), 128)            # the library's own thread budget (hostio_internal.h hw_threads)
     span = total - rec_begin
     n_pieces = min(nt * 4, span >> 20)
     assert n_pieces >= 8
