@@ -743,6 +743,35 @@ int32_t midas_genes_count_device(midas_snps_ctx* ctx, const midas_snps_threshold
                                  int64_t* out_mapped, double* out_depth, float* out_kernel_ms);
 int32_t midas_genes_count_timing(const midas_snps_ctx* ctx, float* out_ms2);
 
+/* midas_genes_count over genes/temp/pangenomes.bam itself, in ONE pass on the context's device: what midas_bam_load_resident is to
+ * the snps path.  `bam`: an open handle on which nothing has been loaded (midas_bam_open_device, midas_bam_open, or -- cheapest, it
+ * inflates the header's blocks only and keeps the file mapped with its block table -- midas_bam_open_share(path, 0, 1, 0, ...)); its
+ * header is read, so the caller asks midas_bam_n_refs / midas_bam_ref first and hands gene_length[i] for reference i of the header.
+ * n_genes must equal midas_bam_n_refs(bam) (else MIDAS_SNPS_ERR_INVALID_ARG).  The call leaves the handle as it was.
+ * The steps are the device decode's own, in one arena: the file's BGZF blocks go up, are inflated and held to their CRC-32
+ * (bgzf_inflate.hip), the records are walked in chunks and the chunks stitched (bam_walk.hip), every kept record's offset is
+ * written -- and then, instead of columns, scans and a payload cut, bam_genes_facts_kernel (genes_count.hip) makes every read's
+ * 8-byte fact from its record where it lies in the inflated stream: sixteen lanes a read sum its QUAL run, lane 0 walks the CIGAR
+ * ends and finds NM in the aux block.  Filter, stable sort by gene, bounds and ordered fp64 sums are the tail midas_genes_count and
+ * midas_genes_count_device run.  Nothing per read comes down: the three per-gene arrays do.
+ *   midas_genes_count_bam(file) == midas_genes_count(midas_bam_open + midas_bam_load of the same file)
+ * in every count, every depth bit for bit, and in the status; midas_snps_last_error_read agrees too -- it is the index among the
+ * KEPT records (refID >= 0), as the host decode counts them (tests/test_gpu_genes_bam.py).
+ * Statuses: the per-read ones of midas_genes_count; MIDAS_SNPS_ERR_BAD_LAYOUT for a corrupt BGZF block (err256 names its file
+ * offset, as the other decoders do), a block_size that leaves the stream, a record whose variable parts overrun its block_size or
+ * whose refID names no reference; MIDAS_SNPS_ERR_UNSUPPORTED for l_seq > 1024 or NM > 65534 (as midas_genes_count) and for
+ * record boundaries the walk cannot settle; MIDAS_SNPS_ERR_OUT_OF_MEMORY for a file whose decode does not fit one arena (about
+ * 2.3 x its inflated bytes; there is no streamed form); MIDAS_SNPS_ERR_HIP for a device failure -- a status, never a silent
+ * fall-back (run_midas.py genes --device_inflate auto answers the last two with the host route).  err256 (nullable, 256 bytes)
+ * and midas_snps_last_error hold the message.
+ *   out_stats8 (nullable): records kept, records dropped for refID < 0, BGZF blocks, inflated bytes, chunks walked, chunks walked
+ *                          again, 0, 0
+ *   out_ms8 (nullable):    upload (host clock around a synchronise), then device events: inflate + CRC, walk + stitch + offsets,
+ *                          facts kernel, filter + sort + sums, download, 0, 0 (measurement aid; no reference counterpart).     */
+int32_t midas_genes_count_bam(midas_snps_ctx* ctx, midas_bam* bam, const midas_snps_thresholds* thr, int64_t n_genes,
+                              const int64_t* gene_length, int64_t* out_aligned, int64_t* out_mapped, double* out_depth,
+                              int64_t* out_stats8, float* out_ms8, char* err256);
+
 /* The two halves of midas_genes_count, for N ranks below the species (midas_amd/run/genes.py): a gene's running fp64 sum has
  * to be formed in BAM order on ONE rank, so every rank turns ITS slice of the unsorted BAM into terms, the (gene, term) pairs
  * travel to the gene's owner (one all-to-all; the slices are in file order, so are the pairs a rank receives), and the owner sums.

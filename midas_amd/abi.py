@@ -331,6 +331,7 @@ def load_library(build_if_missing: bool = True):
         'midas_genes_terms': (i32, [vp, C.POINTER(Thresholds), C.POINTER(_Reads), vp, i64, vp, vp, C.POINTER(C.c_float)]),
         'midas_genes_count_device': (i32, [vp, C.POINTER(Thresholds), C.POINTER(_Reads), vp, i64, vp, vp, vp, vp, C.POINTER(C.c_float)]),
         'midas_genes_count_timing': (i32, [vp, vp]),
+        'midas_genes_count_bam': (i32, [vp, vp, C.POINTER(Thresholds), i64, vp, vp, vp, vp, vp, vp, C.c_char_p]),
         'midas_genes_sum': (i32, [vp, i64, vp, vp, i64, vp, vp, vp, C.POINTER(C.c_float)]),
         'midas_merge_sites': (i32, [vp, C.POINTER(MergeParams), i32, i64, C.POINTER(vp), vp] + [vp] * 5 + [C.POINTER(C.c_float)]),
         'midas_bam_open_share': (i32, [C.c_char_p, i32, i32, i64, C.POINTER(vp), vp, C.c_char_p]),
@@ -417,7 +418,7 @@ EXPORTED_SYMBOLS = [
     'midas_fasta_load', 'midas_fasta_n_records', 'midas_fasta_columns', 'midas_fasta_close',
     'midas_snps_table_open', 'midas_snps_table_open_range', 'midas_snps_table_count_rows', 'midas_snps_table_close', 'midas_snps_table_rows', 'midas_snps_table_key_bytes',
     'midas_snps_table_copy', 'midas_merge_sites', 'midas_genes_count', 'midas_genes_terms', 'midas_genes_sum', 'midas_merge_write_info',
-    'midas_genes_count_device', 'midas_genes_count_timing',
+    'midas_genes_count_device', 'midas_genes_count_timing', 'midas_genes_count_bam',
     'midas_merge_write_matrix', 'midas_merge_write_matrix_device', 'midas_merge_sites_tables',
     'midas_bam_open_share',
     'midas_comm_device_key', 'midas_comm_probe', 'midas_comm_unique_id', 'midas_comm_create', 'midas_comm_destroy', 'midas_comm_all_gather', 'midas_comm_all_to_all_v',
@@ -489,6 +490,8 @@ def species_assign(indptr, hit_species, hit_aln, reads, aln, py_state=None, np_s
 # the SAM decode (run_midas.py snps --sam, genes --sam): bound above like the rest, listed by themselves
 SAM_SYMBOLS = ['midas_sam_load_device', 'midas_sam_decode_timing', 'midas_sam_load_device_order']
 SAM_ORDERS = {'coordinate': 0, 'file': 1}        # MIDAS_SAM_ORDER_*
+GENES_BAM_PHASES = ('upload', 'inflate + crc', 'walk + stitch + offsets', 'facts kernel', 'filter + sort + sums', 'download')
+GENES_BAM_STATS = ('records', 'dropped', 'blocks', 'inflated_bytes', 'chunks', 'chunks_again')
 SAM_PHASES = ('map + header', 'upload', 'line index', 'pass 1 (fields)', 'scans', 'pass 2 (payload)', 'sort + gather', 'columns down')
 
 
@@ -744,6 +747,36 @@ def read_bam(path: str, ctx=None, payload_on_device: bool = False, resident: boo
         raise MidasSnpsError(st, err.value.decode())
     refid, reads = _bam_columns(lib, h, int(n.value), int(sb.value), int(qb.value), int(nc.value), owner)
     return names, lens, refid, reads
+
+
+class BamDeviceHandle:
+    """An open BAM on which nothing is loaded, for Context.genes_count_bam: `ref_names`, `ref_lengths` (the header's, by index)."""
+
+    def __init__(self, lib, h, path):
+        self._owner = _BamOwner(lib, h)
+        self._h = h
+        self.path = path
+        self.ref_names, self.ref_lengths = _bam_refs(lib, h)
+
+    def close(self):
+        self._owner.__del__()
+        self._h = None
+
+
+def open_bam_device(path: str, ctx) -> BamDeviceHandle:
+    """The handle midas_genes_count_bam takes: the file mapped, its block table walked, its header read -- and no record looked at
+    (midas_bam_open_share(path, 0, 1, 0): midas_bam_open_device would inflate the whole file to show its header).  ctx: the device
+    context the count will run on; without one this raises ERR_INVALID_ARG, there is no host form."""
+    if ctx is None or not getattr(ctx, 'inflates', False):
+        raise MidasSnpsError(ERR_INVALID_ARG, "open_bam_device needs a device context")
+    lib = load_library()
+    h = C.c_void_p()
+    err = C.create_string_buffer(256)
+    out3 = (C.c_int64 * 3)()
+    st = lib.midas_bam_open_share(path.encode(), 0, 1, 0, C.byref(h), out3, err)
+    if st != 0:
+        raise MidasSnpsError(st, err.value.decode())
+    return BamDeviceHandle(lib, h, path)
 
 
 def read_sam(path: str, ctx=None, order: str = 'coordinate'):
@@ -1546,6 +1579,28 @@ class Context:
         ms = (C.c_float * 2)()
         self._check(self._lib.midas_genes_count_timing(self._h, ms))
         return {'facts kernel': float(ms[0]), 'filter + sort + sums': float(ms[1])}
+
+    def genes_count_bam(self, thr: Thresholds, handle: "BamDeviceHandle", gene_length):
+        """midas_genes_count_bam(): genes_count over the BAM behind `handle` (open_bam_device) in one pass on this context's device;
+        gene_length[i]: the length of reference i of the header.  -> (aligned_reads i64, mapped_reads i64, depth f64, ms: the
+        call's device milliseconds from the inflate to the download)."""
+        gl = np.ascontiguousarray(gene_length, dtype=np.int64)
+        n = gl.shape[0]
+        aligned, mapped, depth = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.float64)
+        stats, ms = np.zeros(8, np.int64), np.zeros(8, np.float32)
+        err = C.create_string_buffer(256)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        st = self._lib.midas_genes_count_bam(self._h, handle._h, C.byref(thr), n, p(gl), p(aligned), p(mapped), p(depth), p(stats), p(ms), err)
+        self._genes_bam = (dict(zip(GENES_BAM_PHASES, (float(x) for x in ms))), dict(zip(GENES_BAM_STATS, (int(x) for x in stats))))
+        self._check(st)
+        return aligned, mapped, depth, float(ms[1:6].sum())
+
+    def genes_count_bam_timing(self):
+        """(laps, stats) of the last genes_count_bam on this context: milliseconds by phase (GENES_BAM_PHASES: the upload by the host's
+        clock, the others device events) and the decode's counts (GENES_BAM_STATS)."""
+        if getattr(self, '_genes_bam', None) is None:
+            raise MidasSnpsError(ERR_INVALID_ARG, "genes_count_bam_timing: no genes_count_bam has run on this context")
+        return self._genes_bam
 
     def genes_terms(self, thr: Thresholds, reads: "ReadsSoA", ref_id, gene_length):
         """midas_genes_terms(): per read of a slice its term (f64; +0.0 for a read keep_read drops)."""

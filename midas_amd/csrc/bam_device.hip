@@ -37,7 +37,7 @@ int32_t fail(midas_snps_ctx* ctx, int32_t st, const std::string& msg) {
 
 // ---- errors and traces ----------------------------------------------------------------------------------------------------------
 constexpr char kInflate[] = "device inflate", kDecode[] = "device decode", kStreamed[] = "device decode (streamed)",
-               kToColumns[] = "resident BAM to columns";
+               kToColumns[] = "resident BAM to columns", kGenes[] = "genes count over a BAM";
 int32_t hip_err(char* err256, const char* who, hipError_t e, const char* what) {
   if (err256) snprintf(err256, 256, "%s: %s: %s", who, what, hipGetErrorString(e));
   (void)hipGetLastError();
@@ -937,6 +937,9 @@ int32_t decode_streamed_if_large(midas_snps_ctx* ctx, const uint8_t* comp_base, 
 // DeviceDecoder::run (hostio.h): BGZF blocks of a BAM -- the whole file's, a rank's slice, or the runs that hold a rank's contigs --
 // decoded on the device: up, inflated, resolved and CRC-checked (bgzf_inflate.hip), records found and decoded (bam_walk.hip), SEQ /
 // QUAL / CIGAR cut out where the stream lies; the small columns are all that comes down.
+// payload == 3 (midas_genes_count_bam; sink: its GenesBamCall, alloc and res unused): the same steps up to every kept record's
+// offset, then the genes count over the records where they lie (genes_count.hip) -- no columns, no scans, no payload cut, and
+// nothing per read comes down.
 int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob* jobs, size_t n_jobs, uint64_t total, DecodeSegment* segs,
                           size_t n_segs, const int64_t* ref_lens, int32_t n_ref, int payload, int extra, HostColumns (*alloc)(void*, int64_t),
                           void* sink, DeviceDecodeResult* res, int64_t* bad_job, int64_t* bad_record, char* err256) {
@@ -974,8 +977,10 @@ int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob
     fill_inflate_blocks(jobs + lo, segs[k].job_hi - lo, c0, seg_at[k], 0, blocks.data() + lo, want.data() + lo, &n_match_room);
   }
   const InflateLayout L((size_t)total, comp_bytes, n_jobs, (size_t)n_match_room);
-  // (a BAM's columns are ~0.95 of its inflated bytes, the offsets and small columns ~0.2: the scratch must hold them too)
-  const size_t arena_bytes = std::max(L.end, L.at_comp + (size_t)total + (size_t)total / 3 + ((size_t)16 << 20));
+  GenesBamCall* const genes = payload == 3 ? static_cast<GenesBamCall*>(sink) : nullptr;
+  // (a BAM's columns are ~0.95 of its inflated bytes, the offsets and small columns ~0.2: the scratch must hold them too; the
+  // genes count wants 40 bytes a record and 44 a gene instead)
+  const size_t arena_bytes = std::max(L.end, L.at_comp + (size_t)total + (size_t)total / 3 + ((size_t)16 << 20)) + (genes ? (size_t)(n_ref > 0 ? n_ref : 0) * 64 : 0);
   bool pooled = false;
   void* arena_p = ctx->arena->take(arena_bytes, &pooled);
   if (!arena_p) { if (err256) snprintf(err256, 256, "device decode: out of device memory (%.1f GB)", (double)arena_bytes / 1e9); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
@@ -990,9 +995,15 @@ int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob
   // (Inflating a first group of blocks while the next group's bytes go up -- four groups, a stream each -- was built and
   // measured: 216 ms against 188 ms for the whole decode of configs[2]'s BAM on the same box.  The copy threads and the
   // link are slowed by the running kernels by more than the overlap wins.  One upload, one launch.)
+  const auto t_up = Clock::now();
   for (size_t k = 0; k < n_segs; ++k) {
     const int32_t cst = copy_to_device_staged(ctx, base + L.at_comp + seg_at[k], comp_base + jobs[segs[k].job_lo].cpos, seg_at[k + 1] - seg_at[k], s);
     if (cst != MIDAS_SNPS_OK) { if (err256) snprintf(err256, 256, "device decode: blocks to the device: %s", ctx->error_text().c_str()); return cst; }
+  }
+  if (genes) {       // (its laps: the upload by the host's clock, waited for; everything behind it between events)
+    TRY(kGenes, hipStreamSynchronize(s));
+    genes->ms[0] = (float)ms_since(t_up);
+    TRY(kGenes, hipEventRecord(genes->ev[0], s));
   }
   if (lap.on) {      // (phase by phase, each waited for)
     TRY(kDecode, hipStreamSynchronize(s)); lap("blocks up");
@@ -1011,6 +1022,7 @@ int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob
   if (ast != MIDAS_SNPS_OK) return ast;
   if (again) lap("streams decoded again");
   if (check_block_statuses(status, 0, bad_job, err256) != MIDAS_SNPS_OK) return MIDAS_SNPS_ERR_BAD_LAYOUT;
+  if (genes) TRY(kGenes, hipEventRecord(genes->ev[1], s));
   // ---- the record walk: chunks of at most 32 KiB, laid out segment by segment over [from, stop) ---------------------------
   WalkTables walk{kDecode, err256};
   std::vector<size_t> seg_chunk(n_segs + 1, 0);
@@ -1046,6 +1058,19 @@ int32_t device_decode_run(void* user, const uint8_t* comp_base, const InflateJob
   lap("stitch");
   const size_t n1 = (size_t)n + 1;
   unsigned long long* d_rec = sc.as<unsigned long long>(n1 * 8);
+  if (genes) {
+    if (!d_rec) { if (err256) snprintf(err256, 256, "genes count over a BAM: the arena is too small for the record offsets"); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
+    TRY(kGenes, launch_bam_offsets(walk.wp, walk.d_base, d_rec, s));
+    TRY(kGenes, hipEventRecord(genes->ev[2], s));
+    int64_t dropped = 0;
+    for (size_t k = 0; k < n_segs; ++k) dropped += segs[k].n_unmapped;
+    const int64_t stats[8] = {(int64_t)n, dropped, (int64_t)n_jobs, (int64_t)total, (int64_t)walk.h.size(), (int64_t)rounds, 0, 0};
+    memcpy(genes->stats, stats, sizeof stats);
+    const int32_t gst = genes_count_stream(ctx, base, (unsigned long long)total, d_rec, n, sc.p + sc.at, sc.bytes - sc.at, genes);
+    if (gst != MIDAS_SNPS_OK && err256) snprintf(err256, 256, "%s", ctx->error_text().c_str());
+    lap("genes: facts, filter, sort, sums");
+    return gst;
+  }
   BamColumnsParams cp;
   cp.d = base; cp.rec_off = d_rec; cp.n = n; cp.n_ref = n_ref;
   cp.refid = sc.as<int32_t>(n1 * 4); cp.pos = sc.as<int32_t>(n1 * 4);
@@ -1274,6 +1299,34 @@ int32_t midas_bam_resident_to_columns(midas_bam* bam, midas_snps_ctx* ctx, int64
   bam_resident_became_columns(bam, base, base + at_q, base + at_c, own.p, device_free);
   own.p = nullptr;
   return MIDAS_SNPS_OK;
+}
+
+int32_t midas_genes_count_bam(midas_snps_ctx* ctx, midas_bam* bam, const midas_snps_thresholds* thr, int64_t n_genes, const int64_t* gene_length,
+                              int64_t* out_aligned, int64_t* out_mapped, double* out_depth, int64_t* out_stats8, float* out_ms8, char* err256) {
+  if (!ctx || !bam || !thr || n_genes < 0 || (n_genes > 0 && (!gene_length || !out_aligned || !out_mapped || !out_depth))) return MIDAS_SNPS_ERR_INVALID_ARG;
+  ctx->clear_error();
+  ctx->err_read = -1;
+  if (err256) err256[0] = 0;
+  if (n_genes != (int64_t)midas_bam_n_refs(bam)) {
+    if (err256) snprintf(err256, 256, "genes count over a BAM: %lld gene lengths for the %d references of the header", (long long)n_genes, midas_bam_n_refs(bam));
+    return fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, err256 ? err256 : "");
+  }
+  GenesBamCall call;
+  call.thr = thr; call.n_genes = n_genes; call.gene_length = gene_length;
+  call.out_aligned = out_aligned; call.out_mapped = out_mapped; call.out_depth = out_depth;
+  struct Events { GenesBamCall& c; ~Events() { for (hipEvent_t e : c.ev) if (e) (void)hipEventDestroy(e); } } events{call};
+  TRY(kGenes, hipSetDevice(ctx->device));
+  for (hipEvent_t& e : call.ev) TRY(kGenes, hipEventCreate(&e));
+  char text[256] = {0};
+  const DeviceDecoder dec{ctx, device_decode_run};
+  const int32_t st = bam_genes_on_device(bam, &dec, &call, text);
+  if (out_stats8) memcpy(out_stats8, call.stats, sizeof call.stats);
+  if (out_ms8) memcpy(out_ms8, call.ms, sizeof call.ms);
+  if (st != MIDAS_SNPS_OK) {
+    if (err256) snprintf(err256, 256, "%s", text);
+    if (ctx->error_text().empty()) ctx->set_error(text);       // (a status of the decode: the context says what the buffer says)
+  }
+  return st;
 }
 
 int32_t midas_bam_load_ranges_device(midas_bam* bam, midas_snps_ctx* ctx, int32_t n_ranges, const int64_t* range_begin,

@@ -387,6 +387,24 @@ void set_decode_error(char* err256, const char* path, long long bad_fpos, int64_
   else if (otherwise) set_err(err256, otherwise, path);
 }
 
+// What the whole-file device decodes share (bam_decode_on_device, bam_genes_on_device): the job table of the file's blocks, ONE
+// segment from the header's end to the file's, dec->run, and its MIDAS_SNPS_ERR_BAD_LAYOUT turned into the file's text.
+static int32_t decode_whole_file(const midas_bam* b, const uint8_t* base, const std::vector<FileBlk>& blocks, size_t total, const midas::DeviceDecoder* dec,
+                                 int payload, midas::HostColumns (*alloc)(void*, int64_t), void* sink, midas::DeviceDecodeResult* res, char* err256) {
+  std::vector<midas::InflateJob> jobs;
+  jobs.reserve(blocks.size());
+  for (const FileBlk& q : blocks) jobs.push_back({(uint64_t)q.cpos, (uint64_t)q.upos, (uint32_t)q.clen, (uint32_t)q.ulen, rd32(base + q.cpos + q.clen), 1u});
+  int64_t bad_job = -1, bad_record = -1;
+  midas::DecodeSegment seg;
+  seg.job_lo = 0; seg.job_hi = jobs.size(); seg.from = (uint64_t)b->rec_begin; seg.exact = 1; seg.stop = (uint64_t)total;
+  const int32_t st = dec->run(dec->user, base, jobs.data(), jobs.size(), (uint64_t)total, &seg, 1, b->ref_lens.data(), (int32_t)b->ref_lens.size(),
+                              payload, 0, alloc, sink, res, &bad_job, &bad_record, err256);
+  if (st == MIDAS_SNPS_ERR_BAD_LAYOUT)
+    set_decode_error(err256, b->path.c_str(), bad_job >= 0 && (size_t)bad_job < blocks.size() ? (long long)blocks[(size_t)bad_job].fpos : -1, bad_record,
+                     bad_record == -2 ? "%s: malformed alignment record (a block_size that leaves the stream)" : nullptr);
+  return st;
+}
+
 int32_t midas::bam_decode_on_device(const char* path, const midas::DeviceDecoder* dec, midas_bam** out, int64_t* n_reads,
                                     int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar, char* err256, int payload) {
   if (!path || !out || !dec) return MIDAS_SNPS_ERR_INVALID_ARG;
@@ -412,26 +430,38 @@ int32_t midas::bam_decode_on_device(const char* path, const midas::DeviceDecoder
     if (st != MIDAS_SNPS_OK) return st;
   }
   lap("header");
-  std::vector<midas::InflateJob> jobs;
-  jobs.reserve(blocks.size());
-  for (const FileBlk& q : blocks) jobs.push_back({(uint64_t)q.cpos, (uint64_t)q.upos, (uint32_t)q.clen, (uint32_t)q.ulen, rd32(&comp[q.cpos + q.clen]), 1u});
   ColumnSink sink{b.get(), true, payload};
   midas::DeviceDecodeResult res;
-  int64_t bad_job = -1, bad_record = -1;
-  midas::DecodeSegment seg;
-  seg.job_lo = 0; seg.job_hi = jobs.size(); seg.from = (uint64_t)b->rec_begin; seg.exact = 1; seg.stop = (uint64_t)total;
-  st = dec->run(dec->user, comp.data(), jobs.data(), jobs.size(), (uint64_t)total, &seg, 1, b->ref_lens.data(), (int32_t)b->ref_lens.size(),
-                payload, 0, ColumnSink::alloc, &sink, &res, &bad_job, &bad_record, err256);
+  st = decode_whole_file(b.get(), comp.data(), blocks, total, dec, payload, ColumnSink::alloc, &sink, &res, err256);
   lap("device");
-  if (st == MIDAS_SNPS_ERR_BAD_LAYOUT)
-    set_decode_error(err256, path, bad_job >= 0 && (size_t)bad_job < blocks.size() ? (long long)blocks[(size_t)bad_job].fpos : -1, bad_record,
-                     bad_record == -2 ? "%s: malformed alignment record (a block_size that leaves the stream)" : nullptr);
   if (st != MIDAS_SNPS_OK) return st;
   if (!sink.ok) { set_err(err256, "out of memory decoding %s", path); if (res.dev_free && res.dev_owner) res.dev_free(res.dev_owner); return MIDAS_SNPS_ERR_OUT_OF_MEMORY; }
   adopt_device_result(b.get(), res, payload);
   report_totals(res.n_records, res.seq_bytes, res.qual_bytes, res.n_cigar, n_reads, seq_bytes, qual_bytes, n_cigar);
   *out = b.release();
   return MIDAS_SNPS_OK;
+}
+
+// midas_genes_count_bam (bam_device.hip): the whole file to `dec` with payload 3 (decode_whole_file) -- the
+// handle's own mapping and block table when it has them (midas_bam_open_share), else the file read as bam_decode_on_device reads it.
+// Nothing is loaded into the handle.
+int32_t midas::bam_genes_on_device(const midas_bam* b, const midas::DeviceDecoder* dec, void* call, char* err256) {
+  if (!b || !dec || !call || b->loaded) return MIDAS_SNPS_ERR_INVALID_ARG;
+  FileImage comp;
+  std::vector<FileBlk> own;
+  const uint8_t* base = nullptr;
+  const std::vector<FileBlk>* blocks = &own;
+  size_t total = 0;
+  if (b->map && !b->map->local) {
+    base = b->map->base; blocks = &b->map->blocks; total = (size_t)b->map->total;
+  } else {
+    const int32_t st = read_bgzf_file(b->path, comp, own, &total, err256);
+    if (st != MIDAS_SNPS_OK) return st;
+    base = comp.data();
+  }
+  if (blocks->empty() || b->rec_begin > total) { set_err(err256, "%s: truncated BAM header", b->path.c_str()); return MIDAS_SNPS_ERR_BAD_LAYOUT; }
+  midas::DeviceDecodeResult res;
+  return decode_whole_file(b, base, *blocks, total, dec, 3, nullptr, call, &res, err256);
 }
 
 int32_t midas::bam_open_with(const char* path, const midas::BlockInflater* inflater, midas_bam** out, char* err256) {

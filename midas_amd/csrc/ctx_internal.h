@@ -10,6 +10,8 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/midas_snps.h"
+
 // The context's device arena: ONE allocation that the BAM decodes of a context take turns in (a hipMalloc / hipFree pair
 // costs ~17 ms a gigabyte here, and a decode wants a few times the BAM's inflated size).  A decode borrows it (take), a BAM
 // handle whose payload columns were cut into it keeps it until it is closed (give) -- whoever asks meanwhile gets an
@@ -180,4 +182,22 @@ extern const unsigned int kHostAllocFlags;
 int32_t copy_to_host(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t on = nullptr);
 int32_t copy_to_device_staged(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
 void device_free(void* p);
+
+// midas_genes_count_bam: what the entry (bam_device.hip) hands through the decode to the genes count (genes_count.hip).  The decode
+// fills `stats` and the first three laps and records ev[0..2] (inflate begins, inflate done, record offsets written); the genes
+// count records the rest, waits, and turns the events into `ms`.
+struct GenesBamCall {
+  const midas_snps_thresholds* thr;
+  int64_t n_genes;
+  const int64_t* gene_length;
+  int64_t* out_aligned; int64_t* out_mapped; double* out_depth;
+  int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // records kept, dropped for refID < 0, BGZF blocks, inflated bytes, chunks, chunks walked again, 0, 0
+  float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};          // upload, inflate + CRC, walk + stitch + offsets, facts kernel, filter + sort + sums, download, 0, 0
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+// The genes count over the n kept records at rec_off[0, n) (device memory, file order) of the inflated stream d[0, total): facts
+// kernel, then the tail midas_genes_count_device runs; its buffers are carved out of scratch[0, scratch_bytes) (device memory the
+// caller lends: too small is MIDAS_SNPS_ERR_OUT_OF_MEMORY).  Statuses, the context's error text and err_read as midas_genes_count.
+int32_t genes_count_stream(midas_snps_ctx* ctx, const uint8_t* d, unsigned long long total, const unsigned long long* rec_off, long long n,
+                           uint8_t* scratch, size_t scratch_bytes, GenesBamCall* call);
 }  // namespace midas_ctx

@@ -35,6 +35,7 @@
 #include "workers.h"
 #include "device_common.h"
 #include "kernels.h"
+#include "bam_record.h"
 
 namespace midas {
 namespace {
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void genes_filter_kernel(FilterKParams p) {
 // A read pack_records would refuse leaves (read << 8 | kind) in *bad, lowest read first, and a record of zeros; its gene is
 // set to 0 so that the filter kernel behind this one indexes nothing outside the gene table.  Offsets that point outside
 // their column are refused here too (kFactLayout): the host's pass would read whatever lies there, a kernel must not.
-enum : uint32_t { kFactRef = 1, kFactLayout = 2, kFactSize = 3 };
+enum : uint32_t { kFactRef = 1, kFactLayout = 2, kFactSize = 3, kFactRecord = 4 };      // (kFactRecord: bam_genes_facts_kernel's alone)
 constexpr int kFactLanes = 16;
 
 struct FactsKParams {
@@ -171,6 +172,106 @@ __global__ __launch_bounds__(256) void genes_facts_kernel(FactsKParams p) {
   const uint32_t nm_u = (uint32_t)(nm < 0 ? 0 : nm);
   const uint32_t qmean = l > 0 ? qsum / (uint32_t)l : 0u;
   p.rec[i] = make_uint2((uint32_t)al | ((uint32_t)l << 11) | (flags << 22), nm_u | (qmean << 16) | ((uint32_t)p.mapq[i] << 24));
+}
+
+// ---- the 8-byte record straight from the alignment RECORD where it lies in the inflated BAM stream (midas_genes_count_bam) ----------
+// The same sixteen lanes a read, the same granule scheme -- the "column" is the whole stream d[0, total), a record starts at any byte
+// of it, and its QUAL run lies at r + 36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2.  Only the stream's own first and last
+// granule can fail to lie wholly inside it; those are fetched byte by byte, so no load reaches outside [d, d + total) whatever
+// follows the stream in the arena.  Lane 0 walks the CIGAR ends in the record ([EXT], as above) and finds NM in its aux block
+// (bam_record.h find_nm, the one bam_columns_kernel uses).  Nothing was cut into columns for this and nothing per read comes down.
+// Refused, lowest read first, with a record of zeros: a record whose variable parts overrun its block_size or whose refID names no
+// reference (kFactRecord: what bam_columns_kernel calls bad_record; the gene becomes 0), l_seq or NM beyond the record (kFactSize).
+struct BamFactsKParams {
+  const uint8_t* d; unsigned long long total;      // the inflated stream
+  const unsigned long long* rec_off;               // [n] the kept records (refID >= 0), file order (bam_offsets_kernel)
+  uint32_t* gene;                                  // [n] out: refID
+  uint2* rec;                                      // [n] out
+  unsigned long long* bad;                         // atomicMin((read << 8) | kind)
+  long long n, n_genes;
+};
+
+__global__ __launch_bounds__(256) void bam_genes_facts_kernel(BamFactsKParams p) {
+  const int sub = threadIdx.x & (kFactLanes - 1);
+  const long long i = (long long)blockIdx.x * (256 / kFactLanes) + (threadIdx.x / kFactLanes);
+  if (i >= p.n) return;                               // (the same in all sixteen lanes of a read, like everything up to the loads)
+  const unsigned long long u = p.rec_off[i];
+  uint32_t kind = 0;
+  uint32_t bs = 0, w3 = 0, n_cig = 0, l = 0;
+  long long g = 0;
+  unsigned long long body = 0;
+  const uint8_t* r = p.d + u;
+  if (u + 36ull > p.total) {                          // (the walk hands out no such offset: nothing is read through it all the same)
+    kind = kFactRecord;
+  } else {
+    bs = rd32(r);
+    g = (long long)(int32_t)rd32(r + 4);
+    w3 = rd32(r + 12);
+    n_cig = rd32(r + 16) & 0xFFFFu;
+    l = rd32(r + 20);
+    body = 32ull + (w3 & 0xFFu) + 4ull * n_cig + ((unsigned long long)l + 1ull) / 2ull + l;
+    if (u + 4ull + bs > p.total || body > bs || g < 0 || g >= p.n_genes) kind = kFactRecord;
+    else if (l > (uint32_t)kMaxLSeq) kind = kFactSize;
+  }
+  if (kind) {
+    if (sub == 0) {
+      atomicMin(p.bad, ((unsigned long long)i << 8) | kind);
+      p.rec[i] = make_uint2(0u, 0u);
+      p.gene[i] = kind == kFactRecord ? 0u : (uint32_t)g;
+    }
+    return;
+  }
+  const uint32_t lrn = w3 & 0xFFu;
+  // ---- sum of the l quality bytes ------------------------------------------------------------------------------------------
+  const unsigned long long col_lo = (unsigned long long)p.d, col_hi = col_lo + p.total;
+  const unsigned long long q0 = u + 36ull + lrn + 4ull * n_cig + (l + 1u) / 2u;
+  const unsigned long long run_lo = col_lo + q0, run_hi = run_lo + l;
+  uint32_t qsum = 0;
+  for (unsigned long long b = (run_lo & ~15ull) + 16ull * (unsigned)sub; b < run_hi; b += 16ull * kFactLanes) {
+    const unsigned long long lo = b < run_lo ? run_lo : b, hi = b + 16 > run_hi ? run_hi : b + 16;     // the run's bytes of this granule
+    if (b >= col_lo && b + 16 <= col_hi) {
+      const uint4 v = *reinterpret_cast<const uint4*>(p.d + (b - col_lo));           // (off the stream's pointer: a global load)
+      const uint32_t m = ((1u << (unsigned)(hi - b)) - 1u) & ~((1u << (unsigned)(lo - b)) - 1u);         // (hi - b <= 16)
+      qsum = __builtin_amdgcn_sad_u8(v.x & byte_mask4(m & 15u), 0u, qsum);
+      qsum = __builtin_amdgcn_sad_u8(v.y & byte_mask4((m >> 4) & 15u), 0u, qsum);
+      qsum = __builtin_amdgcn_sad_u8(v.z & byte_mask4((m >> 8) & 15u), 0u, qsum);
+      qsum = __builtin_amdgcn_sad_u8(v.w & byte_mask4((m >> 12) & 15u), 0u, qsum);
+    } else {
+      for (unsigned long long a = lo; a < hi; ++a) qsum += p.d[a - col_lo];            // (the stream's border granule: < 16 bytes)
+    }
+  }
+#pragma unroll
+  for (int w = kFactLanes / 2; w >= 1; w >>= 1) qsum += (uint32_t)__shfl_xor((int)qsum, w, kFactLanes);
+  if (sub != 0) return;
+  const long long nm = find_nm(r + 4 + body, r + 4 + bs);
+  p.gene[i] = (uint32_t)g;
+  if (nm > kMaxField16) {
+    atomicMin(p.bad, ((unsigned long long)i << 8) | kFactSize);
+    p.rec[i] = make_uint2(0u, 0u);
+    return;
+  }
+  // ---- [EXT] pysam query_alignment_start / _end, as pack_records walks them -----------------------------------------------------
+  const uint8_t* cg = r + 36 + lrn;
+  const long long nc = n_cig;
+  long long qs = 0;
+  for (long long k = 0; k < nc; ++k) {
+    const uint32_t w = rd32(cg + 4 * k), op = w & 15u;
+    if (op == 5u) continue;
+    if (op == 4u) qs += w >> 4; else break;
+  }
+  long long qe = l;
+  for (long long k = nc - 1; k >= 1; --k) {
+    const uint32_t w = rd32(cg + 4 * k), op = w & 15u;
+    if (op == 5u) continue;
+    if (op == 4u) qe -= w >> 4; else break;
+  }
+  long long al = qe - qs > 0 ? qe - qs : 0;
+  if (al > (long long)l) al = l;
+  const bool no_qual = l > 0 && p.d[q0] == 0xFFu;
+  const uint32_t flags = (l == 0 ? kNoSeq : 0u) | (nm < 0 ? kNoNm : 0u) | (no_qual ? kNoQual : 0u);
+  const uint32_t nm_u = (uint32_t)(nm < 0 ? 0 : nm);
+  const uint32_t qmean = l > 0 ? qsum / l : 0u;
+  p.rec[i] = make_uint2((uint32_t)al | (l << 11) | (flags << 22), nm_u | (qmean << 16) | (((w3 >> 8) & 0xFFu) << 24));
 }
 
 // first sorted position of every gene: begin[g] = lowest i with key[i] >= g; begin[n_genes] = n
@@ -310,13 +411,17 @@ struct DevBufs {
   } while (0)
 
 // The first read in BAM order that no record can be made of: the status and message of both routes (pack_records on the host,
-// genes_facts_kernel on the device).
+// genes_facts_kernel / bam_genes_facts_kernel on the device; ref_id: not looked at for the latter's kinds).
 int32_t raise_malformed(midas_snps_ctx* ctx, int64_t first, uint32_t kind, const int32_t* ref_id) {
   ctx->err_read = first;
   char buf[200];
   if (kind == kFactRef) {
     snprintf(buf, sizeof buf, "read %lld: reference id %lld is not a gene of the pangenome (the reference fails in getrname / genes[...])",
              (long long)first, (long long)ref_id[first]);
+    return gfail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+  }
+  if (kind == kFactRecord) {
+    snprintf(buf, sizeof buf, "read %lld: the alignment record overruns its block_size or names no reference of the header", (long long)first);
     return gfail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
   }
   if (kind == kFactLayout) return gfail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, "negative size or CSR offsets shorter than l_seq");
@@ -390,6 +495,57 @@ int32_t raise_status(midas_snps_ctx* ctx, unsigned long long err) {
   return kind;
 }
 
+// The device buffers behind the records, whoever made them and wherever they were allocated: (gene, record) pairs in, per-gene
+// numbers out.
+struct GenesBufs {
+  uint2* recs; uint32_t* key; uint32_t* key_b; double* term; double* term_b; int64_t* len; FilterTables* ft;
+  long long* begin; long long* al; long long* mp; double* dp; unsigned long long* err; unsigned int* heavy; uint32_t* hist;
+};
+
+// The tail every route shares: filter (filter: the terms are made from b.recs; else b.term holds them), the terms handed back
+// (out_term), and with out_aligned the stable sort by gene, the bounds, the ordered sums and their way down.  Everything is queued
+// on s and nothing is waited for; e1 is recorded behind the last kernel.
+int32_t genes_tail(midas_snps_ctx* ctx, hipStream_t s, const midas_snps_thresholds* thr, const GenesBufs& b, int64_t n, int64_t n_genes, bool filter,
+                   double* out_term, int64_t* out_aligned, int64_t* out_mapped, double* out_depth, hipEvent_t e1) {
+  const bool sums = out_aligned != nullptr;
+  int key_bits = 1;
+  while (key_bits < 32 && ((int64_t)1 << key_bits) < n_genes) ++key_bits;
+  if (filter && n > 0) {
+    FilterKParams f;
+    f.rec = b.recs; f.gene = b.key; f.gene_len = b.len; f.filt = b.ft; f.term = b.term; f.err = b.err; f.n = n;
+    f.mapq = thr->mapq; f.readq = thr->readq;
+    hipLaunchKernelGGL(genes_filter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, f);
+    G_TRY(hipGetLastError());
+  }
+  if (out_term && n > 0) G_TRY(hipMemcpyAsync(out_term, b.term, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+  if (sums && n_genes > 0) {
+    uint32_t* d_key_sorted = b.key;
+    double* d_term_sorted = b.term;
+    G_TRY(launch_sort_pairs_f64(b.key, b.term, b.key_b, b.term_b, n, key_bits, b.hist, s, &d_key_sorted, &d_term_sorted));
+    hipLaunchKernelGGL(genes_bounds_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s, d_key_sorted, (long long)n,
+                       (long long)n_genes, b.begin);
+    G_TRY(hipGetLastError());
+    SumKParams k;
+    k.term = d_term_sorted; k.begin = b.begin; k.aligned = b.al; k.mapped = b.mp; k.depth = b.dp;
+    k.heavy_count = b.heavy; k.heavy = b.heavy + 1; k.n_genes = n_genes;
+    hipLaunchKernelGGL(genes_sum_kernel, dim3((unsigned)((n_genes + 255) / 256)), dim3(256), 0, s, k);
+    G_TRY(hipGetLastError());
+    // at most n / kHeavyGene genes are heavy; idle waves leave at once
+    const long long max_heavy = std::min<long long>(n_genes, n / kHeavyGene);
+    if (max_heavy > 0) {
+      hipLaunchKernelGGL(genes_sum_heavy_kernel, dim3((unsigned)max_heavy), dim3(64), 0, s, k);
+      G_TRY(hipGetLastError());
+    }
+    G_TRY(hipEventRecord(e1, s));
+    G_TRY(hipMemcpyAsync(out_aligned, b.al, (size_t)n_genes * 8, hipMemcpyDeviceToHost, s));
+    G_TRY(hipMemcpyAsync(out_mapped, b.mp, (size_t)n_genes * 8, hipMemcpyDeviceToHost, s));
+    G_TRY(hipMemcpyAsync(out_depth, b.dp, (size_t)n_genes * 8, hipMemcpyDeviceToHost, s));
+  } else {
+    G_TRY(hipEventRecord(e1, s));
+  }
+  return MIDAS_SNPS_OK;
+}
+
 // One call, either half or both.  reads != nullptr: the terms are made here (records + filter kernel) from the reads and
 // their genes `gene` (= ref_id) -- the records by the host's cores (pack_records), or, with payload_on_device (reads->qual /
 // ->cigar are device addresses), by genes_facts_kernel; everything behind the records is the same; else `term_in` holds them.  out_term != nullptr: they are handed back (and, with no sums asked
@@ -456,8 +612,6 @@ int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const m
     G_TRY(dev.get(&d_dp, ng * 8));
     G_TRY(dev.get(&d_heavy, (ng + 1) * 4));
   }
-  int key_bits = 1;
-  while (key_bits < 32 && ((int64_t)1 << key_bits) < n_genes) ++key_bits;
   if (n > 0) {
     G_TRY(hipMemcpyAsync(d_key, gene, (size_t)n * 4, hipMemcpyHostToDevice, s));
     if (facts) {
@@ -498,39 +652,11 @@ int32_t genes_run(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const m
     }
     G_TRY(hipEventRecord(ef, s));
   }
-  if (filter && n > 0) {
-    FilterKParams f;
-    f.rec = d_recs; f.gene = d_key; f.gene_len = d_len; f.filt = d_ft; f.term = d_term; f.err = d_err; f.n = n;
-    f.mapq = thr->mapq; f.readq = thr->readq;
-    hipLaunchKernelGGL(genes_filter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, f);
-    G_TRY(hipGetLastError());
-  }
-  if (out_term && n > 0) G_TRY(hipMemcpyAsync(out_term, d_term, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  if (sums && n_genes > 0) {
-    uint32_t* d_key_sorted = d_key;
-    double* d_term_sorted = d_term;
-    G_TRY(launch_sort_pairs_f64(d_key, d_term, d_key_b, d_term_b, n, key_bits, d_hist, s, &d_key_sorted, &d_term_sorted));
-    hipLaunchKernelGGL(genes_bounds_kernel, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s, d_key_sorted, (long long)n,
-                       (long long)n_genes, d_begin);
-    G_TRY(hipGetLastError());
-    SumKParams k;
-    k.term = d_term_sorted; k.begin = d_begin; k.aligned = d_al; k.mapped = d_mp; k.depth = d_dp;
-    k.heavy_count = d_heavy; k.heavy = d_heavy + 1; k.n_genes = n_genes;
-    hipLaunchKernelGGL(genes_sum_kernel, dim3((unsigned)((n_genes + 255) / 256)), dim3(256), 0, s, k);
-    G_TRY(hipGetLastError());
-    // at most n / kHeavyGene genes are heavy; idle waves leave at once
-    const long long max_heavy = std::min<long long>(n_genes, n / kHeavyGene);
-    if (max_heavy > 0) {
-      hipLaunchKernelGGL(genes_sum_heavy_kernel, dim3((unsigned)max_heavy), dim3(64), 0, s, k);
-      G_TRY(hipGetLastError());
-    }
-    G_TRY(hipEventRecord(e1, s));
-    G_TRY(hipMemcpyAsync(out_aligned, d_al, (size_t)n_genes * 8, hipMemcpyDeviceToHost, s));
-    G_TRY(hipMemcpyAsync(out_mapped, d_mp, (size_t)n_genes * 8, hipMemcpyDeviceToHost, s));
-    G_TRY(hipMemcpyAsync(out_depth, d_dp, (size_t)n_genes * 8, hipMemcpyDeviceToHost, s));
-  } else {
-    G_TRY(hipEventRecord(e1, s));
-  }
+  GenesBufs gb;
+  gb.recs = d_recs; gb.key = d_key; gb.key_b = d_key_b; gb.term = d_term; gb.term_b = d_term_b; gb.len = d_len; gb.ft = d_ft;
+  gb.begin = d_begin; gb.al = d_al; gb.mp = d_mp; gb.dp = d_dp; gb.err = d_err; gb.heavy = d_heavy; gb.hist = d_hist;
+  const int32_t tst = genes_tail(ctx, s, thr, gb, n, n_genes, filter, out_term, out_aligned, out_mapped, out_depth, e1);
+  if (tst != MIDAS_SNPS_OK) return tst;
   G_TRY(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, s));
   G_TRY(hipStreamSynchronize(s));
   float ms = 0.f;
@@ -554,6 +680,62 @@ bool reads_ok(const midas_snps_reads* reads, const int32_t* ref_id) {
 }
 
 }  // namespace
+
+// midas_genes_count_bam behind its decode (bam_device.hip): the facts from the records where they lie, then the tail.
+int32_t midas_ctx::genes_count_stream(midas_snps_ctx* ctx, const uint8_t* d, unsigned long long total, const unsigned long long* rec_off, long long n,
+                                      uint8_t* scratch, size_t scratch_bytes, GenesBamCall* call) {
+  ctx->clear_error();
+  ctx->err_read = -1;
+  const int64_t n_genes = call->n_genes;
+  if (n > 0x7FFFFFFFll || n_genes > 0x7FFFFFFFll) return gfail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "more than 2^31-1 reads or genes");
+  FilterTables ft;
+  memset(&ft, 0, sizeof ft);
+  build_filter_tables(call->thr->mapid, call->thr->aln_cov, kMaxLSeq, &ft);        // (every length a record can hold, as midas_genes_count_device)
+  hipStream_t s = ctx->stream;
+  const size_t ng = (size_t)(n_genes > 0 ? n_genes : 1), nr = (size_t)(n > 0 ? n : 1);
+  size_t at = 0;
+  bool fits = true;
+  auto take = [&](size_t bytes) -> void* {       // pieces of the caller's scratch, 256-byte aligned
+    uint8_t* q = scratch + at;
+    at += (bytes + 255) & ~(size_t)255;
+    if (at > scratch_bytes) fits = false;
+    return q;
+  };
+  GenesBufs b;
+  b.key = static_cast<uint32_t*>(take(nr * 4)); b.term = static_cast<double*>(take(nr * 8)); b.err = static_cast<unsigned long long*>(take(16));
+  b.recs = static_cast<uint2*>(take(nr * sizeof(uint2))); b.len = static_cast<int64_t*>(take(ng * 8)); b.ft = static_cast<FilterTables*>(take(sizeof(FilterTables)));
+  b.key_b = static_cast<uint32_t*>(take(nr * 4)); b.term_b = static_cast<double*>(take(nr * 8));
+  b.hist = static_cast<uint32_t*>(take(sort_scratch_words((long long)nr) * 4));
+  b.begin = static_cast<long long*>(take((ng + 1) * 8)); b.al = static_cast<long long*>(take(ng * 8)); b.mp = static_cast<long long*>(take(ng * 8));
+  b.dp = static_cast<double*>(take(ng * 8)); b.heavy = static_cast<unsigned int*>(take((ng + 1) * 4));
+  if (!fits) return gfail(ctx, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "genes count over a BAM: the decode's arena is too small for the per-read terms");
+  if (n_genes > 0) G_TRY(hipMemcpyAsync(b.len, call->gene_length, (size_t)n_genes * 8, hipMemcpyHostToDevice, s));
+  G_TRY(hipMemcpyAsync(b.ft, &ft, sizeof ft, hipMemcpyHostToDevice, s));
+  G_TRY(hipMemsetAsync(b.err, 0xFF, 16, s));          // [0]: the filter's, [1]: the facts kernel's
+  G_TRY(hipMemsetAsync(b.heavy, 0, 4, s));
+  if (n > 0) {
+    BamFactsKParams f;
+    f.d = d; f.total = total; f.rec_off = rec_off; f.gene = b.key; f.rec = b.recs; f.bad = b.err + 1; f.n = n; f.n_genes = n_genes;
+    constexpr int kPerBlock = 256 / kFactLanes;
+    hipLaunchKernelGGL(bam_genes_facts_kernel, dim3((unsigned)((n + kPerBlock - 1) / kPerBlock)), dim3(256), 0, s, f);
+    G_TRY(hipGetLastError());
+  }
+  G_TRY(hipEventRecord(call->ev[3], s));
+  int64_t dummy_a = 0, dummy_m = 0;
+  double dummy_d = 0.0;
+  const int32_t tst = genes_tail(ctx, s, call->thr, b, n, n_genes, true, nullptr, n_genes > 0 ? call->out_aligned : &dummy_a,
+                                 n_genes > 0 ? call->out_mapped : &dummy_m, n_genes > 0 ? call->out_depth : &dummy_d, call->ev[4]);
+  if (tst != MIDAS_SNPS_OK) return tst;
+  unsigned long long err[2] = {~0ull, ~0ull};
+  G_TRY(hipMemcpyAsync(err, b.err, 16, hipMemcpyDeviceToHost, s));
+  G_TRY(hipEventRecord(call->ev[5], s));
+  G_TRY(hipStreamSynchronize(s));
+  for (int k = 1; k < 6; ++k) G_TRY(hipEventElapsedTime(&call->ms[k], call->ev[k - 1], call->ev[k]));
+  // a read no record could be made of comes first, as on the host's route
+  if (err[1] != ~0ull) return raise_malformed(ctx, (int64_t)(err[1] >> 8), (uint32_t)(err[1] & 0xFF), nullptr);
+  if (err[0] != ~0ull) return raise_status(ctx, err[0]);
+  return MIDAS_SNPS_OK;
+}
 
 extern "C" int32_t midas_genes_count(midas_snps_ctx* ctx, const midas_snps_thresholds* thr, const midas_snps_reads* reads,
                                      const int32_t* ref_id, int64_t n_genes, const int64_t* gene_length,

@@ -109,6 +109,9 @@ struct DeviceDecoder {
 };
 int32_t bam_decode_on_device(const char* path, const DeviceDecoder* dec, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
                              int64_t* qual_bytes, int64_t* n_cigar, char* err256, int payload = 1);
+// midas_genes_count_bam (bam_device.hip): an open handle on which nothing has been loaded, its whole file handed to dec->run with
+// payload == 3 and `call` as the sink; nothing is loaded into the handle.  Statuses and texts as bam_decode_on_device's.
+int32_t bam_genes_on_device(const midas_bam* b, const DeviceDecoder* dec, void* call, char* err256);
 // a handle decoded with payload == 2: its device columns (nullptr: it is not such a handle), record count and array totals
 const ResidentReads* bam_resident(const midas_bam* b, int64_t* n_records, int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar);
 // midas_bam_resident_to_columns (bam_device.hip): the handle's host columns for n records (false: out of memory); then the handle

@@ -8,6 +8,8 @@ added to the gene's depth in BAM order, so the fp64 sums are the reference's bit
 --sam: bowtie2's own SAM text (genes/temp/pangenomes.sam) stands in for the BAM and samtools is not needed -- the text is
 parsed on the device in the order of its lines (= the BAM's order) and the per-read facts are made there as well
 (read_sam(order='file'), midas_genes_count_device).
+--device_inflate: pangenomes.bam itself counted in one pass on the device (midas_genes_count_bam) -- blocks inflated, records
+walked, every read's facts made from its record where it lies; the per-gene arrays are all that comes down.
 """
 
 import csv
@@ -306,6 +308,63 @@ def _count_from_sam(args, species, genes, ctx, sam_path):
     return ms
 
 
+# --device_inflate auto takes the one-pass device route for a pangenomes.bam of at least this many bytes (None: for none, 'on'
+# selects it).  The rule (profiles/genes_bam.txt): the smallest size measured by tools/genes_bam_e2e.py at which the device route's
+# median lies below the host route's by more than the spread (max - min) of either route's runs -- the 3.4 M read file of the
+# README's shape (104 ms against 307 ms); at a tenth of it the host's threads were faster (36 ms against 48 ms).
+AUTO_DEVICE_BAM_BYTES = 497616082
+
+
+def bam_route(option, ctx_has_entry, names_known, one_rank, bam_bytes=0, auto_bytes=AUTO_DEVICE_BAM_BYTES):
+    """Which route counts pangenomes.bam: 'device' (midas_genes_count_bam, one pass) or 'host' (read_bam + midas_genes_count).
+    option: --device_inflate; ctx_has_entry: the context offers genes_count_bam; names_known: every gene of the BAM header is in the
+    pangenome database (else the host route, whose _missing_gene_check looks at the reads of such a gene); one_rank: no species
+    are dealt to other ranks."""
+    if option == 'off' or not (ctx_has_entry and names_known and one_rank):
+        return 'host'
+    if option == 'on':
+        return 'device'
+    return 'device' if auto_bytes is not None and bam_bytes >= auto_bytes else 'host'
+
+
+def _count_from_bam_on_device(args, species, genes, ctx, bam_path, option):
+    """genes.py:165-199 over pangenomes.bam in one pass on the device (midas_genes_count_bam).  -> the kernel milliseconds, or None:
+    the host route takes over (a header gene the database lacks; under auto, a device that could not)."""
+    try:
+        handle = abi.open_bam_device(bam_path, ctx)
+    except abi.MidasSnpsError as e:
+        sys.exit("\nError: could not read %s\n%s\n" % (bam_path, e.message))
+    try:
+        gene_ids = list(handle.ref_names)
+        if bam_route(option, True, all(n in genes for n in gene_ids), True, os.path.getsize(bam_path)) != 'device':
+            return None
+        lengths = np.array([genes[n].length for n in gene_ids], dtype=np.int64)
+        try:
+            aligned, mapped, depth, ms = ctx.genes_count_bam(_thresholds(args), handle, lengths)
+        except abi.MidasSnpsError as e:
+            # (record boundaries the device's walk could not settle -- ERR_UNSUPPORTED naming no read -- are the host walk's under auto
+            # as well, as midas_bam_load_device hands them over: auto must not refuse a file the host's threads decode)
+            if e.status in (abi.ERR_OUT_OF_MEMORY, abi.ERR_HIP) or (e.status == abi.ERR_UNSUPPORTED and e.read_index < 0 and option != 'on'):
+                if option == 'on':
+                    sys.exit("\nError: --device_inflate on: %s\n" % e.message)
+                if args.get('log') is not None:
+                    args['log'].write("pangenomes.bam: the one-pass device route could not (%s); the host's threads decode it\n" % e.message)
+                return None
+            if e.read_index >= 0:
+                sys.exit("\nError: %s [read %d of the BAM]\n" % (e.message, e.read_index))
+            sys.exit("\nError: could not read %s\n%s\n" % (bam_path, e.message))
+        stats = ctx.genes_count_bam_timing()[1]
+    finally:
+        handle.close()
+    if args.get('log') is not None:
+        args['log'].write("pangenomes.bam: one pass on the device (--device_inflate %s), %d records decoded, %d without a reference dropped\n"
+                          % (option, stats['records'], stats['dropped']))
+    fold_counts(species, genes, gene_ids, aligned, mapped, depth)
+    print("  total aligned reads: %s" % sum(sp.aligned_reads for sp in species.values()))
+    print("  total mapped reads: %s" % sum(sp.mapped_reads for sp in species.values()))
+    return ms
+
+
 def count_mapped_bp(args, species, genes, ctx, mine=None, owner=None):
     """genes.py:165-199 with the BAM pass on the device: native BAM decode, one midas_genes_count call.  `mine` (N > 1):
     the species this rank owns -- only reads on their genes are counted here; with `owner` (species -> rank) and a BAM whose
@@ -327,10 +386,18 @@ def count_mapped_bp(args, species, genes, ctx, mine=None, owner=None):
                 return _count_below_the_species(args, species, genes, ctx, mine, owner, sl)
             finally:
                 sl.close()
+    option = args.get('device_inflate') or 'auto'
+    # (before the file is opened: with every name known and this file's size -- what the route can still lose is the names)
+    if bam_route(option, hasattr(ctx, 'genes_count_bam'), True, mine is None, os.path.getsize(bam_path) if os.path.isfile(bam_path) else 0) == 'device':
+        ms = _count_from_bam_on_device(args, species, genes, ctx, bam_path, option)
+        if ms is not None:
+            return ms
     try:
         ref_names, ref_lens, refid, reads = abi.read_bam(bam_path)
     except abi.MidasSnpsError as e:
         sys.exit("\nError: could not read %s\n%s\n" % (bam_path, e.message))
+    if mine is None and args.get('log') is not None:
+        args['log'].write("pangenomes.bam: decoded by the host's threads, %d records\n" % int(reads.n_reads))
     _missing_gene_check(ref_names, refid, genes)
     gene_ids = list(ref_names)
     if mine is not None:     # this rank's genes, and the reads on them (BAM order inside a gene is kept)

@@ -127,6 +127,13 @@ def build_genes_parser():
     parser.add_argument('program', help=argparse.SUPPRESS)
     parser.add_argument('outdir', help="sample directory (its name is the sample id)")
     parser.add_argument('--remove_temp', action='store_true', help="delete <outdir>/genes/temp when done")
+    parser.add_argument('--device_inflate', choices=('auto', 'on', 'off'), default='auto',
+                        help="--call_genes over pangenomes.bam in one pass on the GPU (blocks inflated, records walked and every read's\n"
+                             "facts made there; nothing per read comes down) instead of decoding it with the host's threads; one rank\n"
+                             "only.  auto (default): for a pangenomes.bam of at least 497.6 MB, the smallest size measured at which the one\n"
+                             "pass beat the host's threads (profiles/genes_bam.txt); in auto a device that cannot (out of memory, HIP\n"
+                             "error, record boundaries its walk does not settle) hands over to the host's threads, with 'on' that is\n"
+                             "an error; off: the host's threads")
     for title, options in GENES_OPTION_GROUPS:
         group = parser.add_argument_group(title)
         for flags, kw in options:
