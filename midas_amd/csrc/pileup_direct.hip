@@ -20,14 +20,18 @@
 //
 // Lane mapping.  A lane owns LB (30, 32 or 38: direct_lane_bases below) consecutive bases of a read's STORED query: two 16-byte
 // loads of base bytes, and an 8-byte one for 38.  A read of l_seq bases takes ceil(l_seq / LB) adjacent lanes (4 for 150 bp, 5
-// for 151).  Loads are issued two iterations (the read's record: one dwordx4) and one iteration (bases + the first four
-// CIGAR ops + the quality sum: three dwordx4 and a dword off ONE scalar base per wave-iteration -- the payload of the
-// iteration's first read -- plus a 32-bit lane offset) ahead of their use; none of them sits in a branch.
+// for 151).  A lane's loads are issued two iterations (the payload offset and lengths of its read, out of the read's record) and
+// one iteration (its bases, off ONE scalar base per wave-iteration -- the payload of the iteration's first read -- plus a
+// 32-bit lane offset) ahead of their use; none of them sits in a branch.
 //
-// Per read.  The lanes of a read decide in registers what its CIGAR is: ONE or TWO gap-free match runs (direct_common.h
-// ReadShape: clips, at most one insertion / deletion / skip -- what an aligner writes for nearly every read) are tallied
-// straight from the shape, the lane that holds the indel in a second masked pass; anything else (several indels, pads, odd
-// clips, no NM / SEQ, a start off the contig) is walked op by op where it lies, the slow path.
+// Per read, ONCE per read.  What does not depend on the lane -- the shape of the read's CIGAR, ONE or TWO gap-free match runs
+// (direct_common.h ReadShape: clips, at most one insertion / deletion / skip -- what an aligner writes for nearly every read), the
+// two filter tables, keep_read, the read's count and its error -- is done by ONE lane per read for a PHASE of up to four of the
+// wave's iterations (64 reads: one per lane) from loads of its own (record, first four CIGAR ops, quality sum: once per read), and
+// handed to the lanes that hold the read's bases in four words: a DPP quad move where a read has four lanes, ds_bpermute_b32
+// otherwise.  Those lanes clip the runs to the tile and tally them straight from the shape, the lane that holds the indel in a
+// second masked pass.  Anything else (several indels, pads, odd clips, no NM / SEQ, a start off the contig) is walked op by op
+// by the lanes of the read at the start of its phase, the slow path, from loads of its own.
 //
 // Per base: the counter offsets of four bases are `(word << 2) & 0x0C0C0C0C` (two ALU ops a word); then per base one SDWA OR
 // forming the LDS address, one SDWA compare `byte >= thr` (thr = layout.h dense_threshold(baseq), wave-uniform) into a lane
@@ -56,6 +60,13 @@ namespace {
 #endif
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Lane J of every quad's word, on all four lanes of the quad: one DPP move, nothing through the LDS pipeline.
+template <int J>
+__device__ __forceinline__ uint32_t quad_take(uint32_t x) {
+  static_assert(J >= 0 && J < 4, "a lane of the quad");
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, J * 0x55, 0xF, 0xF, false);
+}
 
 // Eight bases of one lane: b0 / b1 two words of four base bytes (layout.h dense_byte, bases in order), thr the byte threshold
 // (dense_threshold, wave-uniform).  Per base one SDWA OR forming the LDS address of its counter ((byte & 3) << 2, two ALU ops a
@@ -292,13 +303,37 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     if constexpr (NG > 4) group(integral_constant<int, 4>{}, integral_constant<int, LB - 32>{});
   };
 
-  // ---- stage F: the record of this lane's read in wave-iteration `it` of a tile's stream: ONE dwordx4.  Raw loads: nothing is
-  // computed from them here, and NO load sits in a branch -- a lane without a read fetches read 0's record, a lane without
+  // ---- phases.  What a read needs done ONCE -- its CIGAR's shape, the two filter tables, keep_read, its count in the species'
+  // counters, its error -- is done by ONE lane for it, for a PHASE of up to PH of the wave's iterations at a time (PH * rpw <= 64
+  // reads: four iterations of 16 reads of four lanes), and not by each of its lanes in each iteration: a wave instruction costs
+  // the same for 16 useful lanes as for 64.  The lane that owns read `og` of the phase's iteration `oj` loads the read's record,
+  // its first four CIGAR ops and its quality sum, and packs what the lanes with the read's bases need into four words (Desc);
+  // they fetch them in their iteration -- with four lanes per read the owner of read g of iteration j is lane 4 g + j, and the
+  // fetch is a DPP quad_perm:[j,j,j,j] move (j static in the unrolled body: nothing goes through the LDS pipeline); any other
+  // lane count: lane j * rpw + g and ds_bpermute_b32.  A phase never straddles a tile.  PH is even where two iterations fit
+  // (the two sets of base registers keep their roles inside a tile); with one lane per read a phase is one iteration.
+  const int ph_fit = 64 / rpw;
+  const int PH = ph_fit >= 4 ? 4 : (ph_fit >= 2 ? 2 : 1);
+  const bool quad = lpr == 4;
+  // (one register: the iteration oj of its phase and the read og of that iteration this lane owns, as the read's place among the
+  // wave's reads of the phase's tile, oj * NWAVES * rpw + og, with oj in the top byte)
+  const uint32_t own_slot = quad ? (uint32_t)((lane & 3) * NWAVES * rpw + (lane >> 2)) | ((uint32_t)(lane & 3) << 24)
+                                 : (uint32_t)((lane / rpw) * NWAVES * rpw + lane % rpw) | ((uint32_t)(lane / rpw) << 24);
+  const bool lane_on = g < rpw;                                  // (64 % lpr lanes at the wave's end never hold a read)
+  // iterations of the phase that opens with `rem` of the wave's iterations of a tile left: PH, but 2 + 3 for the last five of PH =
+  // 4 (not 4 + 1: a phase of at least two iterations requests the next phase's CIGARs a whole iteration ahead of their use)
+  auto phase_len = [&](int rem) -> int { return (PH == 4 && rem == 5) ? 2 : (rem < PH ? rem : PH); };
+  auto wave_its = [&](const Stream& s) -> int { return s.total > wave ? (s.total - wave + NWAVES - 1) / NWAVES : 0; };
+
+  // ---- loads.  NO load sits in a branch of the iteration's body -- a lane without a read fetches read 0's record, a lane without
   // bases the first bytes of the iteration's payload -- so that the compiler can count the loads in flight (a load in a branch
   // makes it wait for every outstanding load, vmcnt(0), before the first use of any of them: the prefetch of the next
   // iteration's bases would be waited for at once).
+  //   nmq: NM (16 bits, 0xFFFF = no NM tag) | mapq << 16      l_nc: l_seq | n_cigar << 16
   struct Raw { uint32_t pos, l_nc, nmq, off; };
   const uint4* const recs = reinterpret_cast<const uint4*>(p.rec);
+  // the record of this lane's read in wave-iteration `it` of a tile's stream: ONE dwordx4, of which the base loads of the iteration
+  // take the payload offset and the lengths (two iterations ahead of the iteration, as the phases' own loads are not)
   auto fetch = [&](const Stream& st, int it) -> Raw {
     const uint32_t v = (uint32_t)(it * rpw) + (uint32_t)g;       // (a stream holds fewer than 2^31 reads, it * rpw <= n0 + 63)
     const uint32_t r = v < (uint32_t)st.n0 ? (uint32_t)st.rb + v : 0u;
@@ -307,60 +342,79 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     f.pos = x.x; f.l_nc = x.y; f.nmq = x.z; f.off = x.w;
     return f;
   };
-  // ---- stage D: what the read's processing needs of its record, and the lane's bases (two 16-byte loads of base bytes, and
-  // an 8-byte one behind them for 38 bases: the payload's slack covers what the read's last lane fetches behind it) + the
-  // read's first four CIGAR ops (one 16-byte load; the payload has slack behind its last read) + its quality sum (one dword).
-  // The four loads go off ONE scalar base -- the payload of the iteration's first read (lane 0's) -- plus a 32-bit lane offset:
-  // the reads of an iteration are neighbours in the payload.
-  //   nmq: NM (16 bits, 0xFFFF = no NM tag) | mapq << 16 | kGenIdle << 24 (a lane without a read)      l_nc: l_seq | n_cigar << 16
-  struct Rd { uint32_t pos, nmq, l_nc; };
-  struct Dat { uint32_t b[NW]; uint32_t cg[4]; uint32_t qs; };
-  auto settle = [&](const Raw& f, int n_reads_it, Rd& r, Dat& d) {
+  // the lane's bases (two 16-byte loads of base bytes, and an 8-byte one behind them for 38 bases: the payload's slack covers
+  // what the read's last lane fetches behind it), off ONE scalar base -- the payload of the iteration's first read (lane 0's) --
+  // plus a 32-bit lane offset: the reads of an iteration are neighbours in the payload.
+  auto settle = [&](const Raw& f, int n_reads_it, uint32_t (&b)[NW]) {
     const bool act = g < n_reads_it;
     const uint32_t l_nc = act ? f.l_nc : 0u;
-    r.pos = f.pos;
-    r.l_nc = l_nc;
-    r.nmq = act ? f.nmq : ((uint32_t)kGenIdle << 24);
     const uint32_t off0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.off);        // (lane 0: the iteration's first read, or read 0)
     const uint8_t* const base = p.payload + ((unsigned long long)off0 << 3);
     const uint32_t l = l_nc & 0xFFFFu, nc4 = (l_nc >> 16) << 2;
     const uint32_t rel = (f.off - off0) << 3;                          // (an iteration's reads lie within a few hundred KB)
     const bool has = (uint32_t)q0 < l && !(kDebug & 128);
-    const uint32_t vc = act && !(kDebug & 128) ? rel : 0u;
-    const uint32_t vq = act && !(kDebug & 128) ? rel + nc4 : 0u;
     const uint32_t vb = has ? rel + nc4 + 4u + (uint32_t)q0 : 0u;
     const u32x4_a1 ba = *reinterpret_cast<const u32x4_a1*>(base + (size_t)vb);
     const u32x4_a1 bb = *reinterpret_cast<const u32x4_a1*>(base + (size_t)vb + 16);
-    const u32x4_a4 cv = *reinterpret_cast<const u32x4_a4*>(base + (size_t)vc);
-    const uint32_t qs = *reinterpret_cast<const uint32_t*>(base + (size_t)vq);
-    d.b[0] = ba.x; d.b[1] = ba.y; d.b[2] = ba.z; d.b[3] = ba.w;
-    d.b[4] = bb.x; d.b[5] = bb.y; d.b[6] = bb.z; d.b[7] = bb.w;
+    b[0] = ba.x; b[1] = ba.y; b[2] = ba.z; b[3] = ba.w;
+    b[4] = bb.x; b[5] = bb.y; b[6] = bb.z; b[7] = bb.w;
     if constexpr (NW > 8) {
       const u32x2_a1 bc = *reinterpret_cast<const u32x2_a1*>(base + (size_t)vb + 32);
-      d.b[8] = bc.x; d.b[9] = bc.y;
+      b[8] = bc.x; b[9] = bc.y;
     }
-    d.cg[0] = cv.x; d.cg[1] = cv.y; d.cg[2] = cv.z; d.cg[3] = cv.w;
-    d.qs = qs;
   };
+  // the record of the read this lane OWNS in the phase of `n` iterations that opens with the wave's k0-th of a stream ...
+  auto owned = [&](const Stream& s, int k0, int n, uint32_t* idx) -> bool {
+    const uint32_t v = (uint32_t)((wave + k0 * NWAVES) * rpw) + (own_slot & 0xFFFFFFu);
+    *idx = (uint32_t)s.rb + v;
+    return (int)(own_slot >> 24) < n && v < (uint32_t)s.n0;
+  };
+  auto fetch_phase = [&](const Stream& s, int k0, int n) -> Raw {
+    uint32_t idx;
+    const bool on = owned(s, k0, n, &idx);
+    const uint4 x = recs[on ? idx : 0u];
+    Raw f;
+    f.pos = x.x; f.l_nc = x.y; f.nmq = x.z; f.off = x.w;
+    return f;
+  };
+  // ... and, addressed from it, the read's first four CIGAR ops (one 16-byte load; the payload has slack behind its last read) and
+  // its quality sum (one dword)
+  struct Own { uint32_t cg[4]; uint32_t qs; };
+  auto gather = [&](const Raw& f, Own& o) {
+    const uint8_t* const rp = p.payload + ((unsigned long long)f.off << 3);
+    const u32x4_a4 cv = *reinterpret_cast<const u32x4_a4*>(rp);
+    const uint32_t qs = *reinterpret_cast<const uint32_t*>(rp + (size_t)((f.l_nc >> 16) << 2));
+    o.cg[0] = cv.x; o.cg[1] = cv.y; o.cg[2] = cv.z; o.cg[3] = cv.w;
+    o.qs = qs;
+  };
+  // What the owner hands to the lanes of a read it keeps (all zero for any other):
+  //   d0 pos    d1 l_seq | lead << 11 | kept << 22    d2 m1 | alen << 16    d3 gap | (the gap is an insertion) << 16
+  // (l_seq and the clip are at most kMaxLSeq = 1024, a deletion or skip at most kMaxFastGap: direct_common.h ReadShape)
+  struct Desc { uint32_t d0, d1, d2, d3; };
 
   Tile tile = load_tile(c_tiles, c_first);
   Stream st = load_stream(c_first, false);
-  // The pipeline of a wave, in two register sets that swap roles every iteration (the loop below is unrolled by two: a copy
-  // at its back edge would have to WAIT for the loads it copies -- the next iteration's bases, requested a moment ago):
+  // The pipeline of a wave.  Bases: two register sets that swap roles every iteration (the phase's body is unrolled: a copy at a
+  // back edge would have to WAIT for the loads it copies -- the next iteration's bases, requested a moment ago):
   //   set A / B   one holds the iteration being tallied, the other the next one's bases (in flight)
-  //   raw X       the columns of the iteration after that (in flight); its bases are requested at the top of the next body
-  // Between tiles the current iteration sits in set A.
-  Raw rawX;
-  int nrX = 0;                                  // reads of the iteration the columns belong to (wave-uniform)
-  Rd rdA, rdB;
-  Dat datA, datB;
-  auto prime = [&](const Stream& s0) {
-    const Raw r0 = fetch(s0, wave);
-    rawX = fetch(s0, wave + NWAVES);
-    nrX = reads_in(s0, wave + NWAVES);
-    settle(r0, reads_in(s0, wave), rdA, datA);
-  };
-  prime(st);
+  //   raw X       the record of the iteration after that (in flight); its bases are requested at the top of the next body
+  // Between tiles, and at the start of every phase, the current iteration sits in set A.  Per-read work:
+  //   desc        the descriptors of the phase in work, one read per lane
+  //   raw N, own N   the records (requested at the start of the phase in work) and CIGARs / quality sums (requested at the top
+  //               of its second iteration) of the NEXT phase's reads
+  Raw rawX, rawN;
+  Own ownN;
+  Desc desc;
+  int nrX = 0;                                  // reads of the iteration the record X belongs to (wave-uniform)
+  uint32_t bA[NW], bB[NW];
+  {
+    const Raw r0 = fetch(st, wave);
+    rawX = fetch(st, wave + NWAVES);
+    nrX = reads_in(st, wave + NWAVES);
+    rawN = fetch_phase(st, 0, phase_len(wave_its(st)));
+    settle(r0, reads_in(st, wave), bA);
+    gather(rawN, ownN);
+  }
   __syncthreads();   // LDS zeroed, tables in place
 
   uint32_t acc_cov = 0u;                 // (a thread's sites between two flushes: far below 2^32)
@@ -389,13 +443,217 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     const bool xt = more && n_w >= 2;
     Stream xs = st;
     if (xt) xs = load_stream(wn, cout);
-    // one wave-iteration: `it` of the tile's stream, the wave's k_it-th; tallies (rd_cur, dat_cur), requests the bases of the
-    // next iteration into (rd_n, dat_n) from the columns rawX and then the columns of the one after it into rawX
-    auto iteration = [&](int it, int k_it, Rd& rd_cur, Dat& dat_cur, Rd& rd_n, Dat& dat_n) {
+    // ---- a read walked op by op (the slow path), by the lanes that would hold its bases.  Rare: what the lanes need -- record,
+    // CIGAR, quality sum, bases -- they fetch here, by the read's index; keep_read with every test evaluated and the reference's
+    // order of outcomes, counters and error of its own.
+    // (bw: a set of base registers that is free -- at the start of a phase set B holds nothing yet)
+    auto walk = [&](bool slow, uint32_t idx, uint32_t (&bw)[NW]) {
+      const DirectRec rc = p.rec[slow ? idx : 0u];
+      const int pos = rc.pos;
+      const int l = slow ? (int)(rc.l_nc & 0xFFFFu) : 0;
+      const uint32_t nc = slow ? rc.l_nc >> 16 : 0u;
+      const uint8_t* const rp = p.payload + ((unsigned long long)rc.off8 << 3);
+      CigarView cg;
+      cg.load(reinterpret_cast<const uint32_t*>(rp));
+      uint32_t qsum = *reinterpret_cast<const uint32_t*>(rp + (size_t)(nc << 2));
+      const int nb = l - q0 < LB ? (l - q0 < 0 ? 0 : l - q0) : LB;     // bases of the read in this lane
+      const bool has = nb > 0;
+      const uint8_t* const bp = has ? rp + (size_t)(nc << 2) + 4u + (size_t)q0 : rp;
+      {
+        const u32x4_a1 ba = *reinterpret_cast<const u32x4_a1*>(bp);
+        const u32x4_a1 bb = *reinterpret_cast<const u32x4_a1*>(bp + 16);
+        bw[0] = ba.x; bw[1] = ba.y; bw[2] = ba.z; bw[3] = ba.w;
+        bw[4] = bb.x; bw[5] = bb.y; bw[6] = bb.z; bw[7] = bb.w;
+        if constexpr (NW > 8) {
+          const u32x2_a1 bc = *reinterpret_cast<const u32x2_a1*>(bp + 32);
+          bw[8] = bc.x; bw[9] = bc.y;
+        }
+      }
+      if (kDebug & 64) qsum = 0x00FFFFFFu;
+      const bool t_noqual = (qsum & kDenseQualAbsent) != 0u;
+      qsum &= ~kDenseQualAbsent;
+      const uint32_t nm16 = rc.nmq & 0xFFFFu;
+      const int nm = (int)nm16, mapq = (int)((rc.nmq >> 16) & 0xFFu);
+      const uint32_t ncs = nc;
+      // [EXT] pysam query_alignment_start / _end -> len(aln.query_alignment_sequence) (midas/run/snps.py:145)
+      long long qs = 0, qe = 0;
+      query_bounds(cg, ncs, l, &qs, &qe);
+      long long al = qe - qs;
+      al = al < 0 ? 0 : (al > 2047 ? 2047 : al);      // (l_seq <= 1024)
+      const int align_g = (int)al;
+      // the one case in which count_coverage raises IndexError for a kept read: a match op maps a query position >= l_seq
+      // onto a site inside the contig
+      bool t_over = false;
+      {
+        long long qpos = 0, rpos = pos;
+        const long long clen = tile.contig_len;
+        for_each_op(cg, ncs, [&](uint32_t, uint32_t v) {
+          const uint32_t op = v & 15u;
+          const long long len = (long long)(v >> 4);
+          if (op_is_match(op)) {
+            if (qpos + len > (long long)l) {
+              const long long qs2 = qpos > (long long)l ? qpos : (long long)l;
+              const long long rs = rpos + (qs2 - qpos), re = rpos + len;
+              if (rs < clen && re > 0) t_over = true;
+            }
+            qpos += len;
+            rpos += len;
+          } else if (op == OP_I || op == OP_S || (op == OP_P && p.pad_advances)) {
+            qpos += len;
+          } else if (op == OP_D || op == OP_N) {
+            rpos += len;
+          }
+          return true;
+        });
+      }
+      // ---- keep_read, every test evaluated, the reference's order decides which outcome wins ---------------------------
+      const int min_match = s_tables[align_g < p.table_len ? align_g : 0];
+      const int min_align = s_tables[p.table_len + (l < p.table_len ? l : 0)];
+      const bool t_noseq = l == 0;
+      const bool t_nonm = nm16 == 0xFFFFu;
+      const bool t_zero = align_g == 0;
+      const bool t_pid = align_g - nm < min_match;
+      const bool t_drop = ((int)qsum < rq * l) | (mapq < p.mapq_min) | (align_g < min_align);
+      uint32_t e = t_over ? (uint32_t)E_CIGAR_OVERRUN : 0u;
+      e = t_drop ? 0u : e;
+      e = t_noqual ? (uint32_t)E_NO_QUAL : e;
+      e = t_pid ? 0u : e;
+      e = t_zero ? (uint32_t)E_ZERO_ALIGN : e;
+      e = t_nonm ? (uint32_t)E_NO_NM : e;
+      e = t_noseq ? (uint32_t)E_NO_SEQ : e;
+      const bool keep_s = slow && !(t_noseq | t_nonm | t_zero | t_pid | t_noqual | t_drop | t_over);
+      // owner tile of a read = the tile holding its (clamped) start: it alone counts the read in the stats
+      int cpos = pos < 0 ? 0 : pos;
+      cpos = cpos > tile.contig_len - 1 ? tile.contig_len - 1 : cpos;
+      const bool owner_s = slow && cpos >= tile_start && cpos < tile_start + tile_len && !(tile.halo && pos < 0);
+      const int rel = pos - tile_start;                                     // may wrap for absurd positions:
+      int rrel = (rel > (1 << 25) || rel < -(1 << 30)) ? (1 << 25) : rel;   // those are parked far right
+      // ---- CIGAR walk ([EXT] get_aligned_pairs(matches_only=True)): one match segment at a time ------------------------
+      // 32-bit saturating positions: a query position only matters below q1 <= 1024 and a tile-relative reference
+      // position only below 4096, and both only ever grow.
+      uint32_t k = 0;
+      int qpos = 0, jlo = 0, jhi = 0, loc0 = 0;
+      const int q1 = q0 + nb;
+      auto next_segment = [&]() -> bool {
+        while (k < nc) {
+          const uint32_t v = cg[k];
+          ++k;
+          const uint32_t op = v & 15u;
+          const int len = (int)(v >> 4);
+          const bool m = consumes_both(op);
+          bool found = false;
+          if (m) {
+            const int lo = qpos > q0 ? qpos : q0;
+            const int hi = (qpos + len) < q1 ? (qpos + len) : q1;
+            found = lo < hi;
+            if (found) { jlo = lo - q0; jhi = hi - q0; loc0 = rrel + (q0 - qpos); }
+          }
+          if (m || op == OP_I || op == OP_S || (op == OP_P && p.pad_advances)) { qpos += len; qpos = qpos > (1 << 29) ? (1 << 29) : qpos; }
+          if (m || op == OP_D || op == OP_N) { rrel += len; rrel = rrel > (1 << 29) ? (1 << 29) : rrel; }
+          if (found) return true;   // H, P and anything else: no effect
+        }
+        return false;
+      };
+      bool walking = keep_s && has;
+      if (walking) walking = next_segment();
+      while (__ballot(walking) != 0ull) {
+        const int lo = jlo > -loc0 ? jlo : -loc0;
+        const int hi = jhi < ext_len - loc0 ? jhi : ext_len - loc0;
+        if (!(kDebug & 1)) tally_range(walking && lo < hi, lo, hi, loc0, bw, std::true_type{});
+        walking = (walking && k < nc) ? next_segment() : false;
+      }
+      const bool head = owner_s && c == 0;
+      w_aligned += (uint32_t)__popcll(__ballot(head));
+      w_mapped += (uint32_t)__popcll(__ballot(head && keep_s));
+      // (a read of the piece in front, midas_snps_contigs.origin: its own piece reports what keep_read raises, this one the
+      // overrun its walk runs into here)
+      const bool walk_err = slow && tile.halo && pos < 0 && c == 0 && e == (uint32_t)E_CIGAR_OVERRUN;
+      if ((head && e) || walk_err) atomicMin(p.err, ((unsigned long long)idx << 8) | e);
+    };
+
+    // ---- the start of a phase of n_ph iterations, the wave's k0-th onwards: every owner its read, from raw N / own N (requested
+    // in the phase before, or in front of the tile).  Then the records of the phase after it are requested: the next of this
+    // tile, or the first of the next tile's stream (`xs`, as the bases' look-ahead).
+    auto open_phase = [&](int k0, int n_ph) {
+      MIDAS_MARK("phase");
+      uint32_t idx;
+      const bool act = owned(st, k0, n_ph, &idx);
+      const int pos = (int)rawN.pos;
+      const int l = act ? (int)(rawN.l_nc & 0xFFFFu) : 0;
+      const uint32_t nc = act ? rawN.l_nc >> 16 : 0u;
+      // (developer timing variant, bit 512: ALL per-read work off -- no quality sum, no CIGAR shape, no filter tables: every read is
+      // one match run of its length and kept; the tallies and the stream stay)
+      // The read's quality sum travels with it (layout.h: bit 31 QUAL absent); sum(q) < readq * l_seq is np.mean(q) < readq exactly.
+      uint32_t qsum = (kDebug & (64 | 512)) ? 0x00FFFFFFu : ownN.qs;
+      const bool t_noqual = (qsum & kDenseQualAbsent) != 0u;
+      qsum &= ~kDenseQualAbsent;
+      const uint32_t nm16 = rawN.nmq & 0xFFFFu;
+      const int nm = (int)nm16, mapq = (int)((rawN.nmq >> 16) & 0xFFu);
+      // ---- the read's shape: one match op of the read's length settles most reads; anything else takes the four-op grammar
+      // (wave-uniform branch) -----------------------------------------------------------------------------------------------
+      MIDAS_MARK("shape");
+      ReadShape sh;
+      sh.lead = 0u; sh.m1 = (uint32_t)l; sh.ins = 0u; sh.del = 0u; sh.alen = (uint32_t)l;
+      bool shaped = nc == 1u && op_is_match(ownN.cg[0] & 15u) && (ownN.cg[0] >> 4) == (uint32_t)l && l >= 1;
+      if (kDebug & 512) shaped = true;
+      if (__ballot(act && !shaped) != 0ull) {
+        ReadShape s2;
+        const bool ok = decode_shape(ownN.cg[0], ownN.cg[1], ownN.cg[2], ownN.cg[3], nc, (uint32_t)l, &s2);
+        if (!shaped) { sh = s2; shaped = ok; }
+      }
+      // one or two match runs, NM present, the start inside the contig: the fast path.  Everything else is walked.
+      const bool fast = act && shaped && nm16 != 0xFFFFu && pos >= 0 && pos < tile.contig_len;
+      const bool slow = act && !fast;
+      // ---- keep_read (midas/run/snps.py:141-162): a fast read has SEQ, NM and a non-empty aligned part -------------------------
+      MIDAS_MARK("filter");
+      const int align_len = (int)sh.alen;
+      const int min_match = (kDebug & 512) ? 0 : s_tables[align_len < p.table_len ? align_len : 0];
+      const int min_align = (kDebug & 512) ? 0 : s_tables[p.table_len + (l < p.table_len ? l : 0)];
+      const bool t_pid = align_len - nm < min_match;                                                       // pid < mapid
+      const bool t_drop = ((int)qsum < rq * l) | (mapq < p.mapq_min) | (align_len < min_align);             // readq, mapq, aln_cov
+      const uint32_t err = (fast && !t_pid && t_noqual) ? (uint32_t)E_NO_QUAL : 0u;
+      const bool keep = fast && !(t_pid | t_noqual | t_drop);
+      const int rel = pos - tile_start;            // 0 <= pos < contig length: no wrap
+      const bool owner = fast && rel >= 0 && rel < tile_len;
+      const uint32_t gap = sh.ins ? sh.ins : sh.del;
+      desc.d0 = (uint32_t)pos;
+      desc.d1 = keep ? ((uint32_t)l | (sh.lead << 11) | (1u << 22)) : 0u;
+      desc.d2 = sh.m1 | (sh.alen << 16);
+      desc.d3 = gap | (sh.ins ? 1u << 16 : 0u);
+      // ---- per-species read counters: one ballot pair per phase ------------------------------------------------------------
+      MIDAS_MARK("counters");
+      w_aligned += (uint32_t)__popcll(__ballot(owner));
+      w_mapped += (uint32_t)__popcll(__ballot(owner && keep));
+      if (owner && err) atomicMin(p.err, ((unsigned long long)idx << 8) | err);
+      {                                        // the records of the phase after this one
+        const int kn = k0 + n_ph;
+        const bool over = xt && kn >= n_w;
+        Stream fs;
+        fs.rb = over ? xs.rb : st.rb; fs.n0 = over ? xs.n0 : st.n0; fs.total = over ? xs.total : st.total;
+        const int kf = over ? 0 : kn;
+        rawN = fetch_phase(fs, kf, phase_len((over ? wave_its(xs) : n_w) - kf));
+      }
+      MIDAS_MARK("slowgate");
+      const unsigned long long slow_mask = __ballot(slow);
+      if (slow_mask != 0ull) {
+        for (int j = 0; j < n_ph; ++j) {
+          const int ol = quad ? 4 * g + j : j * rpw + g;
+          const bool mine = lane_on && ((slow_mask >> (ol & 63)) & 1ull) != 0ull;
+          if (__ballot(mine) != 0ull) walk(mine, (uint32_t)(st.rb + (wave + (k0 + j) * NWAVES) * rpw + g), bB);
+        }
+      }
+      MIDAS_MARK("phaseend");
+    };
+
+    // one wave-iteration, the J-th of its phase and the wave's k_it-th of the tile: tallies the bases b_cur, requests the bases
+    // of the next iteration into b_n from the record rawX and then the record of the one after it into rawX
+    auto iteration = [&](auto jtag, int k_it, uint32_t (&b_cur)[NW], uint32_t (&b_n)[NW]) {
+      constexpr int J = decltype(jtag)::value;
       const unsigned long long pt0 = PROBE_NOW();
+      (void)pt0;
       MIDAS_MARK("settle");
-      settle(rawX, nrX, rd_n, dat_n);          // (the columns of the next iteration have arrived: its bases are requested ...)
-      {                                        // ... then the columns of the one after it
+      settle(rawX, nrX, b_n);                  // (the record of the next iteration has arrived: its bases are requested ...)
+      {                                        // ... then the record of the one after it
         const int kf = k_it + 2;               // the wave's iteration (of this tile, or counted on into the next) to fetch for
         const bool over = xt && kf >= n_w;
         Stream fs;
@@ -404,71 +662,46 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         rawX = fetch(fs, fi);
         nrX = reads_in(fs, fi);
       }
+      if constexpr (J == 1) gather(rawN, ownN);      // (the next phase's records, requested an iteration ago, have arrived)
 #if MIDAS_SNPS_DEBUG_BITS & 256
-      asm volatile("" :: "v"(rd_n.pos), "v"(rd_n.l_nc));
       const unsigned long long pt1 = PROBE_NOW();
-      asm volatile("" :: "v"(dat_cur.b[0]), "v"(dat_cur.b[NW - 1]), "v"(dat_cur.qs), "v"(dat_cur.cg[3]));
+      asm volatile("" :: "v"(b_cur[0]), "v"(b_cur[NW - 1]));
       const unsigned long long pt2 = PROBE_NOW();
       pr_cols += pt1 - pt0; pr_bases += pt2 - pt1; pr_iters += 1;
 #endif
 
       if (kDebug & 4) {          // (developer timing variant: the stream of loads only)
-        asm volatile("" :: "v"(dat_cur.b[0]), "v"(dat_cur.b[NW - 1]), "v"(dat_cur.qs), "v"(dat_cur.cg[0]), "v"(rd_cur.pos));
+        asm volatile("" :: "v"(b_cur[0]), "v"(b_cur[NW - 1]), "v"(desc.d0));
         return;
       }
-      MIDAS_MARK("qsum");
-      const int pos = (int)rd_cur.pos;
-      const int l = (int)(rd_cur.l_nc & 0xFFFFu);
-      const uint32_t nc = rd_cur.l_nc >> 16;
-      const int nb = l - q0 < LB ? (l - q0 < 0 ? 0 : l - q0) : LB;     // bases of the read in this lane
-      const bool has = nb > 0;
-      // (developer timing variant, bit 512: ALL per-read work off -- no quality sum, no CIGAR shape, no filter tables: every read is
-      // one match run of its length and kept; the tallies and the stream stay.  What a scheme that does the per-read work once
-      // per read instead of on each of its lanes could save AT MOST: profiles/r06_kernel_experiments.txt section 3)
-      // The read's quality sum travels with it (layout.h: bit 31 QUAL absent); sum(q) < readq * l_seq is np.mean(q) < readq exactly.
-      uint32_t qsum = (kDebug & (64 | 512)) ? 0x00FFFFFFu : dat_cur.qs;
-      const bool t_noqual = (qsum & kDenseQualAbsent) != 0u;
-      qsum &= ~kDenseQualAbsent;
-      const uint32_t nm16 = rd_cur.nmq & 0xFFFFu;
-      const int nm = (int)nm16, mapq = (int)((rd_cur.nmq >> 16) & 0xFFu);
-      const bool act = !((rd_cur.nmq >> 24) & kGenIdle);
-
-      // ---- the read's shape, in registers: one match op of the read's length settles most reads; anything else takes the
-      // four-op grammar (wave-uniform branch) ------------------------------------------------------------------------------
-      MIDAS_MARK("shape");
-      ReadShape sh;
-      sh.lead = 0u; sh.m1 = (uint32_t)l; sh.ins = 0u; sh.del = 0u; sh.alen = (uint32_t)l;
-      bool shaped = nc == 1u && op_is_match(dat_cur.cg[0] & 15u) && (dat_cur.cg[0] >> 4) == (uint32_t)l && l >= 1;
-      if (kDebug & 512) shaped = true;
-      if (__ballot(act && !shaped) != 0ull) {
-        ReadShape s2;
-        const bool ok = decode_shape(dat_cur.cg[0], dat_cur.cg[1], dat_cur.cg[2], dat_cur.cg[3], nc, (uint32_t)l, &s2);
-        if (!shaped) { sh = s2; shaped = ok; }
+      // ---- the read's descriptor, from its owner -----------------------------------------------------------------------------
+      MIDAS_MARK("handoff");
+      uint32_t d0, d1, d2, d3;
+      if (quad) {
+        d0 = quad_take<J>(desc.d0); d1 = quad_take<J>(desc.d1); d2 = quad_take<J>(desc.d2); d3 = quad_take<J>(desc.d3);
+      } else {
+        const int src = (J * rpw + g) << 2;
+        d0 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)desc.d0);
+        d1 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)desc.d1);
+        d2 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)desc.d2);
+        d3 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)desc.d3);
       }
-      // one or two match runs, NM present, the start inside the contig: the fast path.  Everything else is walked.
-      const bool fast = act && shaped && nm16 != 0xFFFFu && pos >= 0 && pos < tile.contig_len;
-      const bool slow = act && !fast;
-
-      // ======================= fast: one or two gap-free match runs ==========================================================
-      MIDAS_MARK("filter");
-      const int lead = (int)sh.lead, align_len = (int)sh.alen;
-      bool keep, owner;
-      uint32_t err;
+      // ======================= one or two gap-free match runs ==================================================================
+      MIDAS_MARK("clip");
+      const bool keep = lane_on && ((d1 >> 22) & 1u) != 0u;
+      const int pos = (int)d0;
+      const int l = (int)(d1 & 0x7FFu), lead = (int)((d1 >> 11) & 0x7FFu);
+      const int m1 = (int)(d2 & 0xFFFFu), align_len = (int)(d2 >> 16);
+      const int gapl = (int)(d3 & 0xFFFFu);
+      const int ins = (d3 >> 16) ? gapl : 0, del = (d3 >> 16) ? 0 : gapl;
+      const int nb = l - q0 < LB ? (l - q0 < 0 ? 0 : l - q0) : LB;     // bases of the read in this lane
       {
-        // ---- keep_read (midas/run/snps.py:141-162): such a read has SEQ, NM and a non-empty aligned part -----------------------
-        const int min_match = (kDebug & 512) ? 0 : s_tables[align_len < p.table_len ? align_len : 0];
-        const int min_align = (kDebug & 512) ? 0 : s_tables[p.table_len + (l < p.table_len ? l : 0)];
-        const bool t_pid = align_len - nm < min_match;                                                       // pid < mapid
-        const bool t_drop = ((int)qsum < rq * l) | (mapq < p.mapq_min) | (align_len < min_align);             // readq, mapq, aln_cov
-        err = (fast && !t_pid && t_noqual) ? (uint32_t)E_NO_QUAL : 0u;
-        keep = fast && !(t_pid | t_noqual | t_drop);
         const int rel = pos - tile_start;            // 0 <= pos < contig length: no wrap
-        owner = fast && rel >= 0 && rel < tile_len;
         // run A: query [lead, lead + m1) at sites pos ...; run B: query [lead + m1 + ins, lead + alen) at pos + m1 + del ...
         // -- this lane's part of each, clipped to the tile
-        const int qa1 = lead + (int)sh.m1, qb0 = qa1 + (int)sh.ins, qb1 = lead + align_len;
+        const int qa1 = lead + m1, qb0 = qa1 + ins, qb1 = lead + align_len;
         const int loc_a = rel + (q0 - lead);
-        const int loc_b = loc_a + (int)sh.del - (int)sh.ins;
+        const int loc_b = loc_a + del - ins;
         int lo_a = lead - q0, hi_a = qa1 - q0, lo_b = qb0 - q0, hi_b = qb1 - q0;
         lo_a = lo_a > -loc_a ? lo_a : -loc_a;
         lo_a = lo_a > 0 ? lo_a : 0;
@@ -484,140 +717,44 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         const bool go1 = go_a | go_b;
         MIDAS_MARK("pass1");
         if (!(kDebug & 1) && __ballot(go1) != 0ull)
-          tally_range(go1, go_a ? lo_a : lo_b, go_a ? hi_a : hi_b, go_a ? loc_a : loc_b, dat_cur.b, std::false_type{});
+          tally_range(go1, go_a ? lo_a : lo_b, go_a ? hi_a : hi_b, go_a ? loc_a : loc_b, b_cur, std::false_type{});
         const bool go2 = go_a & go_b;
         MIDAS_MARK("pass2");
-        if (!(kDebug & (1 | 16)) && __ballot(go2) != 0ull) tally_range(go2, lo_b, hi_b, loc_b, dat_cur.b, std::true_type{});
+        if (!(kDebug & (1 | 16)) && __ballot(go2) != 0ull) tally_range(go2, lo_b, hi_b, loc_b, b_cur, std::true_type{});
       }
-      // ======================= slow: walked op by op ============================================================================
-      MIDAS_MARK("slowgate");
-      if (__ballot(slow) != 0ull) {
-        const uint32_t idx = (uint32_t)(st.rb + it * rpw + g);
-        CigarView cg;
-        cg.c0 = dat_cur.cg[0]; cg.c1 = dat_cur.cg[1]; cg.c2 = dat_cur.cg[2]; cg.c3 = dat_cur.cg[3];
-        cg.p = reinterpret_cast<const uint32_t*>(p.payload);
-        if (slow && nc > 4u) cg.p = reinterpret_cast<const uint32_t*>(p.payload + ((unsigned long long)p.rec[idx].off8 << 3));   // (only a CIGAR of more than four ops is read again)
-        const uint32_t ncs = slow ? nc : 0u;
-        // [EXT] pysam query_alignment_start / _end -> len(aln.query_alignment_sequence) (midas/run/snps.py:145)
-        long long qs = 0, qe = 0;
-        query_bounds(cg, ncs, l, &qs, &qe);
-        long long al = qe - qs;
-        al = al < 0 ? 0 : (al > 2047 ? 2047 : al);      // (l_seq <= 1024)
-        const int align_g = (int)al;
-        // the one case in which count_coverage raises IndexError for a kept read: a match op maps a query position >= l_seq
-        // onto a site inside the contig
-        bool t_over = false;
-        {
-          long long qpos = 0, rpos = pos;
-          const long long clen = tile.contig_len;
-          for_each_op(cg, ncs, [&](uint32_t, uint32_t v) {
-            const uint32_t op = v & 15u;
-            const long long len = (long long)(v >> 4);
-            if (op_is_match(op)) {
-              if (qpos + len > (long long)l) {
-                const long long qs2 = qpos > (long long)l ? qpos : (long long)l;
-                const long long rs = rpos + (qs2 - qpos), re = rpos + len;
-                if (rs < clen && re > 0) t_over = true;
-              }
-              qpos += len;
-              rpos += len;
-            } else if (op == OP_I || op == OP_S || (op == OP_P && p.pad_advances)) {
-              qpos += len;
-            } else if (op == OP_D || op == OP_N) {
-              rpos += len;
-            }
-            return true;
-          });
-        }
-        // ---- keep_read, every test evaluated, the reference's order decides which outcome wins ---------------------------
-        const int min_match = s_tables[align_g < p.table_len ? align_g : 0];
-        const int min_align = s_tables[p.table_len + (l < p.table_len ? l : 0)];
-        const bool t_noseq = l == 0;
-        const bool t_nonm = nm16 == 0xFFFFu;
-        const bool t_zero = align_g == 0;
-        const bool t_pid = align_g - nm < min_match;
-        const bool t_drop = ((int)qsum < rq * l) | (mapq < p.mapq_min) | (align_g < min_align);
-        uint32_t e = t_over ? (uint32_t)E_CIGAR_OVERRUN : 0u;
-        e = t_drop ? 0u : e;
-        e = t_noqual ? (uint32_t)E_NO_QUAL : e;
-        e = t_pid ? 0u : e;
-        e = t_zero ? (uint32_t)E_ZERO_ALIGN : e;
-        e = t_nonm ? (uint32_t)E_NO_NM : e;
-        e = t_noseq ? (uint32_t)E_NO_SEQ : e;
-        const bool keep_s = slow && !(t_noseq | t_nonm | t_zero | t_pid | t_noqual | t_drop | t_over);
-        // owner tile of a read = the tile holding its (clamped) start: it alone counts the read in the stats
-        int cpos = pos < 0 ? 0 : pos;
-        cpos = cpos > tile.contig_len - 1 ? tile.contig_len - 1 : cpos;
-        const bool owner_s = slow && cpos >= tile_start && cpos < tile_start + tile_len && !(tile.halo && pos < 0);
-        if (slow) { err = e; keep = keep_s; owner = owner_s; }
-        const int rel = pos - tile_start;                                     // may wrap for absurd positions:
-        int rrel = (rel > (1 << 25) || rel < -(1 << 30)) ? (1 << 25) : rel;   // those are parked far right
-        // ---- CIGAR walk ([EXT] get_aligned_pairs(matches_only=True)): one match segment at a time ------------------------
-        // 32-bit saturating positions: a query position only matters below q1 <= 1024 and a tile-relative reference
-        // position only below 4096, and both only ever grow.
-        uint32_t k = 0;
-        int qpos = 0, jlo = 0, jhi = 0, loc0 = 0;
-        const int q1 = q0 + nb;
-        auto next_segment = [&]() -> bool {
-          while (k < nc) {
-            const uint32_t v = cg[k];
-            ++k;
-            const uint32_t op = v & 15u;
-            const int len = (int)(v >> 4);
-            const bool m = consumes_both(op);
-            bool found = false;
-            if (m) {
-              const int lo = qpos > q0 ? qpos : q0;
-              const int hi = (qpos + len) < q1 ? (qpos + len) : q1;
-              found = lo < hi;
-              if (found) { jlo = lo - q0; jhi = hi - q0; loc0 = rrel + (q0 - qpos); }
-            }
-            if (m || op == OP_I || op == OP_S || (op == OP_P && p.pad_advances)) { qpos += len; qpos = qpos > (1 << 29) ? (1 << 29) : qpos; }
-            if (m || op == OP_D || op == OP_N) { rrel += len; rrel = rrel > (1 << 29) ? (1 << 29) : rrel; }
-            if (found) return true;   // H, P and anything else: no effect
-          }
-          return false;
-        };
-        bool walking = keep_s && has;
-        if (walking) walking = next_segment();
-        while (__ballot(walking) != 0ull) {
-          const int lo = jlo > -loc0 ? jlo : -loc0;
-          const int hi = jhi < ext_len - loc0 ? jhi : ext_len - loc0;
-          if (!(kDebug & 1)) tally_range(walking && lo < hi, lo, hi, loc0, dat_cur.b, std::true_type{});
-          walking = (walking && k < nc) ? next_segment() : false;
-        }
-      }
-      // ---- per-species read counters: one ballot per wave ---------------------------------------------------------------
-      MIDAS_MARK("counters");
-      const bool head = owner && c == 0;
-      w_aligned += (uint32_t)__popcll(__ballot(head));
-      w_mapped += (uint32_t)__popcll(__ballot(head && keep));
-      // (a read of the piece in front, midas_snps_contigs.origin: its own piece reports what keep_read raises, this one the
-      // overrun its walk runs into here)
-      const bool walk_err = slow && tile.halo && pos < 0 && c == 0 && err == (uint32_t)E_CIGAR_OVERRUN;
-      if ((head && err) || walk_err) {
-        const uint32_t idx = (uint32_t)(st.rb + it * rpw + g);
-        atomicMin(p.err, ((unsigned long long)idx << 8) | err);
-      }
-
       MIDAS_MARK("iterend");
 #if MIDAS_SNPS_DEBUG_BITS & 256
       pr_work += PROBE_NOW() - pt2;
 #endif
     };
     {
-      int it = wave, k_it = 0;
-      bool odd = false;
-      while (it < it_hi) {
-        iteration(it, k_it, rdA, datA, rdB, datB);
-        it += NWAVES;
-        ++k_it;
-        if (it >= it_hi) { odd = true; break; }
-        iteration(it, k_it, rdB, datB, rdA, datA);
-        it += NWAVES;
-        ++k_it;
+      using std::integral_constant;
+      int k0 = 0;
+      while (k0 < n_w) {
+        const int n_ph = phase_len(n_w - k0);
+        open_phase(k0, n_ph);
+        iteration(integral_constant<int, 0>{}, k0, bA, bB);
+        if (n_ph > 1) {
+          iteration(integral_constant<int, 1>{}, k0 + 1, bB, bA);
+          if (n_ph > 2) {
+            iteration(integral_constant<int, 2>{}, k0 + 2, bA, bB);
+            if (n_ph > 3) iteration(integral_constant<int, 3>{}, k0 + 3, bB, bA);
+          }
+        } else {
+          gather(rawN, ownN);      // (a phase of one iteration: a tile that gives the wave one, or an odd tail of phases of two)
+          // one lane per read: a phase IS an iteration, and every one of them tallies set A (the copy waits for bases that the
+          // next phase's wait for its CIGARs, requested behind them, covers anyway)
+          if (PH == 1) {
+#pragma unroll
+            for (int w = 0; w < NW; ++w) bA[w] = bB[w];
+          }
+        }
+        k0 += n_ph;
       }
-      if (odd) { rdA = rdB; datA = datB; }      // (once per tile, not per iteration)
+      if ((n_w & 1) && PH != 1) {  // (once per tile, not per iteration)
+#pragma unroll
+        for (int w = 0; w < NW; ++w) bA[w] = bB[w];
+      }
     }
 
     // the tile's reference letters: requested here, behind the stream loop (two registers less in it), they arrive while
@@ -641,13 +778,15 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     const Stream nst = load_stream(tn, cout);
     const bool take = more && !in_chunk;          // the next tile opens the next item: draw the one after it
     const unsigned long long ps0 = PROBE_NOW();
-    if (more && !xt) {   // (with xt the pipeline already holds the next tile's first iterations)
-      // (the columns are requested in front of the barrier, the bases behind it)
+    if (more && !xt) {   // (with xt the pipeline already holds the next tile's first iterations and its first phase's reads)
+      // (the records are requested in front of the barrier, the bases and the first phase's CIGARs behind it)
       const Raw r0 = fetch(nst, wave);
       rawX = fetch(nst, wave + NWAVES);
       nrX = reads_in(nst, wave + NWAVES);
+      rawN = fetch_phase(nst, 0, phase_len(wave_its(nst)));
       lds_barrier();       // every tally of this tile is in LDS
-      settle(r0, reads_in(nst, wave), rdA, datA);
+      settle(r0, reads_in(nst, wave), bA);
+      gather(rawN, ownN);
     } else {
       lds_barrier();       // every tally of this tile is in LDS
     }
@@ -725,9 +864,11 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
       acc_depth = 0ull;
       lds_barrier();
       if (tid < MIDAS_STATS) {
-        const unsigned long long v = s_stats[tid];
-        if (v) atomicAdd(&p.stats[(size_t)tile.species * MIDAS_STATS + tid], v);
-        s_stats[tid] = 0ull;
+        int ts = tid;
+        asm volatile("" : "+v"(ts));      // (formed here: hoisted, the address of this rare add holds two registers through every tile)
+        const unsigned long long v = s_stats[ts];
+        if (v) atomicAdd(&p.stats[(size_t)tile.species * MIDAS_STATS + ts], v);
+        s_stats[ts] = 0ull;
       }
       if (!more) {
         if (dynamic && tid == 0) {   // the last workgroup to leave rewinds the counters for the next launch
