@@ -30,11 +30,6 @@ static_assert(sizeof(InflateBlock) == kInflateBlockBytes, "decode_plan.h lays ou
 
 namespace {
 
-int32_t fail(midas_snps_ctx* ctx, int32_t st, const std::string& msg) {
-  ctx->set_error(msg);
-  return st;
-}
-
 // ---- errors and traces ----------------------------------------------------------------------------------------------------------
 constexpr char kInflate[] = "device inflate", kDecode[] = "device decode", kStreamed[] = "device decode (streamed)",
                kToColumns[] = "resident BAM to columns", kGenes[] = "genes count over a BAM";
@@ -64,7 +59,6 @@ struct Lap {
   }
 };
 
-struct DeviceBuf { void* p = nullptr; ~DeviceBuf() { if (p) (void)hipFree(p); } };
 struct Loan { std::shared_ptr<midas_arena_pool> pool; void* p; ~Loan() { if (p) pool->give(p); } };      // the context's arena, given back on every way out
 
 // A region handed out piece by piece, every piece rounded up to 256 bytes; nullptr once a piece does not fit (and for every one after it)

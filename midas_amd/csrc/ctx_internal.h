@@ -4,6 +4,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstdio>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -175,13 +176,36 @@ struct midas_snps_ctx {
   void stage_join() { if (stage_thread.joinable()) stage_thread.join(); }
 };
 
-// What the context's side (snps_abi.hip) lends the other translation units that implement entry points (bam_device.hip):
-// the flags of every page-locked allocation, the copies through the pinned staging ring, and hipFree as a handle's free_fn.
+// What the context's side (ctx_runtime.hip) lends the translation units that implement entry points (batch*.hip, bam_device.hip,
+// measure.hip): the one error idiom, the flags of every page-locked allocation, the copy kernel and the copies through the pinned
+// staging ring, and hipFree as a handle's free_fn.
 namespace midas_ctx {
+#define MIDAS_INTERNAL __attribute__((visibility("hidden")))      // shared between the library's sources, not an exported symbol
+MIDAS_INTERNAL inline int32_t fail(midas_snps_ctx* ctx, int32_t st, const std::string& msg) {
+  if (ctx) ctx->set_error(msg);
+  return st;
+}
+MIDAS_INTERNAL inline int32_t hip_fail(midas_snps_ctx* ctx, hipError_t e, const char* what) {
+  char buf[512];
+  snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+  (void)hipGetLastError();
+  return fail(ctx, e == hipErrorOutOfMemory ? MIDAS_SNPS_ERR_OUT_OF_MEMORY : MIDAS_SNPS_ERR_HIP, buf);
+}
+// a HIP call that failed / a status other than OK ends the function with that status
+#define HIP_TRY(ctx, call) do { const hipError_t e__ = (call); if (e__ != hipSuccess) return midas_ctx::hip_fail(ctx, e__, #call); } while (0)
+#define ST_TRY(expr) do { const int32_t st__ = (expr); if (st__ != MIDAS_SNPS_OK) return st__; } while (0)
+struct MIDAS_INTERNAL DeviceBuf {      // device memory freed on every way out
+  void* p = nullptr;
+  ~DeviceBuf() { if (p) (void)hipFree(p); }
+};
+
 extern const unsigned int kHostAllocFlags;
+// n16 x 16 bytes from src to dst (device memory, or the device's view of page-locked host memory), streaming stores
+MIDAS_INTERNAL hipError_t launch_copy16(void* dst, const void* src, size_t n16, int grid_blocks, hipStream_t s);
 int32_t copy_to_host(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t on = nullptr);
 int32_t copy_to_device_staged(midas_snps_ctx* ctx, void* dst, const void* src, size_t bytes, hipStream_t s);
 void device_free(void* p);
+MIDAS_INTERNAL const char* read_err_name(int32_t st);      // the text of a MIDAS_SNPS_ERR_READ_* status
 
 // midas_genes_count_bam: what the entry (bam_device.hip) hands through the decode to the genes count (genes_count.hip).  The decode
 // fills `stats` and the first three laps and records ev[0..2] (inflate begins, inflate done, record offsets written); the genes

@@ -1,8 +1,9 @@
-// Launch interface between the C-ABI runtime (snps_abi.hip) and the gfx950 kernels.
+// Launch interface between the C-ABI runtime (ctx_runtime.hip, batch*.hip, bam_device.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "filter_tables.h"
 #include "layout.h"
 
 namespace midas {
@@ -51,17 +52,8 @@ struct IndexParams {
   int32_t lane_bases;                // bases per lane of the blob layout (31 or 32)
 };
 
-// keep_read's two ratio tests as exact integer thresholds, built on the host per threshold set
-// (snps_abi.hip: build_filter_tables) by evaluating the reference's own fp64 expressions:
-//   min_match[a] = least x with !(100*x/float(a) < mapid)   -> keep iff (align_len - NM) >= min_match[align_len]
-//   min_align[l] = least a with !(a/float(l) < aln_cov)     -> keep iff align_len >= min_align[l_seq]
-struct FilterTables {
-  int32_t min_match[kMaxLSeq + 1];
-  int32_t min_align[kMaxLSeq + 1];
-};
-
-// host: tabulate the two thresholds for lengths 1..max_l (snps_abi.hip)
-void build_filter_tables(double mapid, double aln_cov, int32_t max_l, FilterTables* t);
+// (FilterTables, keep_read's two ratio tests as exact integer thresholds, and the host function that builds them: filter_tables.h)
+static_assert(kFilterTableLen == kMaxLSeq + 1, "the filter tables hold an entry for every length a read can have");
 
 constexpr int kSchedGroups = 8;                      // XCDs
 constexpr int kSchedWords = 32 * (kSchedGroups + 1);
@@ -84,10 +76,6 @@ struct PileupParams {
   uint32_t* split_ticket;            // [n_tiles] arrival counter of a split tile's parts (self-resetting), then twice
                                      // kSchedWords: {8 item counters, workgroups done}, one cache line each, of the
                                      // whole-tile and of the parts launch
-  // streaming kernel (pileup_stream.hip, developer variant): workgroup b owns tiles [wg_begin[b], wg_begin[b + 1])
-  const uint32_t* wg_begin;          // [n_stream_wgs + 1]
-  const uint8_t* tile_split;         // [n_tiles] 1 = the tile is processed as parts by the phased kernel; nullptr = none is
-  int32_t n_stream_wgs;              // one per CU
   int32_t n_items;
   int32_t n_whole_items;             // items [0, n_whole_items) are whole tiles (n_parts == 1), the rest parts of split tiles
   int32_t n_tiles;
@@ -238,10 +226,6 @@ struct DirectLayoutParams {
 struct DirectParams {
   const DirectRec* rec;                           // [n_reads + 1]
   const uint8_t* payload;                         // per read [cigar][sum q][base bytes], 8-byte aligned (64 bytes of slack behind the last)
-  // (the caller's arrays: read by developer variants of the kernel only)
-  const int32_t* pos; const uint8_t* mapq; const int32_t* nm; const int32_t* l_seq;
-  const int64_t* seq_off; const int64_t* qual_off; const int64_t* cigar_off;
-  const uint8_t* seq4; const uint8_t* qual; const uint32_t* cigar;
   const uint32_t* tbegin; const uint32_t* tend;
   const uint8_t* ref;
   const Tile* tiles;
@@ -397,6 +381,5 @@ int direct_index_blocks(int64_t n_reads);
 
 hipError_t launch_index_reads(const IndexParams& p, hipStream_t stream);
 hipError_t launch_pileup_tiles(const PileupParams& p, hipStream_t stream, bool whole_tiles, bool parts);   // barrier-phased
-hipError_t launch_pileup_stream(const PileupParams& p, hipStream_t stream);   // whole tiles, barrier-free
 
 }  // namespace midas

@@ -81,12 +81,9 @@ __global__ __launch_bounds__(kBlock) void midas_calib_write16_kernel(v4u* dst, s
   for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) dst[i] = v;
 }
 
-int32_t fail(midas_snps_ctx* ctx, int32_t st, const char* msg) {
-  if (ctx) ctx->set_error(msg);
-  return st;
-}
-
 }  // namespace
+
+using midas_ctx::fail;
 
 extern "C" {
 

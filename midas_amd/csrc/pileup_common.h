@@ -1,5 +1,5 @@
 // Helpers shared by the two gfx950 pileup kernels (pileup_tiles.hip: barrier-phased workgroups, kept for the parts of split
-// hot-spot tiles; pileup_stream.hip: the barrier-free streaming kernel that processes whole tiles).
+// hot-spot tiles; attic/variants/pileup_stream.hip: the barrier-free streaming kernel, measured and not shipped).
 #pragma once
 #include "device_common.h"
 

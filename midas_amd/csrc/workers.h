@@ -1,4 +1,4 @@
-// Worker threads shared by the host-side parallel regions of the library (bgzf_host.cpp and the other host I/O sources, snps_abi.hip).
+// Worker threads shared by the host-side parallel regions of the library (bgzf_host.cpp and the other host I/O sources, ctx_runtime.hip).
 #pragma once
 #include <unistd.h>
 

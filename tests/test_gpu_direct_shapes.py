@@ -10,7 +10,7 @@ on the device (helpers.border_conditions; tests/test_direct_shapes_host.py asser
 Which kernel a case launches follows from what it asserts of info() and from its baseq: <lane_bases, baseq <= 0,
 direct_overhang>.  One class of cases launches none: the direct layout keeps a quality up to 50 (layout.h kDenseMaxQual), so a
 run with baseq 51 over a batch that holds an A/C/G/T quality above 50 -- every border batch does -- is served by the long path
-(snps_abi.hip).  Those cases hold that detour to the oracle at these shapes; their cells run once more with baseq 41, so that
+(batch.hip).  Those cases hold that detour to the oracle at these shapes; their cells run once more with baseq 41, so that
 every cell launches both of its instantiations.  Reads with a hard clip or a start in front of the contig are walked op by op, as
 the five-op reads are: all three count in direct_general_reads."""
 import functools
@@ -179,7 +179,7 @@ def test_outliers_against_the_long_overhang(hip_ctx, request, lane_bases, max_le
 def test_filter_tables_of_16_bits_and_beyond(hip_ctx, request, mapid, aln_cov, baseq):
     """The long-overhang instantiation keeps the read filter's tables as 16-bit entries: the strictest and the loosest thresholds
     that fit them, and an identity threshold whose entry for 250 bases (-50 000 matches) does not -- that run takes the common
-    instantiation tile by tile (snps_abi.hip filt_fits16), the batch still reporting its chunks."""
+    instantiation tile by tile (batch.hip filt_fits16), the batch still reporting its chunks."""
     table, soa, reads = border_batch_of(32, 250, 288)
     thr = abi.Thresholds.from_args(dict(abi.DEFAULT_ARGS, baseq=baseq, mapid=mapid, aln_cov=aln_cov, readq=0))
     oracle = c_oracle.pileup(thr, table, soa)
