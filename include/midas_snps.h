@@ -282,6 +282,22 @@ int32_t midas_snps_rows_code(midas_snps_ctx* ctx, int64_t n_sites, const uint32_
                              const int32_t* id_len, const uint8_t* ids, int64_t ids_bytes, int64_t arena_bytes, int32_t grid_blocks,
                              uint32_t* out_status, uint32_t* out_n_bytes, uint32_t* out_crc, uint32_t* out_text_len,
                              int64_t* out_arena_off, uint8_t* out_streams, int64_t out_cap, int64_t* out_stream_bytes);
+/* The library's two generic device primitives (device_sort.hip) on host arrays of the caller's choosing, through the launches
+ * every front end uses (test aids; no reference counterpart).  The arrays go up, the launch runs on the context's stream, the result
+ * comes down.  Every device buffer of a call lies between 64 guard words in front and 64 behind, written before the launch and
+ * compared afterwards; the scan's sums and the sort's scratch are exactly as many words as the library's callers allocate.
+ * *out_guards_ok: 1 when every guard word is as it was, else 0.  n == 0 is legal (nothing is written to the outputs but the flags).
+ * MIDAS_SNPS_ERR_INVALID_ARG: a null context, n < 0, bits outside 0..32, a value_kind other than 0 and 1, a missing array.
+ *
+ * midas_snps_scan_u32: out[i] = (in[0] + ... + in[i - 1]) mod 2^32.  in_place != 0: one device buffer is both the scan's input
+ * and its output; else two, and *out_in_kept says whether the input's buffer still held `in` after the launch (1 in place).   */
+int32_t midas_snps_scan_u32(midas_snps_ctx* ctx, int64_t n, const uint32_t* in, int32_t in_place, uint32_t* out, int32_t* out_guards_ok,
+                            int32_t* out_in_kept);
+/* midas_snps_sort_pairs: the stable sort of (key[i], val[i]) by the low `bits` bits of the keys (keys must lie below 2^bits; n below
+ * 2^32).  value_kind 0: val and out_val are uint32_t[n]; 1: double[n], moved as 64-bit patterns.  *out_which: the device buffer
+ * pair the launch named as the result -- 0 the pair the input was uploaded to, 1 the other one.                             */
+int32_t midas_snps_sort_pairs(midas_snps_ctx* ctx, int64_t n, int32_t bits, int32_t value_kind, const uint32_t* key, const void* val,
+                              uint32_t* out_key, void* out_val, int32_t* out_which, int32_t* out_guards_ok);
 /* Re-run the device packer over the batch's resident BAM-native arrays (the arrays batch_create uploaded, unchanged):
  * per read the CIGAR walk into gap-free match segments (pysam get_aligned_pairs(matches_only=True), reached from
  * midas/run/snps.py:194-199), the clip structure (query_alignment_sequence, :145), floor(mean(query_qualities))

@@ -267,6 +267,8 @@ def load_library(build_if_missing: bool = True):
         'midas_snps_set_row_coder': (i32, [vp, i32]),
         'midas_snps_row_coder_counts': (i32, [vp, vp]),
         'midas_snps_rows_code': (i32, [vp, i64, vp, vp, i32] + [vp] * 6 + [i64, i64, i32] + [vp] * 6 + [i64, C.POINTER(i64)]),
+        'midas_snps_scan_u32': (i32, [vp, i64, vp, i32, vp, C.POINTER(i32), C.POINTER(i32)]),
+        'midas_snps_sort_pairs': (i32, [vp, i64, i32, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]),
         'midas_snps_copy_rate': (i32, [vp, i64, i32, C.POINTER(C.c_double)]),
         'midas_snps_batch_fetch_packed': (i32, [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]),
         'midas_snps_batch_pack_timing': (i32, [vp, i32, C.POINTER(C.c_float)]),
@@ -405,7 +407,7 @@ EXPORTED_SYMBOLS = [
     'midas_snps_batch_enable_timing', 'midas_snps_batch_timing', 'midas_snps_batch_time_pileup_only',
     'midas_snps_batch_stats_to_device', 'midas_snps_batch_pack', 'midas_snps_batch_fetch_packed',
     'midas_snps_batch_select_path', 'midas_snps_set_default_path', 'midas_snps_copy_rate', 'midas_snps_stream_rates', 'midas_snps_calibration_pass', 'midas_snps_set_pad_rule', 'midas_snps_set_row_coder',
-    'midas_snps_row_coder_counts', 'midas_snps_rows_code',
+    'midas_snps_row_coder_counts', 'midas_snps_rows_code', 'midas_snps_scan_u32', 'midas_snps_sort_pairs',
     'midas_snps_batch_pack_timing',
     'midas_bam_open', 'midas_bam_close', 'midas_bam_write', 'midas_bam_n_refs', 'midas_bam_ref', 'midas_bam_load', 'midas_bam_copy', 'midas_bam_columns',
     'midas_bam_open_slice', 'midas_bam_slice_facts', 'midas_bam_slice_marks', 'midas_bam_load_ranges',
@@ -1497,6 +1499,34 @@ class Context:
             out.append(dict(status=int(st_[k]), n_bytes=int(nb[k]), crc=int(crc[k]), text_len=int(tl[k]), arena_off=int(off[k]), stream=stream))
         assert at == got.value
         return out
+
+    def scan_u32(self, v, in_place: bool = False, n=None):
+        """The library's exclusive scan of 32-bit counters on v, between guard words (midas_snps_scan_u32; test aid).
+        in_place: one device buffer is input and output.  n: the count handed over, len(v) unless given.
+        -> (out uint32 [n], guards_ok, in_kept)."""
+        v = np.ascontiguousarray(v, np.uint32).reshape(-1)
+        out = np.zeros(v.size, np.uint32)
+        ok, kept = C.c_int32(-1), C.c_int32(-1)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.midas_snps_scan_u32(self._h, v.size if n is None else int(n), p(v), int(bool(in_place)), p(out),
+                                                  C.byref(ok), C.byref(kept)))
+        return out, ok.value == 1, kept.value == 1
+
+    def sort_pairs(self, key, val, bits: int, n=None):
+        """The library's stable radix sort of (key, val) pairs by the keys' low `bits` bits, between guard words
+        (midas_snps_sort_pairs; test aid).  key uint32 [n] below 2^bits; val uint32 [n] or float64 [n] (moved as bit patterns).
+        n: the count handed over, len(key) unless given.
+        -> (keys, values, which, guards_ok); which: 0 the result lay in the buffer pair the input went up to, 1 in the other."""
+        key = np.ascontiguousarray(key, np.uint32).reshape(-1)
+        val = np.ascontiguousarray(val).reshape(-1)
+        if val.dtype not in (np.uint32, np.float64) or val.size != key.size:
+            raise ValueError("sort_pairs: val must be uint32 or float64 and as long as key")
+        out_key, out_val = np.zeros(key.size, np.uint32), np.zeros(val.size, val.dtype)
+        which, ok = C.c_int32(-1), C.c_int32(-1)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.midas_snps_sort_pairs(self._h, key.size if n is None else int(n), int(bits), int(val.dtype == np.float64),
+                                                    p(key), p(val), p(out_key), p(out_val), C.byref(which), C.byref(ok)))
+        return out_key, out_val, which.value, ok.value == 1
 
     def copy_rate(self, nbytes: int = 1 << 30, reps: int = 10) -> float:
         """GB/s (read + written) of a device-to-device copy with the library's 16-bytes-per-lane copy kernel."""

@@ -3,11 +3,16 @@
 //   * a STABLE least-significant-digit radix sort of (32-bit key, value) pairs, eight bits of the key a pass, for keys whose
 //     range is known (a gene index, a tile bin): as many passes as the range has bytes.  Input order survives inside a key --
 //     what the callers are after (genes_count.hip: BAM order inside a gene; pack_reads.hip: read order inside a tile bin).
+// At the end: midas_snps_scan_u32 and midas_snps_sort_pairs, the two launches on host arrays (tests/test_gpu_sort.py).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <vector>
 
+#include "ctx_internal.h"
 #include "kernels.h"
 
 namespace midas {
@@ -212,3 +217,130 @@ hipError_t launch_sort_pairs_f64(uint32_t* key_a, double* val_a, uint32_t* key_b
 }
 
 }  // namespace midas
+
+// ---- test aids: the two primitives on host arrays, every device buffer between guard words ------------------------------------
+namespace {
+using midas_ctx::fail;
+
+constexpr size_t kGuardWords = 64, kGuardBytes = kGuardWords * 4;
+constexpr uint32_t kGuardWord = 0x5AC3A53Cu;
+
+struct GuardPattern {
+  uint32_t w[kGuardWords];
+  GuardPattern() { std::fill(w, w + kGuardWords, kGuardWord); }
+};
+const GuardPattern kGuards;
+
+// `bytes` of device memory (a multiple of 4) with kGuardWords words of kGuardWord right in front of it and right behind it.  What
+// lies between starts out as 0xEE bytes: a word the launch fails to write must not look right because an earlier call's result
+// lay in the same memory.
+struct Guarded {
+  midas_ctx::DeviceBuf buf;
+  size_t bytes = 0;
+  uint8_t* base() const { return static_cast<uint8_t*>(buf.p); }
+  template <class T> T* data() const { return reinterpret_cast<T*>(base() + kGuardBytes); }
+  hipError_t make(size_t n_bytes, hipStream_t s) {
+    bytes = n_bytes;
+    hipError_t e = hipMalloc(&buf.p, bytes + 2 * kGuardBytes);
+    if (e == hipSuccess) e = hipMemsetAsync(buf.p, 0xEE, bytes + 2 * kGuardBytes, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(base(), kGuards.w, kGuardBytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(base() + kGuardBytes + bytes, kGuards.w, kGuardBytes, hipMemcpyHostToDevice, s);
+    return e;
+  }
+  hipError_t put(const void* host, hipStream_t s) const {
+    return bytes ? hipMemcpyAsync(base() + kGuardBytes, host, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+  }
+  // both guards down; *ok goes to false when a word of them differs (the stream is waited for)
+  hipError_t check(hipStream_t s, bool* ok) const {
+    uint32_t got[2 * kGuardWords];
+    hipError_t e = hipMemcpyAsync(got, base(), kGuardBytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(got + kGuardWords, base() + kGuardBytes + bytes, kGuardBytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return e;
+    for (size_t k = 0; k < 2 * kGuardWords; ++k)
+      if (got[k] != kGuardWord) *ok = false;
+    return hipSuccess;
+  }
+};
+
+template <class V>
+int32_t sort_pairs_guarded(midas_snps_ctx* ctx, int64_t n, int32_t bits, const uint32_t* key, const V* val, uint32_t* out_key, V* out_val,
+                           int32_t* out_which, int32_t* out_guards_ok,
+                           hipError_t (*launch)(uint32_t*, V*, uint32_t*, V*, long long, int, uint32_t*, hipStream_t, uint32_t**, V**)) {
+  std::lock_guard<std::mutex> g(ctx->device_mutex);
+  hipStream_t s = ctx->stream;
+  Guarded key_a, key_b, val_a, val_b, scratch;
+  HIP_TRY(ctx, key_a.make((size_t)n * 4, s));
+  HIP_TRY(ctx, key_b.make((size_t)n * 4, s));
+  HIP_TRY(ctx, val_a.make((size_t)n * sizeof(V), s));
+  HIP_TRY(ctx, val_b.make((size_t)n * sizeof(V), s));
+  HIP_TRY(ctx, scratch.make(midas::sort_scratch_words(n) * 4, s));
+  HIP_TRY(ctx, key_a.put(key, s));
+  HIP_TRY(ctx, val_a.put(val, s));
+  uint32_t* key_sorted = nullptr;
+  V* val_sorted = nullptr;
+  HIP_TRY(ctx, launch(key_a.data<uint32_t>(), val_a.data<V>(), key_b.data<uint32_t>(), val_b.data<V>(), n, bits, scratch.data<uint32_t>(), s,
+                      &key_sorted, &val_sorted));
+  const bool in_a = key_sorted == key_a.data<uint32_t>() && val_sorted == val_a.data<V>();
+  const bool in_b = key_sorted == key_b.data<uint32_t>() && val_sorted == val_b.data<V>();
+  if (!in_a && !in_b) {
+    (void)hipStreamSynchronize(s);
+    return fail(ctx, MIDAS_SNPS_ERR_HIP, "sort_pairs: the launch named a result that is neither of the two buffer pairs");
+  }
+  if (n > 0) {
+    HIP_TRY(ctx, hipMemcpyAsync(out_key, key_sorted, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipMemcpyAsync(out_val, val_sorted, (size_t)n * sizeof(V), hipMemcpyDeviceToHost, s));
+  }
+  bool ok = true;
+  for (const Guarded* b : {&key_a, &key_b, &val_a, &val_b, &scratch}) HIP_TRY(ctx, b->check(s, &ok));
+  *out_which = in_b ? 1 : 0;
+  *out_guards_ok = ok ? 1 : 0;
+  return MIDAS_SNPS_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t midas_snps_scan_u32(midas_snps_ctx* ctx, int64_t n, const uint32_t* in, int32_t in_place, uint32_t* out, int32_t* out_guards_ok,
+                            int32_t* out_in_kept) {
+  if (!ctx || n < 0 || (n > 0 && (!in || !out)) || !out_guards_ok || !out_in_kept) return MIDAS_SNPS_ERR_INVALID_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::lock_guard<std::mutex> g(ctx->device_mutex);
+  hipStream_t s = ctx->stream;
+  Guarded d_in, d_out, sums;
+  HIP_TRY(ctx, d_in.make((size_t)n * 4, s));
+  if (!in_place) HIP_TRY(ctx, d_out.make((size_t)n * 4, s));
+  HIP_TRY(ctx, sums.make(midas::scan_scratch_words(n) * 4, s));
+  HIP_TRY(ctx, d_in.put(in, s));
+  uint32_t* const to = in_place ? d_in.data<uint32_t>() : d_out.data<uint32_t>();
+  HIP_TRY(ctx, midas::launch_scan_u32(d_in.data<uint32_t>(), to, n, sums.data<uint32_t>(), s));
+  if (n > 0) HIP_TRY(ctx, hipMemcpyAsync(out, to, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  bool ok = true, kept = true;
+  HIP_TRY(ctx, d_in.check(s, &ok));
+  if (!in_place) HIP_TRY(ctx, d_out.check(s, &ok));
+  HIP_TRY(ctx, sums.check(s, &ok));
+  if (!in_place && n > 0) {
+    std::vector<uint32_t> back((size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(back.data(), d_in.data<uint32_t>(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    kept = memcmp(back.data(), in, (size_t)n * 4) == 0;
+  }
+  *out_guards_ok = ok ? 1 : 0;
+  *out_in_kept = kept ? 1 : 0;
+  return MIDAS_SNPS_OK;
+}
+
+int32_t midas_snps_sort_pairs(midas_snps_ctx* ctx, int64_t n, int32_t bits, int32_t value_kind, const uint32_t* key, const void* val,
+                              uint32_t* out_key, void* out_val, int32_t* out_which, int32_t* out_guards_ok) {
+  if (!ctx || n < 0 || n > 0xFFFFFFFFll || bits < 0 || bits > 32 || (value_kind != 0 && value_kind != 1) ||
+      (n > 0 && (!key || !val || !out_key || !out_val)) || !out_which || !out_guards_ok)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (value_kind == 0)
+    return sort_pairs_guarded<uint32_t>(ctx, n, bits, key, static_cast<const uint32_t*>(val), out_key, static_cast<uint32_t*>(out_val), out_which,
+                                        out_guards_ok, midas::launch_sort_pairs_u32);
+  return sort_pairs_guarded<double>(ctx, n, bits, key, static_cast<const double*>(val), out_key, static_cast<double*>(out_val), out_which,
+                                    out_guards_ok, midas::launch_sort_pairs_f64);
+}
+
+}  // extern "C"

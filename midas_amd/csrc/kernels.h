@@ -245,6 +245,7 @@ struct DirectParams {
 
 // device_sort.hip: the library's own exclusive scan of 32-bit counters and stable 8-bit-digit radix sort of (key, value) pairs
 size_t scan_scratch_words(long long n);                 // 32-bit words of `sums` a scan of n counters needs
+// out[i] = sum of in[0, i) modulo 2^32 (the counters wrap, by construction); in == out is allowed at every size
 hipError_t launch_scan_u32(const uint32_t* in, uint32_t* out, long long n, uint32_t* sums, hipStream_t s);     // in == out allowed
 size_t sort_scratch_words(long long n);                 // 32-bit words of `scratch` a sort of n pairs needs
 // keys below 2^bits; the sorted pairs end up in (*key_sorted, *val_sorted) = one of the two buffer pairs
