@@ -610,6 +610,41 @@ int32_t midas_snps_tableset_read_counts(midas_snps_tableset* ts, int64_t row_beg
                                         uint32_t* const* out_counts, char* err256);
 void midas_snps_tableset_close(midas_snps_tableset* ts);
 
+/* The samples' count tables of one merge, RESIDENT on the device: n_samples x n_rows x 4 u32 (A, C, G, T), the layout the merge
+ * kernels read.  _set_host uploads the first n_rows rows of one sample's table from a host array (a table the host read), _fetch
+ * brings them down again (tests and tools), _shape says what the set was created with.  _free(NULL) is allowed.             */
+typedef struct midas_merge_tables midas_merge_tables;
+int32_t midas_merge_tables_create(midas_snps_ctx* ctx, int32_t n_samples, int64_t n_rows, midas_merge_tables** out);
+void midas_merge_tables_free(midas_merge_tables* tables);
+int32_t midas_merge_tables_shape(const midas_merge_tables* tables, int32_t* n_samples, int64_t* n_rows);
+int32_t midas_merge_tables_set_host(midas_snps_ctx* ctx, midas_merge_tables* tables, int32_t sample, int64_t n_rows, const uint32_t* counts);
+int32_t midas_merge_tables_fetch(midas_snps_ctx* ctx, const midas_merge_tables* tables, int32_t sample, int64_t n_rows, uint32_t* out);
+
+/* midas_snps_tableset_read_counts on the device: for EVERY table t of the open set, rows [row_begin, row_begin + n_rows) -- n_rows
+ * clipped to what the shortest table holds behind row_begin, as the host's zip over the files is -- end up in sample slot
+ * first_sample_slot + t of `tables`, rows 0 ... .  The gzip members that hold those rows go up compressed, are inflated there
+ * (every member's bytes checked against the CRC-32 and ISIZE of its trailer) and parsed there; nothing per row comes down.
+ * Rows and values are accepted exactly as the host readers accept them (a row of more than 16 tabs included: fields 13-16, the
+ * last one running to the end of the line).  Works in groups of members whose inflated text stays below a cap taken from the free
+ * device memory (MIDAS_SNPS_MERGE_READ_KB overrides it; a member larger than the cap is a group by itself); a group's bytes go up
+ * while the group before is in the kernels.  The result does not depend on the cap.
+ * out_stats8 (nullable): tables, members read, groups, compressed bytes sent, inflated bytes, rows per table, groups with streams
+ * decoded twice, 0.  out_ms4 (nullable): upload, inflate + CRC, line index, row parser (HIP events, summed over the groups).
+ * A range that begins behind the shortest table's end is MIDAS_SNPS_ERR_INVALID_ARG, in midas_snps_tableset_read_counts' words.
+ * MIDAS_SNPS_ERR_UNSUPPORTED: a file does not announce its rows (written by the reference): take midas_snps_tableset_read_counts /
+ * midas_snps_table_open.  MIDAS_SNPS_ERR_BAD_LAYOUT, err256 naming the file: corrupt deflate data, a CRC-32 mismatch, a member that
+ * holds another number of rows than it announces, or a malformed row (the lowest one of the table, as "malformed row N").
+ * On any error nothing stays allocated; what `tables` holds in the slots is undefined then.                                  */
+int32_t midas_snps_tableset_read_counts_device(midas_snps_ctx* ctx, midas_snps_tableset* ts, int64_t row_begin, int64_t n_rows,
+                                               int32_t first_sample_slot, midas_merge_tables* tables, int64_t* out_stats8, float* out_ms4,
+                                               char* err256);
+
+/* The device's row parser on text of the caller's (tests: chosen rows reach the kernel without going through a file): the text
+ * of ONE table of n_bytes (< 2^31), skip_header != 0: its first line is the header line.  *out_rows = rows found, the counts of
+ * the first cap_rows of them in out_counts[4 * cap_rows]; *out_bad_row = the lowest malformed row among those (0-based), or -1.   */
+int32_t midas_snps_parse_rows_device(midas_snps_ctx* ctx, const uint8_t* text, int64_t n_bytes, int32_t skip_header, uint32_t* out_counts,
+                                     int64_t cap_rows, int64_t* out_rows, int64_t* out_bad_row);
+
 /* The same rows as midas_snps_write_part, taken from a batch's results WHERE THEY ARE -- on the device -- for the
  * contigs contig_index[k] (indices into the batch's contig table, in output order) under the names ref_ids[k]: the
  * emit loop of species_pileup (midas/run/snps.py:183-213) without a host copy of the counts.  The formatter's
@@ -707,6 +742,17 @@ int32_t midas_merge_sites_tables(midas_snps_ctx* ctx, const midas_merge_params* 
                                  const char* depth_path, const char* header_line, int64_t site_id_base, uint8_t* out_calls,
                                  uint32_t* out_count_samples, uint64_t* out_pooled, int64_t* out_n_keep, float* out_kernel_ms,
                                  float* out_format_ms);
+
+/* The two calls above over a resident set (midas_merge_tables_*) in place of sample_counts: the samples are the set's, the sites
+ * its first n_sites rows (n_sites <= the set's rows).  Everything else as above.  The host-array calls are these two behind a set
+ * made from the arrays: the counts of all sites lie on the device at once, the per-site results are chunked as before.        */
+int32_t midas_merge_sites_resident(midas_snps_ctx* ctx, const midas_merge_params* params, const midas_merge_tables* tables, int64_t n_sites,
+                                   const double* mean_depth, uint8_t* out_calls, uint32_t* out_count_samples, uint64_t* out_pooled,
+                                   uint32_t* out_depth, uint32_t* out_minor_count, float* out_kernel_ms);
+int32_t midas_merge_sites_tables_resident(midas_snps_ctx* ctx, const midas_merge_params* params, const midas_merge_tables* tables, int64_t n_sites,
+                                          const double* mean_depth, const char* freq_path, const char* depth_path, const char* header_line,
+                                          int64_t site_id_base, uint8_t* out_calls, uint32_t* out_count_samples, uint64_t* out_pooled,
+                                          int64_t* out_n_keep, float* out_kernel_ms, float* out_format_ms);
 
 /* snps_info.txt of merge_midas.py snps: GenomicSite.annotate + fetch_ref_codon + the info line of GenomicSite.write
  * (midas/merge/snps.py:116-195) with utility.translate / index_replace (midas/utility.py:306-332) for the kept sites.

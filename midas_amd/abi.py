@@ -324,6 +324,16 @@ def load_library(build_if_missing: bool = True):
         'midas_snps_tableset_open': (i32, [i32, vp, C.POINTER(vp), vp, C.c_char_p]),
         'midas_snps_tableset_read_counts': (i32, [vp, i64, i64, vp, C.c_char_p]),
         'midas_snps_tableset_close': (None, [vp]),
+        'midas_merge_tables_create': (i32, [vp, i32, i64, C.POINTER(vp)]),
+        'midas_merge_tables_free': (None, [vp]),
+        'midas_merge_tables_shape': (i32, [vp, C.POINTER(i32), C.POINTER(i64)]),
+        'midas_merge_tables_set_host': (i32, [vp, vp, i32, i64, vp]),
+        'midas_merge_tables_fetch': (i32, [vp, vp, i32, i64, vp]),
+        'midas_snps_tableset_read_counts_device': (i32, [vp, vp, i64, i64, i32, vp, vp, vp, C.c_char_p]),
+        'midas_snps_parse_rows_device': (i32, [vp, vp, i64, i32, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
+        'midas_merge_sites_resident': (i32, [vp, C.POINTER(MergeParams), vp, i64, vp] + [vp] * 5 + [C.POINTER(C.c_float)]),
+        'midas_merge_sites_tables_resident': (i32, [vp, C.POINTER(MergeParams), vp, i64, vp, C.c_char_p, C.c_char_p, C.c_char_p, i64,
+                                                    vp, vp, vp, C.POINTER(i64), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         'midas_snps_table_open': (i32, [C.c_char_p, i64, i32, C.POINTER(vp), C.c_char_p]),
         'midas_snps_table_close': (None, [vp]),
         'midas_snps_table_rows': (i64, [vp]),
@@ -422,6 +432,8 @@ EXPORTED_SYMBOLS = [
     'midas_snps_table_copy', 'midas_merge_sites', 'midas_genes_count', 'midas_genes_terms', 'midas_genes_sum', 'midas_merge_write_info',
     'midas_genes_count_device', 'midas_genes_count_timing', 'midas_genes_count_bam',
     'midas_merge_write_matrix', 'midas_merge_write_matrix_device', 'midas_merge_sites_tables',
+    'midas_merge_tables_create', 'midas_merge_tables_free', 'midas_merge_tables_shape', 'midas_merge_tables_set_host', 'midas_merge_tables_fetch',
+    'midas_snps_tableset_read_counts_device', 'midas_snps_parse_rows_device', 'midas_merge_sites_resident', 'midas_merge_sites_tables_resident',
     'midas_bam_open_share',
     'midas_comm_device_key', 'midas_comm_probe', 'midas_comm_unique_id', 'midas_comm_create', 'midas_comm_destroy', 'midas_comm_all_gather', 'midas_comm_all_to_all_v',
     'midas_genes_merge_map_open', 'midas_genes_merge_map_n_clusters', 'midas_genes_merge_map_n_genes', 'midas_genes_merge_map_columns',
@@ -749,6 +761,49 @@ def read_bam(path: str, ctx=None, payload_on_device: bool = False, resident: boo
         raise MidasSnpsError(st, err.value.decode())
     refid, reads = _bam_columns(lib, h, int(n.value), int(sb.value), int(qb.value), int(nc.value), owner)
     return names, lens, refid, reads
+
+
+TABLES_READ_PHASES = ('upload', 'inflate + crc', 'index', 'parse')
+TABLES_READ_STATS = ('tables', 'members', 'groups', 'compressed_bytes', 'inflated_bytes', 'rows', 'groups_decoded_twice')
+
+
+class MergeTables:
+    """The samples' count tables of one merge, resident on the device (midas_merge_tables_*): n_samples x n_rows x 4 u32.  Owns
+    the set and frees it (close, `with`, or when collected).  n_sites: the rows a merge takes (<= n_rows; the caller lowers it
+    when a table it read by itself turned out shorter).  stats / ms: what the device readers reported (read_snps_counts_device)."""
+
+    def __init__(self, ctx: "Context", n_samples: int, n_rows: int):
+        self._ctx, self._lib = ctx, ctx._lib
+        h = C.c_void_p()
+        ctx._check(self._lib.midas_merge_tables_create(ctx._h, int(n_samples), int(n_rows), C.byref(h)))
+        self._h = h
+        self.n_samples, self.n_rows, self.n_sites = int(n_samples), int(n_rows), int(n_rows)
+        self.stats, self.ms = {}, {}
+
+    def set_host(self, sample: int, counts):
+        """The first len(counts) rows of sample `sample` from a host array [n, 4] u32."""
+        a = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert a.ndim == 2 and a.shape[1] == 4 and a.shape[0] <= self.n_rows
+        self._ctx._check(self._lib.midas_merge_tables_set_host(self._ctx._h, self._h, int(sample), a.shape[0], a.ctypes.data_as(C.c_void_p)))
+
+    def fetch(self, sample: int, n_rows: int = None):
+        n = self.n_sites if n_rows is None else int(n_rows)
+        out = np.empty((n, 4), np.uint32)
+        self._ctx._check(self._lib.midas_merge_tables_fetch(self._ctx._h, self._h, int(sample), n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def close(self):
+        if getattr(self, '_h', None):
+            self._lib.midas_merge_tables_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 class BamDeviceHandle:
@@ -1656,9 +1711,74 @@ class Context:
         self._check(st)
         return aligned, mapped, depth
 
+    def parse_rows(self, text: bytes, skip_header: bool = True, cap_rows: int = None):
+        """The device's row parser on the text of one table (midas_snps_parse_rows_device) -> (counts[n,4] u32 of the first cap_rows
+        rows, rows found, first malformed row among them or -1)."""
+        buf = np.frombuffer(text, np.uint8)
+        cap = int(cap_rows) if cap_rows is not None else text.count(b"\n") + 1
+        out = np.zeros((cap, 4), np.uint32)
+        rows, bad = C.c_int64(0), C.c_int64(-1)
+        self._check(self._lib.midas_snps_parse_rows_device(self._h, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, 1 if skip_header else 0,
+                                                           out.ctypes.data_as(C.c_void_p), cap, C.byref(rows), C.byref(bad)))
+        return out[:min(cap, int(rows.value))], int(rows.value), int(bad.value)
+
+    def read_snps_counts_device(self, paths, row_begin: int = 0, max_rows: int = -1, first_slot: int = 0, extra_slots: int = 0):
+        """The count columns of several samples' <species>.snps.gz inflated and parsed on the device
+        (midas_snps_tableset_read_counts_device) -> MergeTables: table k of `paths` in sample slot first_slot + k, rows
+        [row_begin, max_rows) of the SHORTEST table (max_rows < 0: its end), as read_snps_counts.  first_slot / extra_slots: slots in
+        front of / behind the tables' for samples the caller fills (MergeTables.set_host).  Raises MidasSnpsError: ERR_UNSUPPORTED
+        when a file does not announce its rows, ERR_BAD_LAYOUT (naming the file) when one is corrupt; nothing stays allocated."""
+        lib = self._lib
+        n = len(paths)
+        arr = (C.c_char_p * n)(*[p.encode() for p in paths])
+        rows = np.empty(n, np.int64)
+        h = C.c_void_p()
+        err = C.create_string_buffer(256)
+        st = lib.midas_snps_tableset_open(n, arr, C.byref(h), rows.ctypes.data_as(C.c_void_p), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode())
+        try:
+            if (rows < 0).any():
+                raise MidasSnpsError(ERR_UNSUPPORTED, "%s: the file does not announce its rows" % paths[int(np.nonzero(rows < 0)[0][0])])
+            hi = int(rows.min()) if max_rows < 0 else min(int(rows.min()), int(max_rows))
+            m = max(0, hi - int(row_begin))
+            tables = MergeTables(self, int(first_slot) + n + int(extra_slots), m)
+            stats, ms = np.zeros(8, np.int64), np.zeros(4, np.float32)
+            st = lib.midas_snps_tableset_read_counts_device(self._h, h, int(row_begin), m, int(first_slot), tables._h, stats.ctypes.data_as(C.c_void_p),
+                                                            ms.ctypes.data_as(C.c_void_p), err)
+            if st != 0:
+                tables.close()
+                raise MidasSnpsError(st, err.value.decode())
+            tables.stats = dict(zip(TABLES_READ_STATS, (int(x) for x in stats)))
+            tables.ms = dict(zip(TABLES_READ_PHASES, (float(x) for x in ms)))
+            return tables
+        finally:
+            lib.midas_snps_tableset_close(h)
+
+    def _merge_resident(self, prm, tables: "MergeTables", mean_depth, with_matrices: bool):
+        n, S = tables.n_sites, tables.n_samples
+        md = np.ascontiguousarray(mean_depth, dtype=np.float64)
+        assert md.shape == (S,)
+        calls = np.empty((n, 4), np.uint8)
+        out = dict(major=calls[:, 0], minor=calls[:, 1], snp_type=calls[:, 2], flag=calls[:, 3],
+                   count_samples=np.empty(n, np.uint32), pooled=np.empty((n, 4), np.uint64))
+        if with_matrices:
+            out.update(depth=np.empty((S, n), np.uint32), minor_count=np.empty((S, n), np.uint32))
+        return n, md, calls, out
+
     def merge_sites(self, prm: "MergeParams", sample_counts, mean_depth):
-        """midas_merge_sites(): sample_counts = list of [n_sites,4] uint32 arrays (one per sample).
+        """midas_merge_sites(): sample_counts = list of [n_sites,4] uint32 arrays (one per sample), or a MergeTables (the counts
+        where the device readers left them: midas_merge_sites_resident).
         -> dict(major, minor, snp_type, flag, count_samples, pooled[n,4] u64, depth[S,n] u32, minor_count[S,n] u32, kernel_ms)"""
+        if isinstance(sample_counts, MergeTables):
+            n, md, calls, out = self._merge_resident(prm, sample_counts, mean_depth, True)
+            ms = C.c_float(0)
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            st = self._lib.midas_merge_sites_resident(self._h, C.byref(prm), sample_counts._h, n, p(md), p(calls), p(out['count_samples']), p(out['pooled']),
+                                                      p(out['depth']), p(out['minor_count']), C.byref(ms))
+            self._check(st)
+            out['kernel_ms'] = float(ms.value)
+            return out
         S = len(sample_counts)
         arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in sample_counts]
         n = arrs[0].shape[0]
@@ -1682,7 +1802,17 @@ class Context:
                            site_id_base: int = 0):
         """midas_merge_sites_tables(): merge_sites with snps_freq.txt / snps_depth.txt written from the device -- depth and
         minor_count stay there.  -> dict(major, minor, snp_type, flag, count_samples, pooled[n,4] u64, n_keep, kernel_ms,
-        format_ms)"""
+        format_ms).  sample_counts: the list of arrays, or a MergeTables (midas_merge_sites_tables_resident)."""
+        if isinstance(sample_counts, MergeTables):
+            n, md, calls, out = self._merge_resident(prm, sample_counts, mean_depth, False)
+            ms, fms, kept = C.c_float(0), C.c_float(0), C.c_int64(0)
+            p = lambda a: a.ctypes.data_as(C.c_void_p)
+            st = self._lib.midas_merge_sites_tables_resident(self._h, C.byref(prm), sample_counts._h, n, p(md), freq_path.encode(), depth_path.encode(),
+                                                             header_line.encode(), int(site_id_base), p(calls), p(out['count_samples']),
+                                                             p(out['pooled']), C.byref(kept), C.byref(ms), C.byref(fms))
+            self._check(st)
+            out['n_keep'], out['kernel_ms'], out['format_ms'] = int(kept.value), float(ms.value), float(fms.value)
+            return out
         S = len(sample_counts)
         arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in sample_counts]
         n = arrs[0].shape[0]

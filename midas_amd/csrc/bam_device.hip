@@ -96,9 +96,11 @@ InflateParams inflate_params(const InflateLayout& L, uint8_t* base, size_t n) {
   return ip;
 }
 
+}  // namespace
+
 // The streams whose matches did not fit their room (status kInflateMatchRoom): again, with the bound's room, into the same output;
-// their statuses replace the first pass's.  want: the streams' CRC-32 (nullptr: not checked).
-int32_t inflate_again(const char* who, const InflateParams& ip, const InflateBlock* blocks, const uint32_t* want, std::vector<uint32_t>& status, hipStream_t s,
+// their statuses replace the first pass's.  want: the streams' CRC-32 (nullptr: not checked).  (Shared with tables_device.hip.)
+int32_t midas_ctx::inflate_again(const char* who, const InflateParams& ip, const InflateBlock* blocks, const uint32_t* want, std::vector<uint32_t>& status, hipStream_t s,
                       bool* ran, char* err256) {
   *ran = false;
   std::vector<size_t> again;
@@ -140,6 +142,8 @@ int32_t inflate_again(const char* who, const InflateParams& ip, const InflateBlo
   for (size_t j = 0; j < n2; ++j) status[again[j]] = st2[j];
   return MIDAS_SNPS_OK;
 }
+
+namespace {
 
 // the first block of a decode that did not inflate to its bytes: named by its index in the file's table (job0: the first status's)
 int32_t check_block_statuses(const std::vector<uint32_t>& status, size_t job0, int64_t* bad_job, char* err256) {

@@ -45,6 +45,7 @@ enum : uint32_t { kOk = 0, kBadBlockType = 1, kBadStored = 2, kBadCodeLengths = 
                   kOutputOverrun = 6, kInputOverrun = 7, kShortOutput = 8, kMatchRoom = kInflateMatchRoom };
 
 constexpr uint32_t kEscape = 0xFF800000u;       // token: 511 in the literal field, the low 23 bits a count of literals, no match
+constexpr uint32_t kEscapeRunFlush = 0x7FFF00u; // a run of literals this long is sent as an escape token before its count outgrows the 23 bits
 
 // (pointers that SAY they point into LDS: through a generic pointer every table look-up would be a FLAT access, which waits
 // for the thread's outstanding global stores -- one store acknowledgement per symbol)
@@ -147,6 +148,9 @@ struct TokenOut {
   }
   // the lanes' common step: whole 16-byte stores of what has gathered
   __device__ __forceinline__ void service(const LV& L) {
+    // (a run of literals that nears what an escape token's 23 bits count -- megabytes of stored or incompressible bytes in one
+    // stream, never a BGZF block -- goes out as a token of its own; a run grows by 16 literals at most between two common steps)
+    if (run >= kEscapeRunFlush) { push(L, kEscape | run); run = 0; }
     if (lw - lr >= 4u) store_lits(L);
     while (tw - tr >= 4u) store_toks(L);
   }

@@ -176,9 +176,19 @@ struct midas_snps_ctx {
   void stage_join() { if (stage_thread.joinable()) stage_thread.join(); }
 };
 
+// The samples' count tables of one merge, resident on the device: counts[sample][row][4] u32 (A, C, G, T), the layout the merge
+// kernels read (merge_sites.hip).  Filled by the device table readers (tables_device.hip) or from host arrays; one allocation.
+struct midas_merge_tables {
+  int device = -1;
+  int32_t n_samples = 0;
+  int64_t n_rows = 0;          // rows of every sample's table: the stride between two samples
+  uint32_t* d = nullptr;
+};
+
 // What the context's side (ctx_runtime.hip) lends the translation units that implement entry points (batch*.hip, bam_device.hip,
 // measure.hip): the one error idiom, the flags of every page-locked allocation, the copy kernel and the copies through the pinned
 // staging ring, and hipFree as a handle's free_fn.
+namespace midas { struct InflateParams; struct InflateBlock; }      // (kernels.h)
 namespace midas_ctx {
 #define MIDAS_INTERNAL __attribute__((visibility("hidden")))      // shared between the library's sources, not an exported symbol
 MIDAS_INTERNAL inline int32_t fail(midas_snps_ctx* ctx, int32_t st, const std::string& msg) {
@@ -224,4 +234,12 @@ struct GenesBamCall {
 // caller lends: too small is MIDAS_SNPS_ERR_OUT_OF_MEMORY).  Statuses, the context's error text and err_read as midas_genes_count.
 int32_t genes_count_stream(midas_snps_ctx* ctx, const uint8_t* d, unsigned long long total, const unsigned long long* rec_off, long long n,
                            uint8_t* scratch, size_t scratch_bytes, GenesBamCall* call);
+
+// bam_device.hip: the streams of an inflate whose matches did not fit their room (status kInflateMatchRoom) decoded again with the
+// bound's room, into the same output; their statuses replace the first pass's.  want: the streams' CRC-32 (nullptr: not checked).
+MIDAS_INTERNAL int32_t inflate_again(const char* who, const midas::InflateParams& ip, const midas::InflateBlock* blocks, const uint32_t* want,
+                                     std::vector<uint32_t>& status, hipStream_t s, bool* ran, char* err256);
+
+// tables_device.hip: the resident set behind the merge's host-array entry points -- made from the arrays, freed by the caller
+int32_t merge_tables_from_host(midas_snps_ctx* ctx, int32_t n_samples, int64_t n_sites, const uint32_t* const* sample_counts, midas_merge_tables** out);
 }  // namespace midas_ctx

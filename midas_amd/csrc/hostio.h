@@ -34,6 +34,17 @@ struct BlockInflater {
                  size_t out_bytes, int64_t* bad_job, char* err256);
 };
 }  // namespace midas
+struct midas_snps_tableset;
+namespace midas {
+// An open midas_snps_tableset (tables_host.cpp) as the device readers (tables_device.hip) see it: per table its path, the file's
+// bytes, its rows (-1: the file does not announce them) and -- for a table that does -- every gzip member in file order.
+struct TableMemberSpan;
+int32_t tableset_tables(const midas_snps_tableset* ts);
+const char* tableset_path(const midas_snps_tableset* ts, int32_t t);
+const uint8_t* tableset_file(const midas_snps_tableset* ts, int32_t t, size_t* bytes);
+int64_t tableset_rows(const midas_snps_tableset* ts, int32_t t);
+const std::vector<TableMemberSpan>& tableset_members(const midas_snps_tableset* ts, int32_t t);
+}  // namespace midas
 struct midas_bam;
 namespace midas {
 // A BAM's bytes are MAPPED for the few places that look into them (the header's blocks, the search for a share's first record),

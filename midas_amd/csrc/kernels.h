@@ -371,6 +371,32 @@ struct LongParams {
 };
 hipError_t launch_pileup_long(const LongParams& p, hipStream_t s);
 
+// ---- tables_scan.hip: the rows of inflated <species>.snps.gz members parsed where they lie, their counts to [row][4] u32 ----
+// A member's text in the group's buffer.  Starts are multiples of 16 and ascend; no byte at or behind start + ulen (the member's
+// ISIZE) is looked at.  Of the member's rows (its header line is none) `take` behind the first `skip` go to rows dst_row ... of
+// `counts`; a malformed one among them is reported to bad[table] as table_row + its index in the member.
+struct TableTextMember {
+  uint32_t start, ulen;
+  uint32_t skip, take;
+  uint32_t take_base;               // rows taken by the members in front of this one
+  uint32_t table;
+  uint32_t header, rows;            // header != 0: the first line is the table's header line; rows: what the member announces
+  unsigned long long dst_row, table_row;
+};
+struct TablesScanParams {
+  const uint8_t* text; long long n16;             // the group's text: n16 words of 16 bytes (allocated that far)
+  const TableTextMember* members; int n_members;
+  uint32_t* word_lines;                           // [n16 + 1]: lines that end in every word, then their exclusive scan (the last entry: all lines)
+  uint32_t* scan_scratch;                         // scan_scratch_words(n16 + 1) words
+  uint32_t* line_end; uint32_t cap_lines;         // where line k ends (its newline, or the member's end for a last line without one), k < cap_lines
+  uint32_t* member_lines;                         // [n_members]: lines found in every member
+  uint32_t* counts;                               // [row][4]: A, C, G, T
+  unsigned long long* bad;                        // per table: its lowest malformed row among the rows taken (callers start it at ~0)
+  long long n_take;                               // rows taken by all members
+};
+hipError_t launch_tables_index(const TablesScanParams& p, hipStream_t s);      // word_lines, line_end, member_lines
+hipError_t launch_tables_parse(const TablesScanParams& p, hipStream_t s);      // behind it: counts, bad (a member whose lines are not header + rows is left alone)
+
 hipError_t launch_direct_facts(const DirectIndexParams& p, hipStream_t s);       // once per batch: validation, totals
 hipError_t launch_direct_layout_sizes(const DirectLayoutParams& p, hipStream_t s);   // once per batch: payload units per workgroup + their scan
 hipError_t launch_direct_layout_fill(const DirectLayoutParams& p, hipStream_t s);    // once per batch: records + payload

@@ -24,7 +24,8 @@ namespace {
 struct SampleLimit { uint32_t lo, hi, zero_from, zero_on; };
 
 struct MergeKParams {
-  const uint32_t* counts;     // [n_samples][n_sites][4]
+  const uint32_t* counts;     // [n_samples][row_stride][4]: this chunk's first site of sample 0; the resident set's rows
+  unsigned long long row_stride;   // rows between two samples' tables (>= n_sites: the chunk is a window of the resident set)
   const SampleLimit* limit;   // [n_samples]
   uint32_t* calls;            // [n_sites] bytes {major, minor, snp_type, flag}: 0..3 = A,C,G,T, 255 = None;
                               // snp_type 0 None, 1 mono, 2 bi, 3 tri, 4 quad; flag 0 keep, 1 min_prev, 2 snp_type
@@ -53,7 +54,7 @@ constexpr long long kMaxChunkSites = 1ll << 26;
 // Addressing: (uniform 64-bit base of the sample's row) + (32-bit byte offset of the site).  That is the form the
 // global_load / global_store "saddr + voffset" encoding takes: no 64-bit address arithmetic in vector registers.
 __device__ __forceinline__ u32x4 load_row(const MergeKParams& p, int s, uint32_t site) {
-  const char* base = reinterpret_cast<const char*>(p.counts + (size_t)s * p.n_sites * 4);
+  const char* base = reinterpret_cast<const char*>(p.counts + (size_t)s * p.row_stride * 4);
   return *reinterpret_cast<const u32x4*>(base + (site * 16u));
 }
 __device__ __forceinline__ void store_u32(uint32_t* table, const MergeKParams& p, int s, uint32_t site, uint32_t v) {
@@ -399,6 +400,15 @@ int32_t mfail(midas_snps_ctx* ctx, int32_t st, const char* what, hipError_t e) {
     }                                                                                                           \
   } while (0)
 
+// The host-array entry points: the arrays become a resident set (all of it: the chunks below bound the per-site results, the
+// counts of all sites lie on the device at once), the resident forms do the rest.
+namespace {
+struct HostTables {      // (freed on every way out)
+  midas_merge_tables* t = nullptr;
+  ~HostTables() { midas_merge_tables_free(t); }
+};
+}  // namespace
+
 extern "C" int32_t midas_merge_sites(midas_snps_ctx* ctx, const midas_merge_params* prm, int32_t n_samples,
                                      int64_t n_sites, const uint32_t* const* sample_counts, const double* mean_depth,
                                      uint8_t* out_calls, uint32_t* out_count_samples, uint64_t* out_pooled, uint32_t* out_depth,
@@ -407,11 +417,25 @@ extern "C" int32_t midas_merge_sites(midas_snps_ctx* ctx, const midas_merge_para
       !out_count_samples || !out_pooled || !out_depth || !out_minor_count)
     return MIDAS_SNPS_ERR_INVALID_ARG;
   ctx->clear_error();
+  HostTables host;
+  const int32_t st = midas_ctx::merge_tables_from_host(ctx, n_samples, n_sites, sample_counts, &host.t);
+  if (st != MIDAS_SNPS_OK) return st;
+  return midas_merge_sites_resident(ctx, prm, host.t, n_sites, mean_depth, out_calls, out_count_samples, out_pooled, out_depth, out_minor_count, out_kernel_ms);
+}
+
+extern "C" int32_t midas_merge_sites_resident(midas_snps_ctx* ctx, const midas_merge_params* prm, const midas_merge_tables* tables, int64_t n_sites,
+                                              const double* mean_depth, uint8_t* out_calls, uint32_t* out_count_samples, uint64_t* out_pooled,
+                                              uint32_t* out_depth, uint32_t* out_minor_count, float* out_kernel_ms) {
+  if (!ctx || !prm || !tables || n_sites < 0 || n_sites > tables->n_rows || !mean_depth || !out_calls ||
+      !out_count_samples || !out_pooled || !out_depth || !out_minor_count)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  const int32_t n_samples = tables->n_samples;
+  ctx->clear_error();
   ctx->err_read = -1;
   if (out_kernel_ms) *out_kernel_ms = 0.f;
   std::vector<void*> dev;
   M_TRY(hipSetDevice(ctx->device));
-  // sites are processed in chunks so that any number of samples fits: <= ~4 GiB of count tables at a time
+  // sites are processed in chunks -- windows of the resident set of <= ~4 GiB of counts -- which bound the per-site results' buffers
   long long chunk = (long long)((4ull << 30) / (16ull * (unsigned long long)n_samples));
   if (chunk < 1024) chunk = 1024;
   if (chunk > kMaxChunkSites) chunk = kMaxChunkSites;
@@ -422,9 +446,8 @@ extern "C" int32_t midas_merge_sites(midas_snps_ctx* ctx, const midas_merge_para
   for (int s = 0; s < n_samples; ++s) shallow = shallow && mean_depth[s] <= 64.0;
   std::vector<SampleLimit> limits((size_t)n_samples);
   for (int s = 0; s < n_samples; ++s) limits[(size_t)s] = sample_limits(mean_depth[s], prm->site_ratio, prm->site_depth);
-  uint32_t* d_counts = nullptr; SampleLimit* d_md = nullptr; uint32_t* d_b = nullptr; uint32_t* d_cs = nullptr;
+  SampleLimit* d_md = nullptr; uint32_t* d_b = nullptr; uint32_t* d_cs = nullptr;
   unsigned long long* d_pool = nullptr; uint32_t* d_depth = nullptr; uint32_t* d_mc = nullptr; unsigned long long* d_err = nullptr;
-  M_TRY(hipMalloc(&d_counts, (size_t)chunk * n_samples * 16)); dev.push_back(d_counts);
   M_TRY(hipMalloc(&d_md, (size_t)n_samples * sizeof(SampleLimit))); dev.push_back(d_md);
   M_TRY(hipMalloc(&d_b, (size_t)chunk * 4)); dev.push_back(d_b);
   M_TRY(hipMalloc(&d_cs, (size_t)chunk * 4)); dev.push_back(d_cs);
@@ -440,12 +463,9 @@ extern "C" int32_t midas_merge_sites(midas_snps_ctx* ctx, const midas_merge_para
   int32_t status = MIDAS_SNPS_OK;
   for (long long lo = 0; lo < n_sites && status == MIDAS_SNPS_OK; lo += chunk) {
     const long long m = (n_sites - lo) < chunk ? (n_sites - lo) : chunk;
-    for (int s = 0; s < n_samples; ++s)
-      M_TRY(hipMemcpyAsync(d_counts + (size_t)s * m * 4, sample_counts[s] + (size_t)lo * 4, (size_t)m * 16,
-                           hipMemcpyHostToDevice, ctx->stream));
     M_TRY(hipMemsetAsync(d_err, 0xFF, 8, ctx->stream));
     MergeKParams k;
-    k.counts = d_counts; k.limit = d_md;
+    k.counts = tables->d + (size_t)lo * 4; k.row_stride = (unsigned long long)tables->n_rows; k.limit = d_md;
     k.calls = d_b;
     k.count_samples = d_cs; k.pooled = d_pool; k.depth = d_depth; k.minor_count = d_mc; k.err = d_err;
     k.n_sites = (uint32_t)m; k.n_samples = n_samples; k.snp_types = prm->snp_types;
@@ -497,6 +517,26 @@ extern "C" int32_t midas_merge_sites_tables(midas_snps_ctx* ctx, const midas_mer
       site_id_base < 0 || !out_calls || !out_count_samples || !out_pooled || !out_n_keep)
     return MIDAS_SNPS_ERR_INVALID_ARG;
   ctx->clear_error();
+  HostTables host;
+  const auto t0 = std::chrono::steady_clock::now();
+  int32_t st = midas_ctx::merge_tables_from_host(ctx, n_samples, n_sites, sample_counts, &host.t);
+  if (st == MIDAS_SNPS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = mfail(ctx, MIDAS_SNPS_ERR_HIP, "merge tables: upload", hipGetLastError());
+  if (st != MIDAS_SNPS_OK) return st;
+  if (getenv("MIDAS_SNPS_TRACE"))
+    fprintf(stderr, "[merge tables] upload %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  return midas_merge_sites_tables_resident(ctx, prm, host.t, n_sites, mean_depth, freq_path, depth_path, header_line, site_id_base, out_calls, out_count_samples,
+                                           out_pooled, out_n_keep, out_kernel_ms, out_format_ms);
+}
+
+extern "C" int32_t midas_merge_sites_tables_resident(midas_snps_ctx* ctx, const midas_merge_params* prm, const midas_merge_tables* tables, int64_t n_sites,
+                                                     const double* mean_depth, const char* freq_path, const char* depth_path, const char* header_line,
+                                                     int64_t site_id_base, uint8_t* out_calls, uint32_t* out_count_samples, uint64_t* out_pooled,
+                                                     int64_t* out_n_keep, float* out_kernel_ms, float* out_format_ms) {
+  if (!ctx || !prm || !tables || n_sites < 0 || n_sites > tables->n_rows || !mean_depth || !freq_path || !depth_path || !header_line ||
+      site_id_base < 0 || !out_calls || !out_count_samples || !out_pooled || !out_n_keep)
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  const int32_t n_samples = tables->n_samples;
+  ctx->clear_error();
   ctx->err_read = -1;
   *out_n_keep = 0;
   if (out_kernel_ms) *out_kernel_ms = 0.f;
@@ -525,9 +565,8 @@ extern "C" int32_t midas_merge_sites_tables(midas_snps_ctx* ctx, const midas_mer
   int32_t status = sink.start();
   if (status != MIDAS_SNPS_OK) return status;
   if ((status = fmt.prepare(chunk, true)) != MIDAS_SNPS_OK) return status;
-  uint32_t* d_counts = nullptr; SampleLimit* d_md = nullptr; uint32_t* d_b = nullptr; uint32_t* d_cs = nullptr;
+  SampleLimit* d_md = nullptr; uint32_t* d_b = nullptr; uint32_t* d_cs = nullptr;
   unsigned long long* d_pool = nullptr; uint32_t* d_depth = nullptr; uint32_t* d_mc = nullptr; unsigned long long* d_err = nullptr;
-  M_TRY(hipMalloc(&d_counts, (size_t)chunk * n_samples * 16)); dev.push_back(d_counts);
   M_TRY(hipMalloc(&d_md, (size_t)n_samples * sizeof(SampleLimit))); dev.push_back(d_md);
   M_TRY(hipMalloc(&d_b, (size_t)chunk * 4)); dev.push_back(d_b);
   M_TRY(hipMalloc(&d_cs, (size_t)chunk * 4)); dev.push_back(d_cs);
@@ -544,20 +583,14 @@ extern "C" int32_t midas_merge_sites_tables(midas_snps_ctx* ctx, const midas_mer
   M_TRY(hipEventCreate(&ev.b));
   const hipEvent_t e0 = ev.a, e1 = ev.b;
   float total_ms = 0.f;
-  double upload_s = 0, results_s = 0, rows_s = 0;
+  double results_s = 0, rows_s = 0;
   long long n_keep = 0;
   for (long long lo = 0; lo < n_sites && status == MIDAS_SNPS_OK; lo += chunk) {
     const long long m = (n_sites - lo) < chunk ? (n_sites - lo) : chunk;
     double t0 = now();
-    for (int s = 0; s < n_samples; ++s)
-      M_TRY(hipMemcpyAsync(d_counts + (size_t)s * m * 4, sample_counts[s] + (size_t)lo * 4, (size_t)m * 16,
-                           hipMemcpyHostToDevice, ctx->stream));
     M_TRY(hipMemsetAsync(d_err, 0xFF, 8, ctx->stream));
-    M_TRY(hipStreamSynchronize(ctx->stream));
-    upload_s += now() - t0;
-    t0 = now();
     MergeKParams k;
-    k.counts = d_counts; k.limit = d_md;
+    k.counts = tables->d + (size_t)lo * 4; k.row_stride = (unsigned long long)tables->n_rows; k.limit = d_md;
     k.calls = d_b;
     k.count_samples = d_cs; k.pooled = d_pool; k.depth = d_depth; k.minor_count = d_mc; k.err = d_err;
     k.n_sites = (uint32_t)m; k.n_samples = n_samples; k.snp_types = prm->snp_types;
@@ -611,9 +644,9 @@ extern "C" int32_t midas_merge_sites_tables(midas_snps_ctx* ctx, const midas_mer
   }
   *out_n_keep = (int64_t)n_keep;
   if (getenv("MIDAS_SNPS_TRACE"))
-    fprintf(stderr, "[merge tables] upload %.3f s, kernel %.3f ms, per-site results down %.3f s, rows %.3f s (format %.3f ms on the device, "
+    fprintf(stderr, "[merge tables] kernel %.3f ms, per-site results down %.3f s, rows %.3f s (format %.3f ms on the device, "
             "text down %.3f s, waiting for the file writer in between), file write %.3f s on the writer thread (%.3f s of it after the last batch), "
-            "%lld bytes of text, %lld kept rows\n", upload_s, total_ms, results_s, rows_s, fmt.format_ms, sink.copy_s, sink.write_s, tail_s,
+            "%lld bytes of text, %lld kept rows\n", total_ms, results_s, rows_s, fmt.format_ms, sink.copy_s, sink.write_s, tail_s,
             sink.bytes, n_keep);
   return MIDAS_SNPS_OK;
 }

@@ -1,5 +1,6 @@
 // The <species>.snps.gz tables on the host: their readers, the row / matrix / info writers and the gzip members they are made of.
 #include "hostio_internal.h"
+#include "tables_plan.h"
 
 // One sample's <species>.snps.gz, parsed: what build_temp_count_matrix (midas/merge/snps.py:246-271) extracts.
 struct ParsedRows {
@@ -25,6 +26,7 @@ struct midas_snps_tableset {
   std::vector<std::string> paths;
   std::vector<RawBuf<uint8_t>> files;
   std::vector<std::vector<TableSetMember>> members;    // per table, the members that hold rows
+  std::vector<std::vector<midas::TableMemberSpan>> all; // per table that announces its rows, every member in file order (the device readers plan over them)
   std::vector<int64_t> rows;                            // per table, -1 = the file does not announce its rows
 };
 
@@ -364,6 +366,7 @@ int32_t midas_snps_tableset_open(int32_t n_tables, const char* const* paths, mid
   ts->paths.resize(n);
   ts->files.resize(n);
   ts->members.resize(n);
+  ts->all.resize(n);
   ts->rows.assign(n, -1);
   // every file in 8 MiB pieces, all pieces of all files in one parallel region
   struct Piece { size_t table, off, len; };
@@ -402,6 +405,7 @@ int32_t midas_snps_tableset_open(int32_t n_tables, const char* const* paths, mid
     int64_t at = 0;
     for (const TableMember& m : all) {
       if (m.rows > 0) ts->members[t].push_back({m.data, m.clen, m.ulen, at, m.rows});
+      ts->all[t].push_back(midas::TableMemberSpan{(uint64_t)m.data, (uint32_t)m.clen, (uint32_t)m.ulen, m.rows});
       at += m.rows;
     }
     ts->rows[t] = at;
@@ -412,6 +416,17 @@ int32_t midas_snps_tableset_open(int32_t n_tables, const char* const* paths, mid
 }
 
 void midas_snps_tableset_close(midas_snps_tableset* ts) { delete ts; }
+
+}  // extern "C"
+namespace midas {
+// the open set as the device readers see it (hostio.h)
+int32_t tableset_tables(const midas_snps_tableset* ts) { return (int32_t)ts->paths.size(); }
+const char* tableset_path(const midas_snps_tableset* ts, int32_t t) { return ts->paths[(size_t)t].c_str(); }
+const uint8_t* tableset_file(const midas_snps_tableset* ts, int32_t t, size_t* bytes) { *bytes = ts->files[(size_t)t].size(); return ts->files[(size_t)t].data(); }
+int64_t tableset_rows(const midas_snps_tableset* ts, int32_t t) { return ts->rows[(size_t)t]; }
+const std::vector<TableMemberSpan>& tableset_members(const midas_snps_tableset* ts, int32_t t) { return ts->all[(size_t)t]; }
+}  // namespace midas
+extern "C" {
 
 int32_t midas_snps_tableset_read_counts(midas_snps_tableset* ts, int64_t row_begin, int64_t n_rows, uint32_t* const* out_counts,
                                         char* err256) {

@@ -6,7 +6,8 @@ GenomicSite (pooled counts, allele calls, per-sample depth/MAF, prevalence, flag
 sites of a species at once (midas_merge_sites in include/midas_snps.h); the temporary acgt_counts matrices and the
 per-thread shard files of the reference are not needed.  The rows of snps_freq.txt / snps_depth.txt (:196-201) can be formatted
 on the GPU as well (midas_merge_sites_tables, MIDAS_SNPS_MERGE_WRITERS=device); annotation (:116-174) and snps_info.txt stay on the host and touch only
-the sites that survive the filters.  No CPU fallback for the arithmetic.
+the sites that survive the filters.  No CPU fallback for the arithmetic.  The samples' count tables can be inflated and parsed on the
+GPU too (MIDAS_SNPS_MERGE_READERS=device): tables 1..S-1 then never exist as host arrays, the merge reads them where the readers left them.
 """
 
 import os
@@ -31,13 +32,55 @@ def _table_paths(species):
     return ['%s/snps/output/%s.snps.gz' % (s.dir, species.id) for s in species.samples]
 
 
-def load_sample_tables(species, args, row_range=None):
+def _load_on_device(ctx, paths, lo, hi):
+    """The device readers (MIDAS_SNPS_MERGE_READERS=device): the first sample's table stays with the host reader on a thread of its
+    own -- only that table's site keys are used -- and its counts go into slot 0; tables 1..S-1 are inflated and parsed on the device.
+    -> (abi.MergeTables, keys, key_off), or None with one log line when this merge takes the host readers after all."""
+    why = None
+    if not hasattr(ctx, 'read_snps_counts_device'):
+        why = 'the context has no device readers'
+    elif len(paths) < 2:
+        why = 'one sample: its table is read for the site keys anyway'
+    else:
+        silent = [p for p in paths if abi.count_snps_rows(p) < 0]       # gzip member headers only: cheap
+        if silent:
+            why = '%s does not announce its rows' % silent[0]
+    if why is None:
+        with ThreadPoolExecutor(1) as ex:
+            first = ex.submit(abi.read_snps_table, paths[0], hi, True, lo)
+            tables = None
+            try:
+                tables = ctx.read_snps_counts_device(paths[1:], lo, hi, first_slot=1)
+                c0, keys, key_off = first.result()
+                n = min(c0.shape[0], tables.n_rows)
+                tables.set_host(0, c0[:n])
+                tables.n_sites = n
+            except abi.MidasSnpsError as e:
+                if tables is not None:
+                    tables.close()
+                if e.status != abi.ERR_UNSUPPORTED:
+                    raise
+                why = e.message
+    if why is not None:
+        print("    sample tables: host readers (%s)" % why)
+        return None
+    print("    sample tables: device readers (%d tables in %d gzip members, %d groups)"
+          % (len(paths) - 1, tables.stats.get('members', 0), tables.stats.get('groups', 0)))
+    return tables, keys, key_off[:n + 1]
+
+
+def load_sample_tables(species, args, row_range=None, ctx=None):
     """read_run_midas_snps + the zip of build_temp_count_matrix (midas/merge/snps.py:236-271), without the
     temporary matrices: per sample the [n_sites,4] counts, plus the site keys of the first sample.  row_range = (lo, hi):
-    only those rows of every table (one rank's share of a site-sharded merge)."""
+    only those rows of every table (one rank's share of a site-sharded merge).  With MIDAS_SNPS_MERGE_READERS=device and a context
+    that offers read_snps_counts_device the counts are an abi.MergeTables (resident on the device) instead of a list of arrays."""
     max_rows = -1 if args['max_sites'] == float('Inf') else int(args['max_sites'])
     lo, hi = row_range if row_range is not None else (0, max_rows)
     paths = _table_paths(species)
+    if ctx is not None and os.environ.get('MIDAS_SNPS_MERGE_READERS', 'host') == 'device':
+        loaded = _load_on_device(ctx, paths, lo, hi)
+        if loaded is not None:
+            return loaded
     # tables written by this library announce their rows: every gzip member of every sample is one task of a single
     # parallel region; the site keys come from the first sample's table alone, as in the reference
     with ThreadPoolExecutor(1) as ex:      # the first sample's table (keys + counts) beside the others' counts
@@ -73,9 +116,10 @@ def merge_species(species, args, ctx, row_range=None, part=None):
         return 0, 0, 0.0
     with ThreadPoolExecutor(1) as ex:      # the gene table is Python work: it runs while the native reader has the cores
         genes_job = ex.submit(annotate.GeneCursor.from_db, species.id, args['db'])
-        counts, keys, key_off = load_sample_tables(species, args, row_range)
+        counts, keys, key_off = load_sample_tables(species, args, row_range, ctx)
         genes = genes_job.result()
-    n = counts[0].shape[0]
+    resident = isinstance(counts, abi.MergeTables)
+    n = counts.n_sites if resident else counts[0].shape[0]
     prm = abi.MergeParams.from_args(args)
     # snps_freq.txt / snps_depth.txt: one number per (kept site, sample).  By default the per-sample arrays come down and host
     # threads format them.  MIDAS_SNPS_MERGE_WRITERS=device, on a context that offers merge_sites_tables, formats both tables'
@@ -93,6 +137,9 @@ def merge_species(species, args, ctx, row_range=None, part=None):
         if e.status == abi.ERR_MERGE_ZERO_MEAN_DEPTH and e.read_index >= 0 and base:
             sys.exit("\nError: %s [row %d of the species' tables]\n" % (e.message, base + e.read_index + 1))
         sys.exit("\nError: %s\n" % e.message)
+    finally:
+        if resident:
+            counts.close()
     keep = np.nonzero(res['flag'] == 0)[0]
     if on_device:
         if res['n_keep'] != len(keep):

@@ -1,11 +1,14 @@
 """Developer script (GPU box): `merge_midas.py snps` on one species, S samples x n sites, phase by phase -- through
 midas_amd.merge.snps.merge_species alone, so that the same file runs on any commit that has it.
 
-    python tools/merge_snps_e2e.py [--sites 2000000] [--samples 50] [--runs 5] [--modes device,host] [--data DIR] [--preset all_sites]
+    python tools/merge_snps_e2e.py [--sites 2000000] [--samples 50] [--runs 5] [--modes device,host] [--readers host,device] [--data DIR] [--preset all_sites]
 
 Setup (not timed): the samples' tables written with the library's own writer under --data (default: a fresh directory on tmpfs;
 an existing one is reused, so two commits can be timed on the same files).  Timed: merge_species, --runs times per mode after one
 warm-up, the modes taking turns (MIDAS_SNPS_MERGE_WRITERS=<mode>; a commit without the switch runs the host writers either way).
+--readers: who reads the samples' tables (MIDAS_SNPS_MERGE_READERS=<reader>; default host): every reader x writer combination is
+a mode of its own ("<reader> readers / <writer> writers").  'tables read' = load_sample_tables as a whole; the device readers' own
+laps (upload, inflate + CRC, index, parse: HIP events) and counts are printed beside it.
 Phases come from timers around the calls merge_species makes (tables read, the merge call, the host writers, snps_info) and,
 where the library prints them (MIDAS_SNPS_TRACE), from its own `[merge tables]` line: upload, kernel, format, text down, file
 write.  'tables out' = from the start of the merge call to the last byte of snps_freq / snps_depth: upload + kernel + (arrays or
@@ -97,6 +100,7 @@ def main():
     ap.add_argument("--samples", type=int, default=50)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--modes", default="device,host")
+    ap.add_argument("--readers", default="host")
     ap.add_argument("--data", default=None)
     ap.add_argument("--preset", default="all_sites", choices=["all_sites", "core_snps"])
     ap.add_argument("--threads", type=int, default=16)
@@ -117,15 +121,27 @@ def main():
         args.update(snp_type=['any'], site_prev=0.0)
     sp = merge.select_species(args, 'snps')[0]
     T = Timers()
-    T.wrap(abi, 'read_snps_counts', 'tables read')
+    T.wrap(msnps, 'load_sample_tables', 'tables read')
+    T.wrap(abi, 'read_snps_counts', 'tables read: the host readers of samples 1..S-1')
     T.wrap(abi, 'read_snps_table', 'tables read (first sample, beside the others)')
     T.wrap(abi, 'write_merge_matrix', 'host writers')
     T.wrap(abi, 'write_merge_info', 'info')
     T.wrap(annotate.GeneCursor, 'from_db', 'gene table (beside the tables read)')
     T.wrap(abi.Context, 'merge_sites', 'merge call')
     T.wrap(abi.Context, 'merge_sites_tables', 'merge call')
+    device_laps = []
+    if hasattr(abi.Context, 'read_snps_counts_device'):
+        read_on_device = abi.Context.read_snps_counts_device
+
+        def timed_read(self, *args_, **kw):
+            t0 = time.perf_counter()
+            tables = read_on_device(self, *args_, **kw)
+            device_laps.append(dict(tables.ms, **{'whole call (open + plan + laps)': (time.perf_counter() - t0) * 1e3}, **{k: float(v) for k, v in tables.stats.items()}))
+            return tables
+        abi.Context.read_snps_counts_device = timed_read
     ctx = abi.Context(0)
-    modes = a.modes.split(",")
+    modes = ["%s/%s" % (r, w) for r in a.readers.split(",") for w in a.modes.split(",")]
+    laps = {m: [] for m in modes}
     os.environ['MIDAS_SNPS_TRACE'] = '1'
     trace_path = os.path.join(root, "trace.txt")
     rows = {m: [] for m in modes}
@@ -133,8 +149,9 @@ def main():
     kept = None
     for it in range(a.runs + 1):          # run 0 warms up (page cache, pinned ring, device buffers)
         for m in modes:
-            os.environ['MIDAS_SNPS_MERGE_WRITERS'] = m
+            os.environ['MIDAS_SNPS_MERGE_READERS'], os.environ['MIDAS_SNPS_MERGE_WRITERS'] = m.split("/")
             T.reset()
+            del device_laps[:]
             sys.stderr.flush()
             saved = os.dup(2)
             fd = os.open(trace_path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC)
@@ -158,15 +175,20 @@ def main():
                 rows[m].append(r)
                 if line:
                     traces[m].append(line[-1])
+                laps[m].extend(device_laps)
             sizes = [os.path.getsize(os.path.join(out, 'sp1', f)) for f in ('snps_freq.txt', 'snps_depth.txt', 'snps_info.txt')]
-            print("  run %d %-6s tables out %.3f s, whole %.3f s (freq %d B, depth %d B, info %d B)%s"
+            print("  run %d %-13s tables out %.3f s, whole %.3f s (freq %d B, depth %d B, info %d B)%s"
                   % (it, m, r['tables out'], total, sizes[0], sizes[1], sizes[2], "  [warm-up]" if it == 0 else ""), flush=True)
     print("\n%d sites x %d samples, %d kept rows, preset %s, %d runs a mode after one warm-up; median [min .. max], seconds" % (n, S, kept, a.preset, a.runs))
     for m in modes:
-        print("mode %s" % m)
+        print("mode %s readers / %s writers" % tuple(m.split("/")))
         for k in sorted(rows[m][0]):
             v = [r.get(k, 0.0) for r in rows[m]]
             print("  %-48s %9.4f  [%9.4f .. %9.4f]" % (k, statistics.median(v), min(v), max(v)))
+        if laps[m]:
+            for key in laps[m][0]:
+                v = [l[key] for l in laps[m]]
+                print("  device readers: %-32s %12.3f  [%12.3f .. %12.3f]%s" % (key, statistics.median(v), min(v), max(v), "  ms" if key in abi.TABLES_READ_PHASES or 'call' in key else ""))
         if traces[m]:
             nums = {}
             for l in traces[m]:
@@ -189,10 +211,17 @@ def main():
                 need = cells * 8 + text
                 print("  formatter: must read %.0f MB (8 B a cell) and write %.0f MB of text; %.3f ms on the device = %.1f GB/s = %.1f %% of the 8 TB/s HBM peak"
                       % (cells * 8 / 1e6, text / 1e6, fms, need / fms / 1e6, 100.0 * need / (fms * 1e-3) / 8e12))
-    if len(modes) == 2:
+    if len(modes) == 2 and len(a.readers.split(",")) == 1:
         a0, a1 = ([r['tables out'] for r in rows[m]] for m in modes)
         print("tables out, %s vs %s: medians %.3f vs %.3f s; spread (max - min) %.3f and %.3f s" %
               (modes[0], modes[1], statistics.median(a0), statistics.median(a1), max(a0) - min(a0), max(a1) - min(a1)))
+    if len(a.readers.split(",")) == 2:
+        for w in a.modes.split(","):
+            r0, r1 = ("%s/%s" % (r, w) for r in a.readers.split(","))
+            for key in ('tables read', 'whole merge_species'):
+                v0, v1 = [r[key] for r in rows[r0]], [r[key] for r in rows[r1]]
+                print("%s, %s writers, %s vs %s readers: medians %.3f vs %.3f s; spread (max - min) %.3f and %.3f s" %
+                      (key, w, r0.split("/")[0], r1.split("/")[0], statistics.median(v0), statistics.median(v1), max(v0) - min(v0), max(v1) - min(v1)))
     ctx.close()
 
 
