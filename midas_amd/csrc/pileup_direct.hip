@@ -68,6 +68,24 @@ __device__ __forceinline__ uint32_t quad_take(uint32_t x) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, J * 0x55, 0xF, 0xF, false);
 }
 
+// DirectParams again, out of the kernel's argument segment: a field that only a tile's end or a rare branch uses is loaded where
+// it is used (one scalar load) and holds no scalar registers through the stream loop, which has none to spare.  (The empty asm
+// keeps the compiler from merging these loads with the ones at the kernel's top.)
+typedef const __attribute__((address_space(4))) DirectParams* ParamsAgain;
+__device__ __forceinline__ ParamsAgain params_again() {
+  ParamsAgain k = (ParamsAgain)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+
+// A scalar in a register of its own: a word of a block of scalars that one load brought (the kernel's arguments, a tile's eight
+// words) otherwise keeps the whole block alive, and the block is saved and restored as one.
+__device__ __forceinline__ int own_scalar(int x) {
+  int y;
+  asm volatile("s_mov_b32 %0, %1" : "=s"(y) : "s"(x));
+  return y;
+}
+
 // Eight bases of one lane: b0 / b1 two words of four base bytes (layout.h dense_byte, bases in order), thr the byte threshold
 // (dense_threshold, wave-uniform).  Per base one SDWA OR forming the LDS address of its counter ((byte & 3) << 2, two ALU ops a
 // word), one SDWA compare `byte >= thr` into a lane mask, one returnless ds_add under it.
@@ -165,9 +183,13 @@ static_assert(kDirectBlock % 64 == 0 && kDirectBlock >= 128 && kDirectBlock <= 1
 constexpr int kDirectWavesPerSimd = (kWorkgroupsPerCU * kDirectBlock / 64 + 3) / 4;      // four workgroups per CU
 
 
-template <int LB, bool BQ0, int OV = kDirectOverhang>
+// LPR: the lanes per read where they are a compile-time constant (4: the lane geometry, the phase of four iterations and the DPP
+// hand-off are static), 0: whatever DirectParams says, the generic body.
+template <int LB, bool BQ0, int OV = kDirectOverhang, int LPR = 0>
 __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_direct_kernel(DirectParams p) {
   static_assert(LB == 30 || LB == 32 || LB == 38, "a lane's bases: 8 or 10 words of four base bytes");
+  static_assert(LPR == 0 || (LPR == 4 && OV == kDirectOverhang), "static lane geometry: four lanes per read");
+  constexpr bool QUAD = LPR == 4;
   constexpr int TILE = kTileSites;
   constexpr int NW = (LB + 3) / 4;          // words of base bytes a lane holds (the last one of LB = 30 / 38: two bytes)
   constexpr int NG = (LB + 7) / 8;          // groups of eight bases (the last one of LB = 30 / 38: six)
@@ -208,7 +230,6 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
   const bool dynamic = (gridDim.x % kSchedGroups) == 0;
 #endif
   const int sched_group = (int)(blockIdx.x % kSchedGroups);
-  uint32_t* const sched = p.sched;
   if ((int)blockIdx.x >= w_end) return;
   int c_first = item_first((int)blockIdx.x), c_end = item_end((int)blockIdx.x);      // the chunk in work: tiles [c_first, c_end)
   int i_next = (int)blockIdx.x + (int)gridDim.x;                                      // the item after it (>= w_end: none)
@@ -238,8 +259,8 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     if (tid < MIDAS_STATS) s_stats[tid] = 0ull;
   }
 
-  const int lpr = p.lanes_per_read;
-  const int rpw = p.reads_per_wave;
+  const int lpr = QUAD ? 4 : p.lanes_per_read;
+  const int rpw = QUAD ? 16 : p.reads_per_wave;
   const int g = lane / lpr;
   const int c = lane - g * lpr;
   const int q0 = c * LB;                           // first base of the lane in the read's stored query
@@ -248,12 +269,12 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
   const uint32_t thr = BQ0 ? dense_threshold(0) : dense_threshold(p.baseq);
   const int rq = p.readq < 0 ? 0 : (p.readq > 256 ? 256 : p.readq);   // sum(q) < rq * l  <=>  np.mean(q) < readq (q <= 255)
   const uint32_t one = 1u;
+  const int table_len = own_scalar(p.table_len), mapq_min = own_scalar(p.mapq_min);
 
-  const ConstWords c_tiles = (ConstWords)(size_t)p.tiles;
-  const ConstWords c_tb = (ConstWords)(size_t)p.tbegin;
-  const ConstWords c_te = (ConstWords)(size_t)p.tend;
   // (cin: the tile continues a chunk in its contig -- the reads that reach in from the tile before were tallied by that tile)
-  auto load_stream = [&](int tt, bool cin) -> Stream {
+  auto load_stream = [&](ParamsAgain q, int tt, bool cin) -> Stream {
+    const ConstWords c_tb = (ConstWords)(size_t)q->tbegin;
+    const ConstWords c_te = (ConstWords)(size_t)q->tend;
     Stream s;
     const uint32_t b = cin ? c_te[tt - 1] : c_tb[tt], e = c_te[tt];
     s.rb = e > b ? (int)b : 0;
@@ -313,13 +334,13 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
   // lane count: lane j * rpw + g and ds_bpermute_b32.  A phase never straddles a tile.  PH is even where two iterations fit
   // (the two sets of base registers keep their roles inside a tile); with one lane per read a phase is one iteration.
   const int ph_fit = 64 / rpw;
-  const int PH = ph_fit >= 4 ? 4 : (ph_fit >= 2 ? 2 : 1);
-  const bool quad = lpr == 4;
+  const int PH = QUAD ? 4 : (ph_fit >= 4 ? 4 : (ph_fit >= 2 ? 2 : 1));
+  const bool quad = QUAD || lpr == 4;
   // (one register: the iteration oj of its phase and the read og of that iteration this lane owns, as the read's place among the
   // wave's reads of the phase's tile, oj * NWAVES * rpw + og, with oj in the top byte)
   const uint32_t own_slot = quad ? (uint32_t)((lane & 3) * NWAVES * rpw + (lane >> 2)) | ((uint32_t)(lane & 3) << 24)
                                  : (uint32_t)((lane / rpw) * NWAVES * rpw + lane % rpw) | ((uint32_t)(lane / rpw) << 24);
-  const bool lane_on = g < rpw;                                  // (64 % lpr lanes at the wave's end never hold a read)
+  const bool lane_on = QUAD || g < rpw;                                  // (64 % lpr lanes at the wave's end never hold a read)
   // iterations of the phase that opens with `rem` of the wave's iterations of a tile left: PH, but 2 + 3 for the last five of PH =
   // 4 (not 4 + 1: a phase of at least two iterations requests the next phase's CIGARs a whole iteration ahead of their use)
   auto phase_len = [&](int rem) -> int { return (PH == 4 && rem == 5) ? 2 : (rem < PH ? rem : PH); };
@@ -392,8 +413,8 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
   // (l_seq and the clip are at most kMaxLSeq = 1024, a deletion or skip at most kMaxFastGap: direct_common.h ReadShape)
   struct Desc { uint32_t d0, d1, d2, d3; };
 
-  Tile tile = load_tile(c_tiles, c_first);
-  Stream st = load_stream(c_first, false);
+  Tile tile = load_tile((ConstWords)(size_t)p.tiles, c_first);
+  Stream st = load_stream(params_again(), c_first, false);
   // The pipeline of a wave.  Bases: two register sets that swap roles every iteration (the phase's body is unrolled: a copy at a
   // back edge would have to WAIT for the loads it copies -- the next iteration's bases, requested a moment ago):
   //   set A / B   one holds the iteration being tallied, the other the next one's bases (in flight)
@@ -421,14 +442,17 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
   unsigned long long acc_depth = 0ull;
   int t = c_first;
   for (;;) {
-    const int tile_len = tile.len;
-    const int tile_start = tile.start;
+    // (what the stream loop uses of the tile: scalars of their own, not parts of the eight words the tile was loaded in)
+    const int tile_len = own_scalar(tile.len), tile_start = own_scalar(tile.start), contig_len = own_scalar(tile.contig_len);
     // the tile after this one: the chunk's next, or the next item's first
     const bool in_chunk = t + 1 < c_end;
     const bool more = in_chunk || i_next < w_end;
     const int wn = in_chunk ? t + 1 : (more ? item_first(i_next) : t);
     // (a chunk that holds -- or is reached by -- a read spanning more than the overhang is piled up tile by tile: chunk_ok)
-    const bool carry = in_chunk && (!p.chunk_ok || p.chunk_ok[c_first / K] != 0);
+    const ParamsAgain pt = params_again();
+    const ConstWords c_tiles = (ConstWords)(size_t)pt->tiles;
+    const uint8_t* const chunk_ok = pt->chunk_ok;
+    const bool carry = in_chunk && (!chunk_ok || chunk_ok[c_first / K] != 0);
     const bool cout = carry && (int32_t)c_tiles[8 * (size_t)wn] == tile.contig;      // its first OV sites are tallied here
     // (the contig's last tile may be shorter than the overhang: nothing is tallied behind the contig's end)
     const int next_len = (int32_t)c_tiles[8 * (size_t)wn + 2];
@@ -442,7 +466,41 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     const int n_w = it_hi > wave ? (it_hi - wave + NWAVES - 1) / NWAVES : 0;
     const bool xt = more && n_w >= 2;
     Stream xs = st;
-    if (xt) xs = load_stream(wn, cout);
+    if (xt) xs = load_stream(pt, wn, cout);
+    // The stream the iterations' records are being fetched from: this tile's, and from where the prefetch crosses into the next
+    // tile the next tile's -- switched ONCE there (cross_if_due, between two iterations), not selected in every iteration.
+    //   f_left  fetches until the prefetch crosses
+    //   f, f_i  the stream and its wave-iteration to fetch next -- or, with the static lane geometry (a vector register for a scalar one):
+    //   f_rec   per lane: the index of the record it fetches next, rb + it * rpw + g (one add an iteration)
+    //   f_end   the stream's end, rb + n0: a lane at or behind it has no read (it fetches record 0)
+    //   f_rem   reads of the stream from the iteration to fetch onwards, n0 - it * rpw (may be <= 0)
+    // (the wave's iterations 0 and 1 of this tile are in the pipeline: n_w - 2 more of this tile, if the prefetch crosses at all;
+    // a stream holds fewer than 2^31 reads and it * rpw <= n0 + 63 + 2 * kDirectBlock)
+    constexpr int f_step = NWAVES * 16;
+    Stream f = st;
+    int f_i = 0;
+    uint32_t f_rec = 0u;
+    int f_end = 0, f_rem = 0;
+    auto fetch_from = [&](const Stream& s, int it) {
+      if constexpr (QUAD) {
+        f_rec = (uint32_t)s.rb + (uint32_t)(it * 16) + (uint32_t)g;
+        f_end = s.rb + s.n0;
+        f_rem = s.n0 - it * 16;
+      } else {
+        f.rb = s.rb; f.n0 = s.n0;
+        f_i = it;
+      }
+    };
+    fetch_from(st, wave + 2 * NWAVES);
+    int f_left = xt ? n_w - 2 : 0x7FFFFFFF;
+    auto cross_if_due = [&]() {
+      if (f_left == 0) {
+        fetch_from(xs, wave);
+        f_left = -1;
+        asm volatile("");      // (a branch, not selects: the next stream's scalars are read here only)
+      }
+    };
+    cross_if_due();
     // ---- a read walked op by op (the slow path), by the lanes that would hold its bases.  Rare: what the lanes need -- record,
     // CIGAR, quality sum, bases -- they fetch here, by the read's index; keep_read with every test evaluated and the reference's
     // order of outcomes, counters and error of its own.
@@ -507,13 +565,13 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         });
       }
       // ---- keep_read, every test evaluated, the reference's order decides which outcome wins ---------------------------
-      const int min_match = s_tables[align_g < p.table_len ? align_g : 0];
-      const int min_align = s_tables[p.table_len + (l < p.table_len ? l : 0)];
+      const int min_match = s_tables[align_g < table_len ? align_g : 0];
+      const int min_align = s_tables[table_len + (l < table_len ? l : 0)];
       const bool t_noseq = l == 0;
       const bool t_nonm = nm16 == 0xFFFFu;
       const bool t_zero = align_g == 0;
       const bool t_pid = align_g - nm < min_match;
-      const bool t_drop = ((int)qsum < rq * l) | (mapq < p.mapq_min) | (align_g < min_align);
+      const bool t_drop = ((int)qsum < rq * l) | (mapq < mapq_min) | (align_g < min_align);
       uint32_t e = t_over ? (uint32_t)E_CIGAR_OVERRUN : 0u;
       e = t_drop ? 0u : e;
       e = t_noqual ? (uint32_t)E_NO_QUAL : e;
@@ -574,7 +632,7 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     // ---- the start of a phase of n_ph iterations, the wave's k0-th onwards: every owner its read, from raw N / own N (requested
     // in the phase before, or in front of the tile).  Then the records of the phase after it are requested: the next of this
     // tile, or the first of the next tile's stream (`xs`, as the bases' look-ahead).
-    auto open_phase = [&](int k0, int n_ph) {
+    auto open_phase = [&](int k0, int n_ph, const Stream& nf, int nf_k, int nf_len) {
       MIDAS_MARK("phase");
       uint32_t idx;
       const bool act = owned(st, k0, n_ph, &idx);
@@ -602,15 +660,15 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         if (!shaped) { sh = s2; shaped = ok; }
       }
       // one or two match runs, NM present, the start inside the contig: the fast path.  Everything else is walked.
-      const bool fast = act && shaped && nm16 != 0xFFFFu && pos >= 0 && pos < tile.contig_len;
+      const bool fast = act && shaped && nm16 != 0xFFFFu && pos >= 0 && pos < contig_len;
       const bool slow = act && !fast;
       // ---- keep_read (midas/run/snps.py:141-162): a fast read has SEQ, NM and a non-empty aligned part -------------------------
       MIDAS_MARK("filter");
       const int align_len = (int)sh.alen;
-      const int min_match = (kDebug & 512) ? 0 : s_tables[align_len < p.table_len ? align_len : 0];
-      const int min_align = (kDebug & 512) ? 0 : s_tables[p.table_len + (l < p.table_len ? l : 0)];
+      const int min_match = (kDebug & 512) ? 0 : s_tables[align_len < table_len ? align_len : 0];
+      const int min_align = (kDebug & 512) ? 0 : s_tables[table_len + (l < table_len ? l : 0)];
       const bool t_pid = align_len - nm < min_match;                                                       // pid < mapid
-      const bool t_drop = ((int)qsum < rq * l) | (mapq < p.mapq_min) | (align_len < min_align);             // readq, mapq, aln_cov
+      const bool t_drop = ((int)qsum < rq * l) | (mapq < mapq_min) | (align_len < min_align);             // readq, mapq, aln_cov
       const uint32_t err = (fast && !t_pid && t_noqual) ? (uint32_t)E_NO_QUAL : 0u;
       const bool keep = fast && !(t_pid | t_noqual | t_drop);
       const int rel = pos - tile_start;            // 0 <= pos < contig length: no wrap
@@ -624,16 +682,9 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
       MIDAS_MARK("counters");
       w_aligned += (uint32_t)__popcll(__ballot(owner));
       w_mapped += (uint32_t)__popcll(__ballot(owner && keep));
-      if (owner && err) atomicMin(p.err, ((unsigned long long)idx << 8) | err);
-      {                                        // the records of the phase after this one
-        const int kn = k0 + n_ph;
-        const bool over = xt && kn >= n_w;
-        Stream fs;
-        fs.rb = over ? xs.rb : st.rb; fs.n0 = over ? xs.n0 : st.n0; fs.total = over ? xs.total : st.total;
-        const int kf = over ? 0 : kn;
-        rawN = fetch_phase(fs, kf, phase_len((over ? wave_its(xs) : n_w) - kf));
-      }
+      rawN = fetch_phase(nf, nf_k, nf_len);    // the records of the phase after this one (nf: the stream they are in)
       MIDAS_MARK("slowgate");
+      if (owner && err) atomicMin(params_again()->err, ((unsigned long long)idx << 8) | err);      // (rare: a kept read without qualities)
       const unsigned long long slow_mask = __ballot(slow);
       if (slow_mask != 0ull) {
         for (int j = 0; j < n_ph; ++j) {
@@ -653,15 +704,19 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
       (void)pt0;
       MIDAS_MARK("settle");
       settle(rawX, nrX, b_n);                  // (the record of the next iteration has arrived: its bases are requested ...)
-      {                                        // ... then the record of the one after it
-        const int kf = k_it + 2;               // the wave's iteration (of this tile, or counted on into the next) to fetch for
-        const bool over = xt && kf >= n_w;
-        Stream fs;
-        fs.rb = over ? xs.rb : st.rb; fs.n0 = over ? xs.n0 : st.n0; fs.total = over ? xs.total : st.total;
-        const int fi = wave + (over ? kf - n_w : kf) * NWAVES;
-        rawX = fetch(fs, fi);
-        nrX = reads_in(fs, fi);
+      // ... then the record of the one after it (the wave's k_it + 2 nd of this tile, or counted on into the next tile's stream)
+      if constexpr (QUAD) {
+        const uint4 x = recs[f_rec < (uint32_t)f_end ? f_rec : 0u];
+        rawX.pos = x.x; rawX.l_nc = x.y; rawX.nmq = x.z; rawX.off = x.w;
+        nrX = f_rem <= 0 ? 0 : (f_rem < 16 ? f_rem : 16);
+        f_rec += (uint32_t)f_step;
+        f_rem -= f_step;
+      } else {
+        rawX = fetch(f, f_i);
+        nrX = reads_in(f, f_i);
+        f_i += NWAVES;
       }
+      f_left -= 1;
       if constexpr (J == 1) gather(rawN, ownN);      // (the next phase's records, requested an iteration ago, have arrived)
 #if MIDAS_SNPS_DEBUG_BITS & 256
       const unsigned long long pt1 = PROBE_NOW();
@@ -672,6 +727,7 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
 
       if (kDebug & 4) {          // (developer timing variant: the stream of loads only)
         asm volatile("" :: "v"(b_cur[0]), "v"(b_cur[NW - 1]), "v"(desc.d0));
+        cross_if_due();
         return;
       }
       // ---- the read's descriptor, from its owner -----------------------------------------------------------------------------
@@ -726,13 +782,23 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
 #if MIDAS_SNPS_DEBUG_BITS & 256
       pr_work += PROBE_NOW() - pt2;
 #endif
+      cross_if_due();
     };
     {
       using std::integral_constant;
       int k0 = 0;
       while (k0 < n_w) {
         const int n_ph = phase_len(n_w - k0);
-        open_phase(k0, n_ph);
+        // the phase after this one: the next of this tile, or -- behind the tile's last -- the first of the next tile's stream
+        Stream nf = st;
+        int nf_k = k0 + n_ph, nf_len = phase_len(n_w - nf_k);
+        if (xt && nf_k >= n_w) {
+          nf.rb = xs.rb; nf.n0 = xs.n0;
+          nf_k = 0;
+          nf_len = phase_len(wave_its(xs));
+          asm volatile("");
+        }
+        open_phase(k0, n_ph, nf, nf_k, nf_len);
         iteration(integral_constant<int, 0>{}, k0, bA, bB);
         if (n_ph > 1) {
           iteration(integral_constant<int, 1>{}, k0 + 1, bB, bA);
@@ -759,9 +825,12 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
 
     // the tile's reference letters: requested here, behind the stream loop (two registers less in it), they arrive while
     // the workgroup waits for its last wave and writes the counts out
+    MIDAS_MARK("refletters");
+    const ParamsAgain pe = params_again();
+    uint8_t* const out_allele = pe->out_allele;
     uint32_t refw[REF_IT];
-    if (p.out_allele) {
-      const uint8_t* ref = p.ref + tile.site_base;
+    if (out_allele) {
+      const uint8_t* ref = pe->ref + tile.site_base;
 #pragma unroll
       for (int it = 0; it < REF_IT; ++it) {
         const int i = 4 * (tid + it * kDirectBlock);
@@ -773,9 +842,10 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
       if (w_mapped) atomicAdd(&s_stats[MIDAS_STAT_MAPPED], (unsigned long long)w_mapped);
     }
     // ---- next tile ---------------------------------------------------------------------------------------------------------
+    MIDAS_MARK("nexttile");
     const int tn = wn;
-    const Tile ntile = load_tile(c_tiles, tn);
-    const Stream nst = load_stream(tn, cout);
+    const Tile ntile = load_tile((ConstWords)(size_t)pe->tiles, tn);
+    const Stream nst = load_stream(pe, tn, cout);
     const bool take = more && !in_chunk;          // the next tile opens the next item: draw the one after it
     const unsigned long long ps0 = PROBE_NOW();
     if (more && !xt) {   // (with xt the pipeline already holds the next tile's first iterations and its first phase's reads)
@@ -792,11 +862,42 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
     }
     const unsigned long long ps1 = PROBE_NOW();
     uint32_t ticket = 0;
-    if (dynamic && take && tid == 0) ticket = atomicAdd(&sched[32 * sched_group], 1u);
+    if (dynamic && take && tid == 0) ticket = atomicAdd(&pe->sched[32 * sched_group], 1u);
 
     // ---- emit the tile: counts[site][A,C,G,T] (and re-zero LDS), covered / total-depth partials ---------------------------
-    {
-      uint4* out = reinterpret_cast<uint4*>(p.out_counts) + ((kDebug & 8) ? 0 : tile.site_base);
+    MIDAS_MARK("writeout");
+    // (a full tile -- all but a contig's last: no row needs a bound, and the LDS reads of four rows are in flight before the first
+    // store waits for its own; the overhang sits in the rows below OV only)
+    constexpr bool kFullRows = TILE % kDirectBlock == 0 && OUT_IT % 4 == 0;
+    const bool full = kFullRows && tile_len == TILE && !(kDebug & (2 | 8));      // workgroup-uniform
+    if (full) {
+      uint4* const out = reinterpret_cast<uint4*>(pe->out_counts) + tile.site_base;
+      uint4* const lds4 = reinterpret_cast<uint4*>(lds);
+#pragma unroll
+      for (int r0 = 0; r0 < OUT_IT; r0 += 4) {
+        uint4 v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = lds4[tid + (r0 + r) * kDirectBlock];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int i = tid + (r0 + r) * kDirectBlock;
+          uint4 front = make_uint4(0u, 0u, 0u, 0u);
+          if ((r0 + r) * kDirectBlock < OV) {           // (a row the overhang reaches: what this tile's reads added behind it opens the next tile)
+            if (cout && i < OV) {
+              front = lds4[TILE + i];
+              lds4[TILE + i] = make_uint4(0u, 0u, 0u, 0u);
+            }
+          }
+          lds4[i] = front;
+          u32x4_a8 nv; nv.x = v[r].x; nv.y = v[r].y; nv.z = v[r].z; nv.w = v[r].w;
+          __builtin_nontemporal_store(nv, reinterpret_cast<u32x4_a8*>(out + i));
+          const uint32_t d = v[r].x + v[r].y + v[r].z + v[r].w;
+          acc_cov += d > 0u ? 1u : 0u;
+          acc_depth += d;
+        }
+      }
+    } else {
+      uint4* out = reinterpret_cast<uint4*>(pe->out_counts) + ((kDebug & 8) ? 0 : tile.site_base);
       uint4* lds4 = reinterpret_cast<uint4*>(lds);
       const int lim = (kDebug & 2) ? 0 : tile_len;
 #pragma unroll
@@ -818,9 +919,15 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         }
       }
     }
-    if (p.out_allele && !(kDebug & 2)) {
-      const uint8_t* ref = p.ref + tile.site_base;
-      uint8_t* al = p.out_allele + tile.site_base;
+    MIDAS_MARK("alleles");
+    if (out_allele && full && TILE % (4 * kDirectBlock) == 0) {      // (a full tile: every thread whole words)
+      uint8_t* al = out_allele + tile.site_base;
+#pragma unroll
+      for (int it = 0; it < REF_IT; ++it)
+        __builtin_nontemporal_store(upper4(refw[it]), reinterpret_cast<u32_a1*>(al + 4 * (tid + it * kDirectBlock)));
+    } else if (out_allele && !(kDebug & 2)) {
+      const uint8_t* ref = pe->ref + tile.site_base;
+      uint8_t* al = out_allele + tile.site_base;
 #pragma unroll
       for (int it = 0; it < REF_IT; ++it) {
         const int i = 4 * (tid + it * kDirectBlock);
@@ -835,6 +942,7 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         }
       }
     }
+    MIDAS_MARK("tiletail");
     if (dynamic && take && tid == 0) s_next_ticket = ticket;
     lds_barrier();       // tallies re-zeroed, this tile's s_stats additions done
 #if MIDAS_SNPS_DEBUG_BITS & 256
@@ -867,11 +975,12 @@ __global__ __launch_bounds__(kDirectBlock, kDirectWavesPerSimd) void pileup_dire
         int ts = tid;
         asm volatile("" : "+v"(ts));      // (formed here: hoisted, the address of this rare add holds two registers through every tile)
         const unsigned long long v = s_stats[ts];
-        if (v) atomicAdd(&p.stats[(size_t)tile.species * MIDAS_STATS + ts], v);
+        if (v) atomicAdd(&params_again()->stats[(size_t)tile.species * MIDAS_STATS + ts], v);
         s_stats[ts] = 0ull;
       }
       if (!more) {
         if (dynamic && tid == 0) {   // the last workgroup to leave rewinds the counters for the next launch
+          uint32_t* const sched = params_again()->sched;
           if (atomicAdd(&sched[32 * kSchedGroups], 1u) == gridDim.x - 1u) {
             for (int k = 0; k <= kSchedGroups; ++k) sched[32 * k] = 0u;
           }
@@ -927,6 +1036,17 @@ hipError_t launch_pileup_direct(const DirectParams& p, int lane_bases, hipStream
     } else {
       if (bq0) hipLaunchKernelGGL((pileup_direct_kernel<30, true, kDirectOverhangLong>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
       else hipLaunchKernelGGL((pileup_direct_kernel<30, false, kDirectOverhangLong>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
+    }
+  } else if (p.lanes_per_read == 4 && p.reads_per_wave == 16) {      // (four lanes per read: the lane geometry is static)
+    if (lane_bases == 38) {
+      if (bq0) hipLaunchKernelGGL((pileup_direct_kernel<38, true, kDirectOverhang, 4>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
+      else hipLaunchKernelGGL((pileup_direct_kernel<38, false, kDirectOverhang, 4>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
+    } else if (lane_bases == 32) {
+      if (bq0) hipLaunchKernelGGL((pileup_direct_kernel<32, true, kDirectOverhang, 4>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
+      else hipLaunchKernelGGL((pileup_direct_kernel<32, false, kDirectOverhang, 4>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
+    } else {
+      if (bq0) hipLaunchKernelGGL((pileup_direct_kernel<30, true, kDirectOverhang, 4>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
+      else hipLaunchKernelGGL((pileup_direct_kernel<30, false, kDirectOverhang, 4>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);
     }
   } else if (lane_bases == 38) {
     if (bq0) hipLaunchKernelGGL((pileup_direct_kernel<38, true>), dim3(grid), dim3(kDirectBlock), dyn_lds, stream, p);

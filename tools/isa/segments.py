@@ -3,18 +3,21 @@
 usage: python tools/isa/segments.py listing.s kernel-name-substring [first-mark]
 Walks the listing in layout order from the first occurrence of `first-mark` (default: settle) to the next one of the same
 name -- one body of the unrolled loop -- and prints, per segment, VALU by class (plain / slow = perm, sdwa, sad, dpp /
-cmp -> sgpr), SALU, LDS, VMEM and a wall-time estimate from tools/probes/isa_rate.hip's figures.  Straight-line layout: code
+cmp -> sgpr / lane = v_readlane_b32 and v_writelane_b32: scalars the register allocator keeps in the lanes of a VGPR), SALU, LDS,
+VMEM and a wall-time estimate from tools/probes/isa_rate.hip's figures.  Straight-line layout: code
 in side branches (slow path, partial lanes) is counted where it lies, so read the segments with the source next to them.
 """
 import re
 import sys
 
-NS = {"plain": 1.17, "slow": 1.88, "cmps": 2.5}
+NS = {"plain": 1.17, "slow": 1.88, "cmps": 2.5, "lane": 1.17}      # (a lane move issues as a plain VALU instruction)
 
 
 def klass(op, line):
     if not op.startswith("v_"):
         return None
+    if op.startswith(("v_readlane", "v_writelane")):
+        return "lane"
     if "sdwa" in op or "sdwa" in line or "dpp" in line or op.startswith("v_perm") or op.startswith("v_sad") or op.startswith("v_mul_lo") or op.startswith("v_mad_i64") or op.startswith("v_mad_u64"):
         if op.startswith("v_cmp"):
             return "cmps"
@@ -43,7 +46,7 @@ def main():
                 if seen == 2:
                     break
             if seen:
-                cur = {"name": name, "plain": 0, "slow": 0, "cmps": 0, "s": 0, "ds": 0, "vm": 0, "wait": 0}
+                cur = {"name": name, "plain": 0, "slow": 0, "cmps": 0, "lane": 0, "s": 0, "ds": 0, "vm": 0, "wait": 0}
                 segs.append(cur)
             continue
         if cur is None or not s or s.startswith(";") or s.startswith(".") or re.match(r"^\S+:$", s):
@@ -66,8 +69,8 @@ def main():
     for g in segs:
         ns = sum(g[k] * NS[k] for k in NS)
         tot += ns
-        print("%-10s plain %4d  slow %4d  cmp->s %3d | SALU %4d  LDS %3d  VMEM %2d  waits %2d | ~%6.1f ns" % (
-            g["name"], g["plain"], g["slow"], g["cmps"], g["s"], g["ds"], g["vm"], g["wait"], ns))
+        print("%-10s plain %4d  slow %4d  cmp->s %3d  lane %3d | SALU %4d  LDS %3d  VMEM %2d  waits %2d | ~%6.1f ns" % (
+            g["name"], g["plain"], g["slow"], g["cmps"], g["lane"], g["s"], g["ds"], g["vm"], g["wait"], ns))
     print("sum of VALU time ~%.1f ns (static, straight-line)" % tot)
 
 
