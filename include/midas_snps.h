@@ -488,6 +488,20 @@ int32_t midas_sam_decode_timing(const midas_snps_ctx* ctx, float* out_ms8);
 #define MIDAS_SAM_ORDER_FILE 1
 int32_t midas_sam_load_device_order(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam** out, int64_t* n_reads,
                                     int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar, char* err256);
+/* The SAM decode straight into the pileup kernel's own layout: what midas_bam_load_resident (below) is to midas_bam_load_device.
+ * The chunk loop, both passes and the coordinate sort are midas_sam_load_device's; the gather behind the sort writes every sorted
+ * record ONCE, as its 16-byte record and its [cigar][quality sum][one byte a base] payload run, straight from the columns pass 2
+ * accumulated in file order -- no sorted SEQ / QUAL / CIGAR column is built, the small columns and the offsets stay on the device,
+ * and only refID comes down.  The handle is in the state a streamed midas_bam_load_resident leaves: midas_bam_is_resident 1,
+ * midas_bam_columns entry 0 (refID, host) and NULL elsewhere, midas_bam_n_refs / _ref / _close as before,
+ * midas_snps_batch_create_resident and midas_bam_resident_to_columns take it unchanged (raw columns, when asked for, are cut out of
+ * the direct layout; the reads its bytes cannot give back exactly -- an IUPAC letter or '=', an A/C/G/T quality above 50, another
+ * base's above 51, QUAL '*' -- lie raw in a side buffer that pass 2's flags size exactly before the gather is launched).
+ * *sum_l_seq: the bases of all records.  Every field rule, message and status is midas_sam_load_device's (the first bad line in
+ * file order, 1-based), and so are its limits; besides, MIDAS_SNPS_ERR_UNSUPPORTED: more than 32 GiB of read payload (the
+ * record's offset is 32 bits of 8-byte units) -- decode with midas_sam_load_device instead.  midas_sam_decode_timing keeps its
+ * eight slots: "sort + gather" covers the new gather, "columns down" is refID alone.                                            */
+int32_t midas_sam_load_resident(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* sum_l_seq, char* err256);
 /* A handle of midas_bam_open_slice / _open_share whose ranges are loaded needs its file no more: the mapping is handed to a
  * thread that unmaps it (a page-table walk of 0.2 s for a 9 GB BAM) while the caller piles the records up; the columns / the
  * resident records stay.  midas_bam_load_ranges* on the handle afterwards is MIDAS_SNPS_ERR_INVALID_ARG.                       */

@@ -292,6 +292,7 @@ def load_library(build_if_missing: bool = True):
         'midas_sam_load_device': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_sam_decode_timing': (i32, [vp, vp]),
         'midas_sam_load_device_order': (i32, [C.c_char_p, vp, i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
+        'midas_sam_load_resident': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_bam_release_file': (None, [vp]),
         'midas_bam_load_resident': (i32, [C.c_char_p, vp, C.POINTER(vp), C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
         'midas_bam_load_ranges_resident': (i32, [vp, vp, i32, vp, vp, C.POINTER(i64), C.POINTER(i64), C.c_char_p]),
@@ -502,7 +503,7 @@ def species_assign(indptr, hit_species, hit_aln, reads, aln, py_state=None, np_s
 
 
 # the SAM decode (run_midas.py snps --sam, genes --sam): bound above like the rest, listed by themselves
-SAM_SYMBOLS = ['midas_sam_load_device', 'midas_sam_decode_timing', 'midas_sam_load_device_order']
+SAM_SYMBOLS = ['midas_sam_load_device', 'midas_sam_decode_timing', 'midas_sam_load_device_order', 'midas_sam_load_resident']
 SAM_ORDERS = {'coordinate': 0, 'file': 1}        # MIDAS_SAM_ORDER_*
 GENES_BAM_PHASES = ('upload', 'inflate + crc', 'walk + stitch + offsets', 'facts kernel', 'filter + sort + sums', 'download')
 GENES_BAM_STATS = ('records', 'dropped', 'blocks', 'inflated_bytes', 'chunks', 'chunks_again')
@@ -836,19 +837,37 @@ def open_bam_device(path: str, ctx) -> BamDeviceHandle:
     return BamDeviceHandle(lib, h, path)
 
 
-def read_sam(path: str, ctx=None, order: str = 'coordinate'):
+def read_sam(path: str, ctx=None, order: str = 'coordinate', resident: bool = False):
     """Decode the aligner's SAM text on the device of `ctx` (midas_sam_load_device) -> (ref_names, ref_lengths, refid[int32],
     ReadsSoA), the tuple read_bam(..., payload_on_device=True) returns: the records with a reference, coordinate-sorted there
     (equal keys in file order), the small columns as views of the decoder's host buffers, SEQ / QUAL / CIGAR as device
     addresses (`device`).  order='file': the records stay in the order of their lines (midas_sam_load_device_order; what
-    Context.genes_count_device wants).  There is no host decoder: without a device context this raises ERR_INVALID_ARG."""
+    Context.genes_count_device wants).  resident=True (coordinate order only): the sorted records are written once, in the pileup
+    kernel's own layout, and every column stays on the device (midas_sam_load_resident) -> (ref_names, ref_lengths, refid,
+    ResidentReads), exactly as read_bam(..., resident=True); more payload than that layout addresses: the columns' way.
+    There is no host decoder: without a device context this raises ERR_INVALID_ARG."""
     if ctx is None or not getattr(ctx, 'inflates', False):
         raise MidasSnpsError(ERR_INVALID_ARG, "read_sam needs a device context (the SAM text is parsed and sorted on the GPU)")
     if order not in SAM_ORDERS:
         raise MidasSnpsError(ERR_INVALID_ARG, "read_sam: order is 'coordinate' or 'file', not %r" % (order,))
+    if resident and order != 'coordinate':
+        raise MidasSnpsError(ERR_INVALID_ARG, "read_sam: resident records are coordinate-sorted, order=%r is not for them" % (order,))
     lib = load_library()
     h = C.c_void_p()
     err = C.create_string_buffer(256)
+    if resident:
+        n, total = C.c_int64(), C.c_int64()
+        st = lib.midas_sam_load_resident(path.encode(), ctx._h, C.byref(h), C.byref(n), C.byref(total), err)
+        if st == ERR_UNSUPPORTED:
+            return read_sam(path, ctx, order)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode())
+        owner = _BamOwner(lib, h)
+        names, lens = _bam_refs(lib, h)
+        ptrs = (C.c_void_p * 12)()
+        lib.midas_bam_columns(h, ptrs)
+        refid = np.asarray(_Column(owner, ptrs[0] or 0, int(n.value), np.int32))
+        return names, lens, refid, ResidentReads(lib, h, owner, int(n.value), int(total.value))
     n, sb, qb, nc = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
     if order == 'coordinate':
         st = lib.midas_sam_load_device(path.encode(), ctx._h, C.byref(h), C.byref(n), C.byref(sb), C.byref(qb), C.byref(nc), err)

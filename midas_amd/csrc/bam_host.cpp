@@ -362,6 +362,11 @@ void adopt_device_result(midas_bam* b, const midas::DeviceDecodeResult& res, int
     b->dev_payload[0] = res.dev_seq; b->dev_payload[1] = res.dev_qual; b->dev_payload[2] = res.dev_cigar;
   }
 }
+int32_t* midas::bam_alloc_host_refid(midas_bam* b, int64_t n_records) {
+  midas::HostColumns c{};
+  return alloc_host_refid(b, n_records, &c) ? c.refid : nullptr;
+}
+void midas::bam_resident_ready(midas_bam* b, const midas::DeviceDecodeResult& res) { adopt_device_result(b, res, 2); }
 bool alloc_host_columns(midas_bam* b, int64_t n, midas::HostColumns* c, bool keep_refid) {
   const size_t n1 = n > 0 ? (size_t)n : 1;
   if ((!keep_refid && !b->refid.resize(n1)) || !b->pos.resize(n1) || !b->nm.resize(n1) || !b->l_seq.resize(n1) || !b->mapq.resize(n1) ||

@@ -247,15 +247,7 @@ __global__ __launch_bounds__(256) void bam_direct_kernel(BamDirectParams p) {
     const uint8_t* qual = seq + (l + 1u) / 2u;
     const bool exc = dense::encode<32>(dst + nc4, (uint32_t)(room - nc4), seq, qual, l, (int)sl, p.side);
     if (exc && p.side_copy) dense::side_copy<32>(p.side, (unsigned long long)(p.read_base + i), seq, qual, l, (int)sl);
-    if (sl == 0u) {
-      const int32_t nm = p.nm[i];
-      DirectRec rec;
-      rec.pos = p.pos[i];
-      rec.l_nc = (l > 0xFFFFu ? 0xFFFFu : l) | ((n_cig > 0xFFFFu ? 0xFFFFu : n_cig) << 16);     // (beyond the fast paths' limits: the batch takes the long path)
-      rec.nmq = (nm < 0 ? (uint32_t)kNmAbsent : (nm > kMaxField16 ? (uint32_t)kMaxField16 : (uint32_t)nm)) | ((uint32_t)r[13] << 16);
-      rec.off8 = (uint32_t)u0;
-      p.rec[i] = rec;
-    }
+    if (sl == 0u) p.rec[i] = direct_rec(p.pos[i], l, n_cig, p.nm[i], r[13], (uint32_t)u0);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {       // the sentinel: where the payload ends
     DirectRec rec;

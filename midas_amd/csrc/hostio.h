@@ -144,6 +144,11 @@ int32_t bam_load_ranges_on_device(midas_bam* bam, const DeviceDecoder* dec, int3
 // from there on the handle answers like one of midas_bam_load_device.  nullptr: out of memory.
 midas_bam* bam_new_columns_handle(const char* path, const std::vector<std::string>& ref_names, const std::vector<int64_t>& ref_lens);
 void bam_columns_ready(midas_bam* b, int64_t n_records);
+// midas_sam_load_resident (sam_scan.hip): the same handle in the state a streamed midas_bam_load_resident leaves instead -- refID
+// for n records in host memory (nullptr: out of memory), then everything `res` names on the device (res->resident, its totals,
+// dev_owner freed with the handle)
+int32_t* bam_alloc_host_refid(midas_bam* b, int64_t n_records);
+void bam_resident_ready(midas_bam* b, const DeviceDecodeResult& res);
 
 // Members whose DEFLATE streams exist already (the device's row coder): frame them (this library's gzip header with the
 // member's size and row count, CRC-32, ISIZE) and write them in order behind the header line's member.

@@ -128,6 +128,17 @@ __host__ __device__ inline uint32_t direct_payload_units(uint32_t l_seq, uint32_
   return (4u * n_cigar + 4u + l_seq + 7u) >> 3;
 }
 constexpr unsigned long long kMaxDirectPayloadUnits = 0xFFFFFFFFull;    // 32 GiB per batch
+// the record a producer writes for a read whose payload starts at unit off8 (bam_walk.hip bam_direct_kernel, sam_scan.hip
+// sam_direct_kernel): an l_seq or n_cigar beyond 16 bits is stored as 0xFFFF -- beyond the fast paths' limits, the batch takes the
+// long path, which reads the columns -- a negative NM is "no tag", one above kMaxField16 is stored as kMaxField16
+__host__ __device__ inline DirectRec direct_rec(int32_t pos, uint32_t l_seq, uint32_t n_cigar, int32_t nm, uint32_t mapq, uint32_t off8) {
+  DirectRec rec;
+  rec.pos = pos;
+  rec.l_nc = (l_seq > 0xFFFFu ? 0xFFFFu : l_seq) | ((n_cigar > 0xFFFFu ? 0xFFFFu : n_cigar) << 16);
+  rec.nmq = (nm < 0 ? (uint32_t)kNmAbsent : (nm > kMaxField16 ? (uint32_t)kMaxField16 : (uint32_t)nm)) | ((mapq & 0xFFu) << 16);
+  rec.off8 = off8;
+  return rec;
+}
 
 // The base byte: A, C, G, T (SEQ nibbles 1, 2, 4, 8) -> ((min(q, 50) + 13) << 2) | code with code A=0 C=1 G=2 T=3 (>= 52);
 // any other nibble (N, IUPAC, '=') -> min(q, 51) (<= 51: never counts).  Zero is "no base" (what the kernel's masks write).

@@ -17,6 +17,14 @@
 // MIDAS_SAM_ORDER_FILE (midas_sam_load_device_order; run_midas.py genes, whose fp64 sums follow the order of the aligner's
 // lines): no sort and no gather -- the columns pass 2 accumulated, chunk after chunk, ARE the result: the small ones are
 // copied down, the three payload arrays are handed to the handle as they are.
+// midas_sam_load_resident: the same passes and the same sort, but the gather writes the pileup kernel's own layout (layout.h
+// DirectRec + payload) -- what a streamed midas_bam_load_resident leaves -- and nothing else:
+//   sizes    per sorted record also its direct_payload_units and, from the byte pass 2 wrote for it ("exceptional": dense_exact
+//            fails for a base), what it reserves in the side buffer; the library's scan over each
+//   direct   HALF a wave a sorted record (sam_direct_kernel, shaped like bam_walk.hip's bam_direct_kernel): the CIGAR words copied,
+//            SEQ + QUAL through dense::encode, the exceptional reads' raw bytes through dense::side_copy, the 16-byte record, the
+//            small columns and the int64 offsets in sorted order, all to device arrays; no sorted SEQ / QUAL / CIGAR column exists.
+//            The side buffer is sized exactly before the launch; only refID comes down.
 // Everything a kernel reads of the text lies inside its line; everything it writes lies inside room the host sized from the
 // scans' totals before the launch.
 #include <hip/hip_runtime.h>
@@ -38,8 +46,10 @@
 
 #include "../../include/midas_snps.h"
 #include "ctx_internal.h"
+#include "dense_bases.h"
 #include "hostio.h"
 #include "kernels.h"
+#include "sam_resident_plan.h"
 #include "text_rows.h"
 
 namespace midas {
@@ -126,6 +136,7 @@ struct SamCols {
   int32_t *refid, *pos, *nm, *l_seq; uint32_t* n_cigar; uint8_t* mapq; uint16_t* flag;
   long long *seq_off, *qual_off, *cigar_off;
   uint8_t *seq4, *qual; uint32_t* cigar;
+  uint8_t* exc;                  // (nullable; the resident decode asks for it) 1: dense_exact fails for a base of the record
 };
 
 // ---- pass 1: one thread a line ------------------------------------------------------------------------------------------------
@@ -286,6 +297,13 @@ __global__ __launch_bounds__(256) void sam_payload_kernel(SamP p, SamCols c, lon
     c.seq4[so + j] = (uint8_t)(hi << 4 | lo);
   }
   for (uint32_t j = lane; j < l; j += 64) c.qual[qo + j] = qual_at == kNoQual ? (uint8_t)0xFF : (uint8_t)(t[qual_at + j] - 33);
+  if (c.exc) {       // is the read exceptional (layout.h dense_exact fails for a base; a QUAL '*' is 0xFF on every base)?  (wave-uniform)
+    bool exc = false;
+    for (uint32_t j = lane; j < l; j += 64)
+      exc = exc || !dense_exact(seq_code((uint8_t)t[seq_at + j]), qual_at == kNoQual ? 0xFFu : (uint32_t)(uint8_t)(t[qual_at + j] - 33));
+    const bool any = __ballot(exc) != 0ull;
+    if (lane == 0) c.exc[i] = any ? (uint8_t)1 : (uint8_t)0;
+  }
   if (nc) {
     const uint32_t cig_at = p.cig_at[r], cig_len = p.cig_len[r];
     const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
@@ -357,6 +375,64 @@ __global__ __launch_bounds__(256) void sam_gather_kernel(SamGatherP g) {
   for (uint32_t j = lane; j < nc; j += 64) g.out.cigar[co + j] = g.in.cigar[fc + j];
 }
 
+// ---- the resident form: sorted sizes, then the direct layout straight from the file-order columns --------------------------------
+// sam_sorted_sizes_kernel's sibling: also the record's 8-byte units in the direct layout and what it reserves in the side buffer
+// (an entry, units of raw SEQ + QUAL) when pass 2 flagged it; n + 1 entries each (the last: zeros)
+struct SamResidentSizes { uint32_t *seq, *qual, *cigar, *unit, *side_entries, *side_units; };
+__global__ __launch_bounds__(256) void sam_resident_sizes_kernel(const uint32_t* perm, const int32_t* l_seq, const uint32_t* n_cigar, const uint8_t* exc,
+                                                                 long long n, SamResidentSizes sz) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i > n) return;
+  uint32_t l = 0, nc = 0, e = 0, units = 0;
+  if (i < n) { const uint32_t s = perm[i]; l = (uint32_t)l_seq[s]; nc = n_cigar[s]; e = exc[s]; units = direct_payload_units(l, nc); }
+  sz.seq[i] = (l + 1u) >> 1; sz.qual[i] = l; sz.cigar[i] = nc; sz.unit[i] = units;
+  sz.side_entries[i] = sam_side_entries(e); sz.side_units[i] = sam_side_units(l, e);
+}
+struct SamDirectP {
+  const uint32_t* perm; long long n;
+  SamCols in;                       // file order
+  const uint32_t *at_seq, *at_qual, *at_cigar, *at_unit;       // [n + 1] scanned sizes, sorted order
+  // sorted, all on the device: the records (n + 1: the sentinel), their payload, the small columns, the offsets (n + 1)
+  DirectRec* rec; uint8_t* payload;
+  int32_t *refid, *pos, *nm, *l_seq; uint8_t* mapq; uint16_t* flag;
+  long long *seq_off, *qual_off, *cigar_off, *unit_off;
+  DenseSide* side;                  // room for every flagged read (sized from the scans before the launch)
+};
+// HALF a wavefront per sorted record, as bam_direct_kernel: the record's CIGAR words to the 8-byte unit the scan gave it, its
+// 4-bit SEQ + QUAL as the sum word and one byte a base behind them (dense_bases.h), an exceptional read's raw bytes into the side
+// buffer, and by the half's first lane the 16-byte record, the small columns and the offsets.
+typedef unsigned long long u64_a4 __attribute__((aligned(4)));
+__global__ __launch_bounds__(256) void sam_direct_kernel(SamDirectP p) {
+  const uint32_t lane = threadIdx.x & 63u, sub = lane >> 5, sl = lane & 31u;
+  const long long slot = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + sub, n_slots = (long long)gridDim.x * 8;
+  for (long long i = slot; i < p.n; i += n_slots) {
+    const uint32_t s = p.perm[i];
+    const uint32_t l = (uint32_t)p.in.l_seq[s], n_cig = p.in.n_cigar[s];
+    const unsigned long long u0 = p.at_unit[i], room = ((unsigned long long)p.at_unit[i + 1] - u0) << 3;
+    uint8_t* dst = p.payload + (u0 << 3);
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(p.in.cigar + p.in.cigar_off[s]);
+    const uint32_t nc4 = 4u * n_cig;
+    for (uint32_t k = sl * 8u; k + 8u <= nc4; k += 256u) *reinterpret_cast<unsigned long long*>(dst + k) = *reinterpret_cast<const u64_a4*>(src + k);
+    if (sl == 0u && (n_cig & 1u)) *reinterpret_cast<uint32_t*>(dst + nc4 - 4u) = *reinterpret_cast<const uint32_t*>(src + nc4 - 4u);
+    const uint8_t* seq = p.in.seq4 + p.in.seq_off[s];
+    const uint8_t* qual = p.in.qual + p.in.qual_off[s];
+    const bool exc = dense::encode<32>(dst + nc4, (uint32_t)(room - nc4), seq, qual, l, (int)sl, p.side);
+    if (exc) dense::side_copy<32>(p.side, (unsigned long long)i, seq, qual, l, (int)sl);
+    if (sl == 0u) {
+      const int32_t nm = p.in.nm[s], pos = p.in.pos[s];
+      const uint32_t mapq = p.in.mapq[s];
+      p.rec[i] = direct_rec(pos, l, n_cig, nm, mapq, (uint32_t)u0);
+      p.refid[i] = p.in.refid[s]; p.pos[i] = pos; p.nm[i] = nm; p.l_seq[i] = (int32_t)l; p.mapq[i] = (uint8_t)mapq; p.flag[i] = p.in.flag[s];
+      p.seq_off[i] = p.at_seq[i]; p.qual_off[i] = p.at_qual[i]; p.cigar_off[i] = p.at_cigar[i]; p.unit_off[i] = (long long)u0;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {       // the sentinel: where the payload ends; the offsets' last entries
+    const long long n = p.n;
+    p.rec[n] = direct_rec(0, 0u, 0u, 0, 0u, p.at_unit[n]);
+    p.seq_off[n] = p.at_seq[n]; p.qual_off[n] = p.at_qual[n]; p.cigar_off[n] = p.at_cigar[n]; p.unit_off[n] = p.at_unit[n];
+  }
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 struct SamFile {
   const char* base = nullptr;
@@ -386,6 +462,7 @@ struct DevGrow {
     cap = want;
     return hipSuccess;
   }
+  void drop() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
 void device_free(void* p) { if (p) (void)hipFree(p); }
@@ -466,10 +543,12 @@ void sam_payload_free(void* o) {
   delete w;
 }
 
-int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
+// resident (coordinate order only): the handle of midas_sam_load_resident instead of the columns
+int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, bool resident, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
                  int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
   if (!ctx || !path || !out || (order != MIDAS_SAM_ORDER_COORDINATE && order != MIDAS_SAM_ORDER_FILE)) return MIDAS_SNPS_ERR_INVALID_ARG;
   const bool file_order = order == MIDAS_SAM_ORDER_FILE;
+  if (resident && file_order) return MIDAS_SNPS_ERR_INVALID_ARG;
   *out = nullptr;
   if (err256) err256[0] = 0;
   using clock = std::chrono::steady_clock;
@@ -564,6 +643,7 @@ int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam
 
   DevGrow g_text, g_counts, g_scratch, g_ends, g_line;      // the chunk: text, newline counts, scan sums, line ends, per-line arrays
   DevGrow g_refid, g_pos, g_nm, g_lseq, g_ncig, g_mapq, g_flag, g_soff, g_qoff, g_coff, g_seq, g_qual, g_cigar;   // the records so far
+  DevGrow g_exc;                                                                                                    // (resident: their "exceptional" bytes)
   unsigned long long* d_bad = nullptr;
   SAM_TRY(dev.get(&d_bad, 8));
   SAM_TRY(hipMemsetAsync(d_bad, 0xFF, 8, st));
@@ -658,6 +738,8 @@ int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam
     cols.flag = static_cast<uint16_t*>(g_flag.p); cols.seq_off = static_cast<long long*>(g_soff.p); cols.qual_off = static_cast<long long*>(g_qoff.p);
     cols.cigar_off = static_cast<long long*>(g_coff.p); cols.seq4 = static_cast<uint8_t*>(g_seq.p); cols.qual = static_cast<uint8_t*>(g_qual.p);
     cols.cigar = static_cast<uint32_t*>(g_cigar.p);
+    if (resident) SAM_TRY(g_exc.need(n2, (size_t)n, st));
+    cols.exc = static_cast<uint8_t*>(g_exc.p);
     if (tot[0]) {
       hipLaunchKernelGGL(sam_payload_kernel, dim3(nblocks(lines, 4)), dim3(256), 0, st, p, cols, n, tot_seq, tot_qual, tot_cigar);
       SAM_TRY(hipGetLastError());
@@ -665,7 +747,7 @@ int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam
     }
     lap(5);
     n += tot[0]; tot_seq += tot[1]; tot_qual += tot[2]; tot_cigar += tot[3];
-    if (n > 2000000000ll) return sam_err(err256, MIDAS_SNPS_ERR_UNSUPPORTED, "%s: more than 2 * 10^9 records (%lld): decode it in parts", path, n);
+    if (n > kSamMaxRecords) return sam_err(err256, MIDAS_SNPS_ERR_UNSUPPORTED, "%s: more than 2 * 10^9 records (%lld): decode it in parts", path, n);
     lines_before += lines;
     at += (long long)last_end + 1;           // (a final line without '\n': one past the text, and the loop ends)
   }
@@ -702,29 +784,19 @@ int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam
     *out = b.release();
     return MIDAS_SNPS_OK;
   }
-  if (tot_qual >= (1ll << 32))
+  if (tot_qual >= kSamMaxQualBytes)
     return sam_err(err256, MIDAS_SNPS_ERR_UNSUPPORTED, "%s: %lld bytes of QUAL: the SAM decode's sorted offsets address 4 GiB of them", path, tot_qual);
-  if (tot_cigar >= (1ll << 32))
+  if (tot_cigar >= kSamMaxCigarOps)
     return sam_err(err256, MIDAS_SNPS_ERR_UNSUPPORTED, "%s: %lld CIGAR ops: the SAM decode's sorted offsets address 2^32 of them", path, tot_cigar);
 
   // ---- sort + gather ----------------------------------------------------------------------------------------------------------------
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t at_q = up((size_t)tot_seq + 64), at_c = at_q + up((size_t)tot_qual + 64), pay_bytes = at_c + up((size_t)tot_cigar * 4 + 64);
-  struct Own { void* p = nullptr; ~Own() { if (p) (void)hipFree(p); } } own;
-  SAM_TRY(hipMalloc(&own.p, pay_bytes));
-  uint8_t* pay = static_cast<uint8_t*>(own.p);
-  SAM_TRY(hipMemsetAsync(pay + tot_seq, 0, 64, st));
-  SAM_TRY(hipMemsetAsync(pay + at_q + tot_qual, 0, 64, st));
-  SAM_TRY(hipMemsetAsync(pay + at_c + (size_t)tot_cigar * 4, 0, 64, st));
-  std::unique_ptr<midas_bam, void (*)(midas_bam*)> b(bam_new_columns_handle(path, names, lens), midas_bam_close);
-  HostColumns hc{};
-  if (!b || !bam_alloc_host_columns(b.get(), n, &hc)) return sam_err(err256, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "%s: out of host memory for %lld records", path, n);
   const size_t n1 = (size_t)n + 1;
-  if (n > 0) {
-    uint32_t *ka = nullptr, *va = nullptr, *kb = nullptr, *vb = nullptr, *scratch = nullptr, *sz = nullptr;
+  // the n > 0 records' order: (pos + 1, index), then (refID, index) through the stable sort -> *perm; *scratch also holds a scan of n + 1
+  auto sort_records = [&](uint32_t** perm, uint32_t** scratch_out) -> int32_t {
+    uint32_t *ka = nullptr, *va = nullptr, *kb = nullptr, *vb = nullptr, *scratch = nullptr;
     SAM_TRY(dev.get(&ka, (size_t)n * 4)); SAM_TRY(dev.get(&va, (size_t)n * 4)); SAM_TRY(dev.get(&kb, (size_t)n * 4)); SAM_TRY(dev.get(&vb, (size_t)n * 4));
     SAM_TRY(dev.get(&scratch, std::max(sort_scratch_words(n), scan_scratch_words((long long)n1)) * 4));
-    SAM_TRY(dev.get(&sz, 6 * n1 * 4));
     hipLaunchKernelGGL(sam_key_pos_kernel, dim3(nblocks(n, 256)), dim3(256), 0, st, cols.pos, n, ka, va);
     SAM_TRY(hipGetLastError());
     uint32_t *ks = nullptr, *vs = nullptr;
@@ -738,6 +810,116 @@ int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam
       SAM_TRY(hipGetLastError());
       SAM_TRY(launch_sort_pairs_u32(ks, vs, ko, vo, n, bits, scratch, st, &ks, &vs));
     }
+    *perm = vs;
+    *scratch_out = scratch;
+    return MIDAS_SNPS_OK;
+  };
+  if (resident) {
+    // ---- the direct layout from the file-order columns: sizes, scans, the result's room, ONE gather ----------------------------------
+    uint32_t *perm = nullptr, *scratch = nullptr, *sz = nullptr;
+    uint32_t down3[3] = {0, 0, 0};        // the scans' totals: payload units (their low 32 bits), side entries, side units
+    if (n > 0) {
+      const int32_t sst = sort_records(&perm, &scratch);
+      if (sst != MIDAS_SNPS_OK) return sst;
+      SAM_TRY(dev.get(&sz, 12 * n1 * 4));
+      const SamResidentSizes zs{sz, sz + n1, sz + 2 * n1, sz + 3 * n1, sz + 4 * n1, sz + 5 * n1};
+      hipLaunchKernelGGL(sam_resident_sizes_kernel, dim3(nblocks((long long)n1, 256)), dim3(256), 0, st, perm, cols.l_seq, cols.n_cigar, cols.exc, n, zs);
+      SAM_TRY(hipGetLastError());
+      for (int k = 0; k < 6; ++k) SAM_TRY(launch_scan_u32(sz + (size_t)k * n1, sz + (size_t)(6 + k) * n1, (long long)n1, scratch, st));
+      // (the three totals lie n1 words apart: one strided copy)
+      SAM_TRY(hipMemcpy2DAsync(down3, 4, sz + (size_t)9 * n1 + (size_t)n, n1 * 4, 4, 3, hipMemcpyDeviceToHost, st));
+      SAM_TRY(hipStreamSynchronize(st));
+    }
+    const unsigned long long units = sam_units_total(sam_units_range(n, tot_qual, tot_cigar), down3[0]);
+    if (units == kSamUnitsUnknown || sam_side_units_bound(n, tot_qual) > kDenseSideMaxField)
+      return sam_err(err256, MIDAS_SNPS_ERR_HIP, "%s: the direct layout's size does not follow from its %lld records' columns", path, n);
+    if (!sam_payload_fits(units))
+      return sam_err(err256, MIDAS_SNPS_ERR_UNSUPPORTED, "%s: %lld bytes of read payload exceed the 32 GiB the direct layout addresses", path, (long long)(units * 8ull));
+    const SamSideSize side_size = sam_side_size(down3[1], down3[2]);
+    // the result: the records' arrays in one allocation (rec, refid, pos, nm, l_seq, mapq, flag, four offset columns), the payload, the side buffer
+    size_t col_at[11], col_bytes = 0;
+    for (int k = 0; k < 11; ++k) { col_at[k] = col_bytes; col_bytes += up((n1 + 1) * (k == 0 ? 16 : (k <= 4 ? 4 : (k == 5 ? 1 : (k == 6 ? 2 : 8))))); }
+    std::unique_ptr<SamPayloadOwner, void (*)(void*)> res_own(new (std::nothrow) SamPayloadOwner{{nullptr, nullptr, nullptr}}, sam_payload_free);
+    if (!res_own) return sam_err(err256, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "%s: out of host memory for %lld records", path, n);
+    SAM_TRY(hipMalloc(&res_own->p[0], col_bytes));
+    SAM_TRY(hipMalloc(&res_own->p[1], (size_t)units * 8 + 64));
+    SAM_TRY(hipMalloc(&res_own->p[2], (size_t)side_size.alloc_bytes));
+    uint8_t* cb = static_cast<uint8_t*>(res_own->p[0]);
+    uint8_t* pay = static_cast<uint8_t*>(res_own->p[1]);
+    DenseSide* d_side = static_cast<DenseSide*>(res_own->p[2]);
+    DenseSide h_side{};
+    h_side.cap_entries = side_size.cap_entries; h_side.cap_bytes = side_size.cap_bytes;
+    SAM_TRY(hipMemcpyAsync(d_side, &h_side, sizeof h_side, hipMemcpyHostToDevice, st));
+    SAM_TRY(hipMemsetAsync(pay + (size_t)units * 8, 0, 64, st));      // (a lane's 16-byte loads may overhang the last read)
+    std::unique_ptr<midas_bam, void (*)(midas_bam*)> b(bam_new_columns_handle(path, names, lens), midas_bam_close);
+    int32_t* h_refid = b ? bam_alloc_host_refid(b.get(), n) : nullptr;
+    if (!h_refid) return sam_err(err256, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "%s: out of host memory for %lld records", path, n);
+    DeviceDecodeResult res;
+    ResidentReads& rr = res.resident;
+    rr.rec = cb + col_at[0]; rr.payload = pay;
+    rr.refid = reinterpret_cast<int32_t*>(cb + col_at[1]); rr.pos = reinterpret_cast<int32_t*>(cb + col_at[2]); rr.nm = reinterpret_cast<int32_t*>(cb + col_at[3]);
+    rr.l_seq = reinterpret_cast<int32_t*>(cb + col_at[4]); rr.mapq = cb + col_at[5]; rr.flag = reinterpret_cast<uint16_t*>(cb + col_at[6]);
+    rr.seq_off = reinterpret_cast<int64_t*>(cb + col_at[7]); rr.qual_off = reinterpret_cast<int64_t*>(cb + col_at[8]);
+    rr.cigar_off = reinterpret_cast<int64_t*>(cb + col_at[9]); rr.unit_off = reinterpret_cast<int64_t*>(cb + col_at[10]);
+    rr.stream = nullptr; rr.rec_off = nullptr;       // (no text is kept: raw columns come out of the direct layout)
+    rr.payload_units = (int64_t)units;
+    rr.side = d_side;
+    if (n > 0) {
+      SamDirectP g{};
+      g.perm = perm; g.n = n; g.in = cols;
+      g.at_seq = sz + 6 * n1; g.at_qual = sz + 7 * n1; g.at_cigar = sz + 8 * n1; g.at_unit = sz + 9 * n1;
+      g.rec = static_cast<DirectRec*>(rr.rec); g.payload = pay;
+      g.refid = rr.refid; g.pos = rr.pos; g.nm = rr.nm; g.l_seq = rr.l_seq; g.mapq = rr.mapq; g.flag = rr.flag;
+      g.seq_off = reinterpret_cast<long long*>(rr.seq_off); g.qual_off = reinterpret_cast<long long*>(rr.qual_off);
+      g.cigar_off = reinterpret_cast<long long*>(rr.cigar_off); g.unit_off = reinterpret_cast<long long*>(rr.unit_off);
+      g.side = d_side;
+      const long long cap = (long long)ctx->prop.multiProcessorCount * 16;
+      const long long blocks = std::max(1ll, std::min(((long long)n + 7) / 8, cap));
+      hipLaunchKernelGGL(sam_direct_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g);
+      SAM_TRY(hipGetLastError());
+      SAM_TRY(hipMemcpyAsync(&h_side, d_side, sizeof h_side, hipMemcpyDeviceToHost, st));
+      SAM_TRY(hipStreamSynchronize(st));
+      g_seq.drop(); g_qual.drop(); g_cigar.drop();       // the file-order payload is gathered: it is not resident beyond this point
+      lap(6);
+      // (sized from pass 2's flags for exactly the reads that reserve: no room is an error of this code, not a reason to retry)
+      if ((h_side.flags & kDenseSideOverflow) || (h_side.bump >> kDenseSideEntryShift) != side_size.cap_entries ||
+          ((h_side.bump & kDenseSideMaxField) << 3) != side_size.cap_bytes)
+        return sam_err(err256, MIDAS_SNPS_ERR_HIP, "%s: kDenseSideOverflow: the side buffer sized for %lld exceptional reads did not hold them", path,
+                       (long long)side_size.cap_entries);
+      SAM_TRY(hipMemcpy(h_refid, rr.refid, (size_t)n * 4, hipMemcpyDeviceToHost));
+    } else {
+      SAM_TRY(hipMemsetAsync(cb, 0, col_bytes, st));
+      SAM_TRY(hipStreamSynchronize(st));
+    }
+    lap(7);
+    rr.dense_flags = h_side.flags;
+    res.n_records = n; res.seq_bytes = tot_seq; res.qual_bytes = tot_qual; res.n_cigar = tot_cigar;
+    res.dev_owner = res_own.release();
+    res.dev_free = sam_payload_free;
+    bam_resident_ready(b.get(), res);
+    if (n_reads) *n_reads = n;
+    if (seq_bytes) *seq_bytes = tot_seq;
+    if (qual_bytes) *qual_bytes = tot_qual;
+    if (n_cigar) *n_cigar = tot_cigar;
+    for (int k = 0; k < 8; ++k) ctx->sam_ms[k] = ms[k];
+    *out = b.release();
+    return MIDAS_SNPS_OK;
+  }
+  const size_t at_q = up((size_t)tot_seq + 64), at_c = at_q + up((size_t)tot_qual + 64), pay_bytes = at_c + up((size_t)tot_cigar * 4 + 64);
+  struct Own { void* p = nullptr; ~Own() { if (p) (void)hipFree(p); } } own;
+  SAM_TRY(hipMalloc(&own.p, pay_bytes));
+  uint8_t* pay = static_cast<uint8_t*>(own.p);
+  SAM_TRY(hipMemsetAsync(pay + tot_seq, 0, 64, st));
+  SAM_TRY(hipMemsetAsync(pay + at_q + tot_qual, 0, 64, st));
+  SAM_TRY(hipMemsetAsync(pay + at_c + (size_t)tot_cigar * 4, 0, 64, st));
+  std::unique_ptr<midas_bam, void (*)(midas_bam*)> b(bam_new_columns_handle(path, names, lens), midas_bam_close);
+  HostColumns hc{};
+  if (!b || !bam_alloc_host_columns(b.get(), n, &hc)) return sam_err(err256, MIDAS_SNPS_ERR_OUT_OF_MEMORY, "%s: out of host memory for %lld records", path, n);
+  if (n > 0) {
+    uint32_t *vs = nullptr, *scratch = nullptr, *sz = nullptr;
+    const int32_t sst = sort_records(&vs, &scratch);
+    if (sst != MIDAS_SNPS_OK) return sst;
+    SAM_TRY(dev.get(&sz, 6 * n1 * 4));
     uint32_t *sz_seq = sz, *sz_qual = sz + n1, *sz_cigar = sz + 2 * n1, *at_seq = sz + 3 * n1, *at_qual = sz + 4 * n1, *at_cigar = sz + 5 * n1;
     hipLaunchKernelGGL(sam_sorted_sizes_kernel, dim3(nblocks((long long)n1, 256)), dim3(256), 0, st, vs, cols.l_seq, cols.n_cigar, n, sz_seq, sz_qual, sz_cigar);
     SAM_TRY(hipGetLastError());
@@ -761,6 +943,7 @@ int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam
     hipLaunchKernelGGL(sam_gather_kernel, dim3(nblocks((long long)n1, 4)), dim3(256), 0, st, g);
     SAM_TRY(hipGetLastError());
     SAM_TRY(hipStreamSynchronize(st));
+    g_seq.drop(); g_qual.drop(); g_cigar.drop();       // the file-order payload is gathered: it is not resident beyond this point
     lap(6);
     // the small columns come down in one copy
     std::vector<uint8_t> down;
@@ -791,10 +974,14 @@ int32_t sam_load(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam
 
 extern "C" int32_t midas_sam_load_device(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* seq_bytes,
                                          int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
-  return sam_load(path, ctx, MIDAS_SAM_ORDER_COORDINATE, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
+  return sam_load(path, ctx, MIDAS_SAM_ORDER_COORDINATE, false, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
+}
+
+extern "C" int32_t midas_sam_load_resident(const char* path, midas_snps_ctx* ctx, midas_bam** out, int64_t* n_reads, int64_t* sum_l_seq, char* err256) {
+  return sam_load(path, ctx, MIDAS_SAM_ORDER_COORDINATE, true, out, n_reads, nullptr, sum_l_seq, nullptr, err256);      // (QUAL holds one byte per base)
 }
 
 extern "C" int32_t midas_sam_load_device_order(const char* path, midas_snps_ctx* ctx, int32_t order, midas_bam** out, int64_t* n_reads,
                                                int64_t* seq_bytes, int64_t* qual_bytes, int64_t* n_cigar, char* err256) {
-  return sam_load(path, ctx, order, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
+  return sam_load(path, ctx, order, false, out, n_reads, seq_bytes, qual_bytes, n_cigar, err256);
 }

@@ -400,6 +400,22 @@ def _alignment_path(args):
     return bampath, False
 
 
+SAM_RESIDENT_DEFAULT = False      # (its gain lies inside the column form's min-max spread, profiles/sam_resident.txt: opt-in -- DESIGN 14)
+
+
+def _sam_resident():
+    """MIDAS_SNPS_SAM_RESIDENT, read at the call: 1 -- the SAM is decoded straight into the pileup kernel's layout
+    (abi.read_sam(..., resident=True)), 0 -- into columns; unset: SAM_RESIDENT_DEFAULT."""
+    want = os.environ.get('MIDAS_SNPS_SAM_RESIDENT', '')
+    return want == '1' if want in ('0', '1') else SAM_RESIDENT_DEFAULT
+
+
+def _read_sam(path, ctx):
+    """(decoded, the form taken: 'resident' or 'columns' -- a payload beyond the resident layout's 32 GiB falls back to columns)"""
+    decoded = abi.read_sam(path, ctx, resident=_sam_resident())
+    return decoded, 'resident' if isinstance(decoded[3], abi.ResidentReads) else 'columns'
+
+
 _ERR_TEXT = {
     abi.ERR_READ_NO_SEQ: "an alignment has no SEQ (the reference raises TypeError in keep_read)",
     abi.ERR_READ_NO_NM: "an alignment has no NM tag (the reference raises KeyError: 'NM' in keep_read)",
@@ -756,7 +772,7 @@ def species_pileup(args, species_id, contigs):
     order, span = _whole(_species_contig_order([species_id], contigs), contigs)
     try:
         with abi.Context(int(os.environ.get("LOCAL_RANK", "0"))) as ctx:
-            decoded = abi.read_sam(bampath, ctx) if is_sam else \
+            decoded = _read_sam(bampath, ctx)[0] if is_sam else \
                 abi.read_bam(bampath, ctx if _inflate_on_device(args, ctx, bampath, 1) else None)
             stats = _pileup_contigs(args, [species_id], order[species_id], order, {}, decoded, ctx, span, contigs)
     except abi.MidasSnpsError as e:
@@ -1065,8 +1081,8 @@ def _count_alleles(args, species, contigs, ctx):
                     if opened is not None:
                         opened.close()
                     # (text from the aligner: parsed and coordinate-sorted on the device, SEQ / QUAL / CIGAR stay there)
-                    decoded = abi.read_sam(bampath, ctx)
-                    _lap("  SAM decoded and sorted on the device", t_in)
+                    decoded, form = _read_sam(bampath, ctx)
+                    _lap("  SAM decoded and sorted on the device (%s)" % form, t_in)
                 elif opened is not None and inflater is not None and ws == 1 and 0 <= opened.first < opened.total:
                     # (the file was mapped and its block table walked while the device context came up)
                     refid, rr = opened.load_ranges([(opened.first, opened.total)], inflater, resident=True)
