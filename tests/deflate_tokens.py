@@ -21,17 +21,19 @@ class DeflateError(ValueError):
 class Block:
     """One block of a stream: kind 0 stored, 1 fixed, 2 dynamic; tokens[first_token:end_token] are its own; for a dynamic block the
     code lengths as sent (cl_lens by symbol 0..18, ll_lens [HLIT + 257], d_lens [HDIST + 1]) and the code length symbols
-    that spelt them (cl_symbols: 0..15 a length, 16 / 17 / 18 the repeats)."""
+    that spelt them (cl_symbols: 0..15 a length, 16 / 17 / 18 the repeats; cl_runs: how many lengths each of them stood for)."""
 
     def __init__(self, kind, final):
         self.kind, self.final = kind, final
         self.first_token = self.end_token = 0
-        self.cl_lens = self.ll_lens = self.d_lens = self.cl_symbols = None
+        self.cl_lens = self.ll_lens = self.d_lens = self.cl_symbols = self.cl_runs = None
 
 
 class Parsed:
-    def __init__(self, text, tokens, blocks, n_bytes):
-        self.text, self.tokens, self.blocks, self.n_bytes = text, tokens, blocks, n_bytes
+    """length_codes: per match, in order, the length code 0..28 that spelt it (258 can be code 28, or code 27 with 31 extra)"""
+
+    def __init__(self, text, tokens, blocks, n_bytes, length_codes=None):
+        self.text, self.tokens, self.blocks, self.n_bytes, self.length_codes = text, tokens, blocks, n_bytes, length_codes
 
     @property
     def matches(self):
@@ -113,7 +115,7 @@ def parse(raw):
         fill -= l
         return e >> 4
 
-    out, tokens, blocks = bytearray(), [], []
+    out, tokens, blocks, length_codes = bytearray(), [], [], []
     while True:
         final, kind = bits(1), bits(2)
         blk = Block(kind, bool(final))
@@ -140,9 +142,9 @@ def parse(raw):
                 for i in range(hclen):
                     cl_lens[CL_ORDER[i]] = bits(3)
                 cl_table, cl_max = _table(cl_lens, "code length code")
-                lens, syms = [], []
+                lens, syms, runs = [], [], []
                 while len(lens) < hlit + hdist:
-                    s = symbol(cl_table, cl_max, "code length code")
+                    s, before = symbol(cl_table, cl_max, "code length code"), len(lens)
                     syms.append(s)
                     if s < 16:
                         lens.append(s)
@@ -152,12 +154,13 @@ def parse(raw):
                         lens += [lens[-1]] * (3 + bits(2))
                     else:
                         lens += [0] * (3 + bits(3) if s == 17 else 11 + bits(7))
+                    runs.append(len(lens) - before)
                 if len(lens) != hlit + hdist:
                     raise DeflateError("dynamic block: a repeat runs past the code lengths")
                 ll_lens, d_lens = lens[:hlit], lens[hlit:]
                 if ll_lens[256] == 0:
                     raise DeflateError("dynamic block: no end-of-block code")
-                blk.cl_lens, blk.ll_lens, blk.d_lens, blk.cl_symbols = cl_lens, ll_lens, d_lens, syms
+                blk.cl_lens, blk.ll_lens, blk.d_lens, blk.cl_symbols, blk.cl_runs = cl_lens, ll_lens, d_lens, syms, runs
             ll_table, ll_max = _table(ll_lens, "literal/length code")
             d_table, d_max = _table(d_lens, "distance code")
             while True:
@@ -178,6 +181,7 @@ def parse(raw):
                     if dist > len(out):
                         raise DeflateError("a match reaches %d bytes back in a text of %d" % (dist, len(out)))
                     tokens.append((length, dist))
+                    length_codes.append(s - 257)
                     at = len(out) - dist
                     if dist >= length:
                         out += out[at:at + length]
@@ -190,7 +194,7 @@ def parse(raw):
         blocks.append(blk)
         if final:
             break
-    return Parsed(bytes(out), tokens, blocks, pos - fill // 8)
+    return Parsed(bytes(out), tokens, blocks, pos - fill // 8, length_codes)
 
 
 def length_code(length):
