@@ -1014,6 +1014,37 @@ int32_t midas_sites_write_markers(const char* path, const midas_sites_tables* t,
 int32_t midas_sites_write_pairs(const char* path, const midas_sites_tables* t, int32_t n_samples, const int32_t* sample_row,
                                 const int64_t* both, char* err1024);
 
+/* ---- snp_trees.py: consensus distances between all pairs of samples, and a neighbour-joining tree over them --------------------
+ * midas_sites_consensus_pairs walks the two matrices as midas_sites_scan does under MIDAS_SITES_SEQ (same text, masks, cell
+ * parsers, row groups, site decisions, --max_sites rule and place of a bad row in out_stats16[4..6]); fparams5 as there (snp_maf
+ * unused); iparams8 = site_depth, max_sites (-1: all), flags (MIDAS_SITES_MASK_ONLY alone is looked at), 0, group_rows,
+ * chunk_bytes, pair_blocks (as midas_sites_track_markers), 0.  The retained sites of a row group become two bit planes [sample]
+ * [64 sites a word]: `called` where call_consensus.py writes a letter (the sample is kept at the site and its depth is not 0),
+ * `minor` where that letter is the minor allele (freq >= 0.5).  out_both / out_diff [n_samples][n_samples], filled for i <= j:
+ * sites called in both samples, and those of them where one sample has the minor and the other the major allele.  Integer sums
+ * held on the device across row groups: they depend on neither group_rows nor pair_blocks.  out_stats16: [0] sites read, [1]
+ * sites retained, [2] / [3] cells converted by the host, [7] row groups, [8] (sample pairs with i <= j) x words of the planes,
+ * [9] group_rows, [10] chunk_bytes, [11] / [12] the most word runs a pair launch had and the most staging steps a run had, [13]
+ * the most samples whose pair matrices fit the free device memory (more is MIDAS_SNPS_ERR_OUT_OF_MEMORY).  out_ms8 (nullable):
+ * upload + index (host clock), index, parse, site, planes, pairs, -, download (device events).
+ * midas_nj_tree: neighbour joining over any symmetric matrix dist [n][n] of finite doubles (host memory), n >= 3, resident on the
+ * device from the first step to the last.  Slots 0..n-1 are active and r = n; while r > 3, every operation one rounded fp64
+ * operation as written:  R[a] = the sum of D[a][b] over the active b != a in ascending slot order, one add each from 0.0;
+ * q = (((double)(r - 2) * D[a][b]) - R[a]) - R[b] for the active a < b; the pair with the least q is joined, compared by value,
+ * ties to the smaller a, then the smaller b; la = 0.5 * D[a][b] + (R[a] - R[b]) / (2.0 * (double)(r - 2)), lb = D[a][b] - la
+ * (negative lengths stay as they come); D[a][k] = D[k][a] = 0.5 * ((D[a][k] + D[b][k]) - D[a][b]) for the active k != a, b;
+ * slot a holds the new node, slot b goes inactive, out_join[n - r] = (a, b), out_len[n - r] = (la, lb), r -= 1.  The last three
+ * slots a < b < c: out_last = (a, b, c), out_last_len = 0.5 * ((D[a][b] + D[a][c]) - D[b][c]), 0.5 * ((D[a][b] + D[b][c]) -
+ * D[a][c]), 0.5 * ((D[a][c] + D[b][c]) - D[a][b]).  The chosen pair never leaves the device between the launches of a step and
+ * the host synchronises once, after the last step.  out_stats16: [0] the largest n the free device memory holds (more is
+ * MIDAS_SNPS_ERR_OUT_OF_MEMORY), [1] steps, [2] kernel launches.  out_ms8 (nullable): upload, the steps, download.              */
+int32_t midas_sites_consensus_pairs(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                    int64_t n_sites_max, const uint8_t* site_mask, int32_t n_samples, const int32_t* sample_col,
+                                    const double* mean_depth, const double* fparams5, const int64_t* iparams8, int64_t* out_both,
+                                    int64_t* out_diff, int64_t* out_stats16, float* out_ms8);
+int32_t midas_nj_tree(midas_snps_ctx* ctx, int32_t n, const double* dist, int32_t* out_join, double* out_len, int32_t* out_last,
+                      double* out_last_len, int64_t* out_stats16, float* out_ms8);
+
 /* ---- compare_genes.py: gene-content distances between all pairs of samples of one `merge_midas.py genes` directory ----------
  * midas_genes_matrix_*: one genes_<kind>.txt mapped and left as text.  counts: out4 = sample columns of the header, data rows
  *   (lines after the header; a last line without '\n' counts), bytes of those rows, bytes of the sample ids.  columns: out4 =

@@ -377,6 +377,8 @@ def load_library(build_if_missing: bool = True):
         'midas_sites_scan': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15),
         'midas_sites_id_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, vp, i32] + [vp] * 6),
         'midas_sites_track_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, i32] + [vp] * 6),
+        'midas_sites_consensus_pairs': (i32, [vp, vp, i64, vp, i64, i64, vp, i32] + [vp] * 8),
+        'midas_nj_tree': (i32, [vp, i32] + [vp] * 7),
         'midas_sites_write_markers': (i32, [C.c_char_p, vp, i64, vp, C.c_char_p]),
         'midas_sites_write_pairs': (i32, [C.c_char_p, vp, i32, vp, vp, C.c_char_p]),
         'midas_genes_matrix_open': (i32, [C.c_char_p, C.POINTER(vp), C.c_char_p]),
@@ -447,7 +449,9 @@ EXPORTED_SYMBOLS = [
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
                  'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_id_markers', 'midas_sites_track_markers',
-                 'midas_sites_write_markers', 'midas_sites_write_pairs']
+                 'midas_sites_write_markers', 'midas_sites_write_pairs', 'midas_sites_consensus_pairs']
+# snp_trees.py (neighbour joining over the consensus distances): bound above like the rest, listed by itself
+TREE_SYMBOLS = ['midas_nj_tree']
 
 
 # run_species.py (the m8 classify step and the serial assignment): bound above like the rest, listed by themselves
@@ -1992,6 +1996,62 @@ class Context:
                                         [which], sample_col, float(min_freq), [int(min_reads), 0, group_rows, chunk_bytes, 0, int(pair_blocks)], both)
         out.update(both=both, n_matched=int(stats[1]), word_pairs=int(stats[8]), pair_runs=int(stats[11]), pair_steps=int(stats[12]))
         return out
+
+    def sites_consensus_pairs(self, freq_text, depth_text, site_mask, sample_col, mean_depth, site_depth: int, site_ratio: float,
+                              allele_support: float, site_prev: float, site_maf: float, max_sites: int = -1, flags: int = 0,
+                              group_rows: int = 0, chunk_bytes: int = 0, pair_blocks: int = 0):
+        """midas_sites_consensus_pairs(): the sites call_consensus.py retains (sites_scan's arguments under SITES_SEQ; of flags
+        SITES_MASK_ONLY alone counts), every (site, sample) call as two bit planes, and the pair counts over them.  -> dict(both /
+        diff int64 [S, S], filled for i <= j: sites called in both samples / those where the two calls are the minor and the major
+        allele; n_sites, n_kept, side_freq, side_depth, groups, word_pairs, pair_runs, pair_steps, sample_limit, ms [8]).  A
+        malformed row raises MidasSnpsError with .bad as sites_scan; more samples than the pair matrices fit the free device
+        memory for raises it with .limit = that number.  pair_blocks as sites_track_markers: the output does not depend on it."""
+        ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
+        dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
+        mask = np.ascontiguousarray(site_mask, dtype=np.uint8)
+        cols = np.ascontiguousarray(sample_col, dtype=np.int32)
+        mean = np.ascontiguousarray(mean_depth, dtype=np.float64)
+        S = int(cols.shape[0])
+        assert mean.shape[0] == S and S >= 1
+        fp = np.array([site_ratio, allele_support, site_prev, site_maf, 0.0], np.float64)
+        ip = np.array([site_depth, max_sites, flags & SITES_MASK_ONLY, 0, group_rows, chunk_bytes, pair_blocks, 0], np.int64)
+        both, diff = np.zeros((S, S), np.int64), np.zeros((S, S), np.int64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_sites_consensus_pairs(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], int(mask.shape[0]), p(mask), S, p(cols),
+                                                   p(mean), p(fp), p(ip), p(both), p(diff), p(stats), p(ms))
+        if st != 0:
+            try:
+                self._check(st)
+            except MidasSnpsError as e:
+                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
+                e.limit = int(stats[13]) if st == ERR_OUT_OF_MEMORY and stats[13] < S else None
+                raise
+        return dict(both=both, diff=diff, n_sites=int(stats[0]), n_kept=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]),
+                    groups=int(stats[7]), word_pairs=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]),
+                    pair_runs=int(stats[11]), pair_steps=int(stats[12]), sample_limit=int(stats[13]), ms=ms.tolist())
+
+    def nj_tree(self, dist):
+        """midas_nj_tree(): neighbour joining over a symmetric matrix of finite doubles [n, n], n >= 3, on the device; the
+        arithmetic is the contract in include/midas_snps.h.  -> dict(join int32 [n - 3, 2] = the slots (a, b) joined at every
+        step (slot a holds the new node), len f64 [n - 3, 2] = their branch lengths, last int32 [3] / last_len f64 [3] = the three
+        slots left and their lengths, sample_limit, ms [8] = upload, steps, download).  A matrix the free device memory does not
+        hold raises MidasSnpsError with .limit = the largest n it holds."""
+        d = np.ascontiguousarray(dist, dtype=np.float64)
+        n = int(d.shape[0])
+        assert d.shape == (n, n)
+        join, length = np.zeros((max(n - 3, 0), 2), np.int32), np.zeros((max(n - 3, 0), 2), np.float64)
+        last, last_len = np.zeros(3, np.int32), np.zeros(3, np.float64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        st = self._lib.midas_nj_tree(self._h, n, p(d), p(join), p(length), p(last), p(last_len), p(stats), p(ms))
+        if st != 0:
+            try:
+                self._check(st)
+            except MidasSnpsError as e:
+                e.limit = int(stats[0]) if st == ERR_OUT_OF_MEMORY and 0 < stats[0] < n else None
+                raise
+        return dict(join=join, len=length, last=last, last_len=last_len, sample_limit=int(stats[0]), ms=ms.tolist())
 
     def genes_compare(self, text, n_rows: int, n_samples: int, n_columns: int, dtype: str = 'presabs', distance: str = 'jaccard',
                       cutoff: float = 0.35, group_rows: int = 0, chunk_bytes: int = 0, pair_blocks: int = 0, dump: bool = False):

@@ -154,6 +154,57 @@ def check_consensus_args(args):
     _common_checks(args)
 
 
+TREE_OPTIONS = [
+    (['--dist'], dict(metavar='PATH', type=str, help="also write the table of pairwise distances here:\nsample1, sample2, sites, mismatches, distance")),
+]
+HIDDEN_DEVICE_OPTIONS = [(['--group_rows'], dict(type=int, default=0, help=argparse.SUPPRESS))]
+NEWICK_SPECIAL = "()[]':;,"
+
+
+def trees_arguments(argv=None):
+    """snp_trees.py: the sample and site options of call_consensus.py under their names and defaults, --dist, the hidden
+    --group_rows.  --out is the Newick file."""
+    parser = _parser('snp_trees.py',
+                     "A core-genome tree of the samples of one species: the consensus allele of every sample at the retained\n"
+                     "sites (as call_consensus.py calls it), the share of differing sites between every two samples, and a\n"
+                     "neighbour-joining tree over these distances, in Newick format.  Run `merge_midas.py snps` first.",
+                     "examples:\n"
+                     "  snp_trees.py OUT/species_1 --out tree.nwk --dist pairs.txt --site_maf 0.01 --site_depth 5 --site_prev 0.90 \\\n"
+                     "      --sample_depth 10 --sample_cov 0.40 --site_ratio 5.0\n"
+                     "  snp_trees.py OUT/species_1 --out tree.nwk --exclude_samples s7,s9 --max_sites 10000",
+                     [("Tree options", TREE_OPTIONS), ("Sample filters", SAMPLE_OPTIONS), ("Site filters", SITE_OPTIONS),
+                      ("Device", HIDDEN_DEVICE_OPTIONS)])
+    return vars(parser.parse_args(argv))
+
+
+def check_trees_args(args):
+    if not os.path.isdir(args['indir']):
+        _exit("Specified input directory '%s' does not exist" % args['indir'])
+    if args['site_depth'] < 1:
+        _exit("--site_depth must be >=1")
+    _common_checks(args)
+
+
+def check_tree_samples(sample_ids):
+    """A tree has at least three leaves, and a leaf is written as it is: no Newick quoting."""
+    if len(sample_ids) < 3:
+        _exit("a tree needs at least 3 samples; %d selected" % len(sample_ids))
+    for sample_id in sample_ids:
+        if any(c.isspace() or c in NEWICK_SPECIAL for c in sample_id):
+            _exit("the sample id '%s' contains whitespace or one of %s, which a Newick label cannot hold" % (sample_id, NEWICK_SPECIAL))
+
+
+def print_trees_args(args):
+    rows = ["Command: %s" % ' '.join(sys.argv), "Script: snp_trees.py", "Input directory: %s" % args['indir'], "Output file: %s" % args['out'],
+            "Distance table: %s" % args['dist']]
+    for title, names in (("Sample filters:", ['sample_depth', 'fract_cov', 'max_samples', 'keep_samples', 'exclude_samples']),
+                         ("Site filters:", ['site_list', 'site_depth', 'site_prev', 'site_maf', 'site_ratio', 'allele_support', 'locus_type',
+                                            'site_type', 'max_sites'])):
+        rows.append(title)
+        rows.extend("  %s: %s" % (name, args[name]) for name in names)
+    sys.stdout.write('\n'.join(rows) + '\n')
+
+
 STRAIN_COMMANDS = ['id_markers', 'track_markers']
 STRAIN_USAGE = ['', 'Usage: strain_tracking.py <command> [options]', '',
                 'Note: use strain_tracking.py <command> -h to view usage for a specific command', '', 'Commands:',
