@@ -954,6 +954,11 @@ int32_t midas_sites_parse_cell(int32_t kind, const char* text, int64_t n, void* 
  * A cell is float() / int() of its text; the device converts plain decimals itself and hands every other cell to the host's
  * exact parser.  A row with too few columns or a cell that is no number, among the rows the reference would read, is
  * MIDAS_SNPS_ERR_BAD_LAYOUT with out_stats16[4..6] = matrix (1 freq, 2 depth), 0-based data row, sample (-1: short row).
+ * So is a site whose pooled frequency the reference cannot form: [4] = 3, a frequency that is not finite under
+ * MIDAS_SITES_ROUND (round() raises; [6] the first such sample, kept or not), or [4] = 6, kept samples whose depths sum to 0
+ * under MIDAS_SITES_WEIGHT (a division by zero; [6] = -1).  The earliest row in file order is reported, a row's cells before
+ * its site, and no site behind the row that fills max_sites (the one row the reference still reads has its cells checked,
+ * whichever row group it falls in; max_sites 0 reads the first row's cells and nothing else).
  * MIDAS_SITES_SUMS: per chain (sample s, or the pool under MIDAS_SITES_POOLED) and gene (MIDAS_SITES_PER_GENE; else one) at
  *   chain * genes + gene: out_pi = the sum of 2 f (1 - f) in site order exactly as `+=` forms it, out_snps, out_sites,
  *   out_depth.  MIDAS_SITES_SEQ: out_seq[s * capacity + k] = '-', minor or major allele of the k-th retained site.

@@ -1891,7 +1891,9 @@ class Context:
         and snps_depth.txt (uint8 arrays, header line excluded).  site_mask [N] uint8; sample_col / mean_depth [S].  -> dict
         (n_sites, n_kept, side_freq, side_depth, groups, no_gene, ms [8]; with SITES_SUMS pi f64, snps / sites / depth i64
         [chains, genes]; with SITES_SEQ seq uint8 [S, n_kept]; with dump: freq f64 / depthv i64 [S, n_sites], keep uint8 and
-        pooled f64 [n_sites]; with dump_keep: keep alone).  A malformed row raises MidasSnpsError with .bad = (matrix 1|2, data row, sample or -1)."""
+        pooled f64 [n_sites]; with dump_keep: keep alone).  A malformed row raises MidasSnpsError with .bad = (matrix 1|2, data row, sample or -1);
+        a site the reference raises on, with .bad = (3, data row, sample): a frequency that is not finite under SITES_ROUND, or
+        (6, data row, -1): kept samples whose depths sum to 0 under SITES_WEIGHT."""
         ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
         dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
         mask = np.ascontiguousarray(site_mask, dtype=np.uint8)
@@ -1915,7 +1917,7 @@ class Context:
         if flags & SITES_SUMS:
             out.update(pi=np.zeros((chains, G), np.float64), snps=np.zeros((chains, G), np.int64), sites=np.zeros((chains, G), np.int64),
                        depth=np.zeros((chains, G), np.int64))
-        seq = np.empty((S, cap), np.uint8) if flags & SITES_SEQ else None
+        seq = np.empty((S, max(cap, 1)), np.uint8) if flags & SITES_SEQ else None       # (max_sites 0: still a buffer to point at)
         if dump:
             out.update(freq=np.zeros((S, N), np.float64), depthv=np.zeros((S, N), np.int64), keep=np.zeros(N, np.uint8),
                        pooled=np.zeros(N, np.float64))

@@ -94,9 +94,14 @@ def exit_bad_row(tables, order, e):
     bad = getattr(e, 'bad', None)
     if not bad:
         sys.exit("\nError: %s\n" % e.message)
-    name = 'snps_freq.txt' if bad[0] == 1 else 'snps_depth.txt'
-    what = "the row has fewer sample columns than the samples in use" if bad[2] < 0 else \
-        "sample %s: the cell is not %s" % (order[bad[2]].id, 'a number' if bad[0] == 1 else 'an integer')
+    name = 'snps_freq.txt' if bad[0] in (1, 3) else 'snps_depth.txt'
+    if bad[0] == 3:         # (round() of nan or inf: ValueError / OverflowError in the reference)
+        what = "sample %s: the frequency is not a finite number, so --consensus cannot round it" % order[bad[2]].id
+    elif bad[0] == 6:       # (maf / depth: ZeroDivisionError in the reference)
+        what = "the depths of the samples kept at the site sum to 0, so --weight_by_depth has no frequency for it"
+    else:
+        what = "the row has fewer sample columns than the samples in use" if bad[2] < 0 else \
+            "sample %s: the cell is not %s" % (order[bad[2]].id, 'a number' if bad[0] == 1 else 'an integer')
     sys.exit("\nError: %s, line %d: %s\n" % (os.path.join(tables.dir, name), bad[1] + 2, what))
 
 

@@ -11,7 +11,9 @@
 //            in before the site kernel runs.  Values land sample-major, [sample][row]
 //   site     one thread a row: GenomicSite.flag_samples, call_consensus, summary_stats, filter, in snps_summary.txt order.
 //            The unweighted pooled frequency is numpy's pairwise add-reduce (blocks of 128, eight partial sums) over the
-//            kept values, consumed in order; the weighted one is a left-to-right sum
+//            kept values, consumed in order; the weighted one is a left-to-right sum.  Where the reference raises instead
+//            (round() of a frequency that is not finite, a weighted mean over depths that sum to 0) the site is reported, and
+//            the earliest such row in file order ends the call as a malformed cell does
 //   order    --max_sites: exclusive scan of the keep flags, a site stays while fewer than max_sites were kept before it
 //   sums     one wave a chain (a sample, or the pool): 64 rows loaded coalesced, then folded in lane order -- the fp64 sum
 //            is the sequential one, bit for bit; per-gene chains switch accumulators where the gene index changes.
@@ -184,7 +186,12 @@ struct SiteP {
   int weight, round_freq, mask_only;
   uint32_t* keep;              // [g] the site's keep decision
   double* pooled;              // [g]
+  unsigned long long* err;     // min over (row << 32 | (sample + 1) << 3 | reason); nullptr: neither flag that can raise is set
 };
+
+// why a site's pooled frequency cannot be formed (the reference raises there): round() of a frequency that is not finite
+// (MIDAS_SITES_ROUND), the weighted mean over kept samples whose depths sum to 0 (MIDAS_SITES_WEIGHT)
+constexpr uint32_t kSiteNonFinite = 1, kSiteZeroDepth = 4;
 
 // the kept frequencies of one site, in sample order
 struct KeptIter {
@@ -196,7 +203,7 @@ struct KeptIter {
     while (!(cell[(long long)s * stride] & 1)) ++s;
     const double f = fv[(long long)s * stride];
     ++s;
-    return round_freq ? rint(f) : f;
+    return round_freq ? rint(f) + 0.0 : f;      // (float(round(f)) is never -0.0)
   }
 };
 
@@ -256,10 +263,12 @@ __global__ __launch_bounds__(256) void ss_site_kernel(SiteP p) {
   if (r >= p.g) return;
   long long count = 0, dsum = 0;
   double msum = 0.0;
+  unsigned long long why = 0;                   // the first sample whose frequency round() refuses, kept or not
   for (int s = 0; s < p.S; ++s) {
     const long long at = (long long)s * p.stride + r;
     const long long d = p.dv[at];
     const double f = p.fv[at];
+    if (p.round_freq && why == 0 && !isfinite(f)) why = ((unsigned long long)(s + 1) << 3) | kSiteNonFinite;
     bool keep = true;
     if (d < p.site_depth) keep = false;
     if (__ddiv_rn((double)d, p.mean_depth[s]) > p.site_ratio) keep = false;
@@ -270,7 +279,7 @@ __global__ __launch_bounds__(256) void ss_site_kernel(SiteP p) {
     if (keep) {
       ++count;
       if (p.weight) {
-        const double f2 = p.round_freq ? rint(f) : f;
+        const double f2 = p.round_freq ? rint(f) + 0.0 : f;
         dsum += d;
         msum += (double)d * f2;
       }
@@ -279,7 +288,8 @@ __global__ __launch_bounds__(256) void ss_site_kernel(SiteP p) {
   double pooled = 0.0;
   if (count > 0) {
     if (p.weight) {
-      pooled = __ddiv_rn(msum, (double)dsum);
+      if (dsum == 0) { if (why == 0) why = kSiteZeroDepth; }
+      else pooled = __ddiv_rn(msum, (double)dsum);
     } else {
       KeptIter it{p.fv + r, p.cell + r, p.stride, 0, p.round_freq};
       pooled = __ddiv_rn(pairwise_sum(it, count), (double)count);
@@ -291,6 +301,7 @@ __global__ __launch_bounds__(256) void ss_site_kernel(SiteP p) {
     if (p.site_prev != 0.0 && prev < (1e-6 > p.site_prev ? 1e-6 : p.site_prev)) k = false;
     if (p.site_maf != 0.0 && pooled < p.site_maf) k = false;
   }
+  if (why != 0 && p.err) atomicMin(p.err, ((unsigned long long)r << 32) | why);
   p.keep[r] = k ? 1u : 0u;
   p.pooled[r] = pooled;
 }
@@ -343,7 +354,7 @@ __global__ __launch_bounds__(64) void ss_sums_kernel(SumP p) {
       on = p.pooled ? true : (p.cell[at] & 1) != 0;
       if (on) {
         double f = p.pooled ? p.fv[r] : p.fv[at];
-        if (!p.pooled && p.round_freq) f = rint(f);
+        if (!p.pooled && p.round_freq) f = rint(f) + 0.0;
         term = (2.0 * f) * (1.0 - f);
         double m = f;                           // min(f, 1 - f) as Python's min
         if (1.0 - f < m) m = 1.0 - f;
@@ -351,6 +362,10 @@ __global__ __launch_bounds__(64) void ss_sums_kernel(SumP p) {
         d = p.pooled ? 0 : p.dv[at];
         if (p.per_gene) gi = p.gene[r];
       }
+    }
+    if (p.per_gene && chain == 0) {             // kept sites without a gene id, whichever samples are kept there
+      const unsigned long long lost = __ballot(r < p.g && p.final_keep[r] && p.gene[r] < 0);
+      if (lane == 0 && lost) atomicAdd(p.no_gene, (unsigned long long)__popcll((long long)lost));
     }
     unsigned long long live = __ballot(on);
     const int tlo = __double2loint(term), thi = __double2hiint(term);
@@ -365,10 +380,7 @@ __global__ __launch_bounds__(64) void ss_sums_kernel(SumP p) {
           cur = gk;
           if (cur >= 0) { pi = p.pi[base + cur]; snps = p.snps[base + cur]; sites = p.sites[base + cur]; depth = p.depth[base + cur]; }
         }
-        if (cur < 0) {
-          if (lane == 0 && chain == 0) atomicAdd(p.no_gene, 1ull);
-          continue;
-        }
+        if (cur < 0) continue;
       }
       pi += t;
       snps += __builtin_amdgcn_readlane(snp, k);
@@ -798,7 +810,8 @@ struct RowGroups {
   // a short row or a cell that is no number among the first read_rows rows of the group: the error, with its place in stats
   int32_t check_rows(long long read_rows) {
     static const char* kFile[2] = {"freq", "depth"};
-    for (int m = 0; m < 2; ++m) {
+    // (the reference converts row by row, sample by sample, the frequency before the depth: the smaller key first)
+    for (int m = bad[1] < bad[0] ? 1 : 0, k = 0; k < 2; ++k, m ^= 1) {
       if (bad[m] == kNoBad || (long long)(bad[m] >> 32) >= read_rows) continue;
       const long long row = base + (long long)(bad[m] >> 32);
       const long long slot = (long long)(bad[m] & 0xFFFFFFFFull) - 1;
@@ -829,7 +842,38 @@ struct RowGroups {
     base += g;
     for (int m = 0; m < 2; ++m) ck[m].at = std::min(ck[m].bytes, ck[m].at + (long long)end_at[m] + 1);
   }
+
+  // max_sites was filled by the last row of the group just done with: the one row more that the reference converts (and then
+  // stops at) opens the next group
+  int32_t check_row_behind() {
+    long long g = 0;
+    const int32_t rc = next(&g);
+    if (rc != MIDAS_SNPS_OK || g == 0) return rc;
+    return check_rows(1);
+  }
 };
+
+// The reference converts a row's cells and then calls the site, row by row: of a row that cannot be read and a site that
+// cannot be called, the one it meets first is the error, whatever the row groups are (a row with both: the cells come first).
+bool call_error_comes_first(const RowGroups& rg, long long g, unsigned long long err) {
+  if (err == kNoBad) return false;
+  const long long bad_row = rg.first_bad_row(g);
+  return bad_row < 0 || (long long)(err >> 32) < bad_row;
+}
+
+// a site whose pooled frequency cannot be formed (ss_site_kernel's err): its place in stats, the reason in words
+int32_t site_pool_error(midas_snps_ctx* ctx, unsigned long long err, long long base, int64_t* stats) {
+  const long long row = base + (long long)(err >> 32), slot = (long long)((err & 0xFFFFFFFFull) >> 3) - 1;
+  const int why = (int)(err & 7u);
+  stats[4] = 2 + why;
+  stats[5] = row;
+  stats[6] = slot;
+  stats[0] = base;
+  char buf[160];
+  if (why == (int)kSiteNonFinite) snprintf(buf, sizeof buf, "data row %lld, sample %lld: the frequency to round is not a finite number", row, slot);
+  else snprintf(buf, sizeof buf, "data row %lld: the depths of the kept samples sum to 0, so no depth-weighted frequency", row);
+  return ss_fail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+}
 
 }  // namespace
 }  // namespace midas
@@ -889,7 +933,9 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
   float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, site, order, sums, seq, download
   RowGroups rg(ctx, dev, ev, ms, out_stats16);
   {
-    const int32_t rc = rg.init(freq, freq_bytes, depth, depth_bytes, n_sites_max, S, col_slot, iparams8[4], iparams8[5], per_row);
+    // (max_sites 0: the reference converts the first row's cells and stops)
+    const int32_t rc = rg.init(freq, freq_bytes, depth, depth_bytes, max_sites == 0 ? std::min<int64_t>(n_sites_max, 1) : n_sites_max, S,
+                               col_slot, iparams8[4], iparams8[5], per_row);
     if (rc != MIDAS_SNPS_OK) return rc;
   }
   const long long G = rg.G;
@@ -900,7 +946,8 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
   uint32_t *d_keep = nullptr, *d_rank = nullptr, *d_scratch = rg.d_scratch;
   int32_t* d_gene = nullptr;
   char *d_minor = nullptr, *d_major = nullptr;
-  unsigned long long* d_no_gene = nullptr;
+  unsigned long long *d_no_gene = nullptr, *d_err = nullptr;
+  SS_TRY(dev.get(&d_err, 8));
   SS_TRY(dev.get(&d_cell, cells));
   SS_TRY(dev.get(&d_mask, (size_t)G));
   SS_TRY(dev.get(&d_final, (size_t)G));
@@ -950,7 +997,8 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     sp.fv = d_fv; sp.dv = d_dv; sp.cell = d_cell; sp.mean_depth = d_mean; sp.mask = d_mask; sp.g = g; sp.stride = G; sp.S = S;
     sp.site_depth = site_depth; sp.site_ratio = fparams5[0]; sp.allele_support = fparams5[1]; sp.site_prev = fparams5[2];
     sp.site_maf = fparams5[3]; sp.weight = weight; sp.round_freq = round_freq; sp.mask_only = mask_only; sp.keep = d_keep;
-    sp.pooled = d_pooled;
+    sp.pooled = d_pooled; sp.err = d_err;
+    SS_TRY(hipMemsetAsync(d_err, 0xFF, 8, st));
     hipLaunchKernelGGL(ss_site_kernel, dim3(nblocks(g, 256)), dim3(256), 0, st, sp);
     SS_TRY(hipGetLastError());
     SS_TRY(hipEventRecord(ev.e[4], st));
@@ -964,6 +1012,8 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     SS_TRY(hipMemcpyAsync(&last_keep, d_keep + g - 1, 4, hipMemcpyDeviceToHost, st));
     SS_TRY(hipMemcpyAsync(&last_rank, d_rank + g - 1, 4, hipMemcpyDeviceToHost, st));
     SS_TRY(hipMemcpyAsync(&last_row, d_last, 8, hipMemcpyDeviceToHost, st));
+    unsigned long long err = kNoBad;
+    SS_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, st));
     if (want_sums) {
       SumP q;
       q.fv = pooled ? d_pooled : d_fv; q.dv = d_dv; q.cell = d_cell; q.final_keep = d_final; q.gene = d_gene; q.g = g; q.stride = G;
@@ -986,9 +1036,14 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     SS_TRY(rg.lap(6, 7, 6));
     long long kept_g = (long long)last_rank + last_keep;
     if (max_sites >= 0) kept_g = std::min(kept_g, max_sites - kept);
-    // the rows the reference reads: all of the group, or up to the one after the row that fills max_sites
+    // the rows the reference reads: all of the group, or up to the one after the row that fills max_sites -- whose cells it
+    // converts, but whose pooled frequency it never forms
     {
-      const int32_t rc = rg.check_rows(last_row >= 0 ? last_row + 2 : g);
+      const long long read_rows = last_row >= 0 ? last_row + 2 : g;
+      const long long pool_rows = max_sites == 0 ? 0 : last_row >= 0 ? last_row + 1 : g;
+      if (err != kNoBad && (long long)(err >> 32) < pool_rows && call_error_comes_first(rg, read_rows, err))
+        return site_pool_error(ctx, err, base, out_stats16);
+      const int32_t rc = rg.check_rows(read_rows);
       if (rc != MIDAS_SNPS_OK) return rc;
     }
     SS_TRY(hipEventRecord(ev.e[0], st));
@@ -1008,7 +1063,11 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     SS_TRY(rg.lap(0, 1, 7));
     kept += kept_g;
     rg.advance(g);
-    if (last_row >= 0) stop = true;
+    if (last_row >= 0) {
+      stop = true;
+      const int32_t rc = last_row == g - 1 ? rg.check_row_behind() : MIDAS_SNPS_OK;
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
   }
   if (want_sums) {
     SS_TRY(hipMemcpyAsync(out_pi, d_pi, n_acc * 8, hipMemcpyDeviceToHost, st));
@@ -1056,14 +1115,6 @@ int32_t strains_begin(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes,
     (*col_slot)[(size_t)sample_col[s]] = s;
   }
   return MIDAS_SNPS_OK;
-}
-
-// The reference converts a row's cells and then calls the site, row by row: of a row that cannot be read and a site that
-// cannot be called, the one it meets first is the error, whatever the row groups are (a row with both: the cells come first).
-bool call_error_comes_first(const RowGroups& rg, long long g, unsigned long long err) {
-  if (err == kNoBad) return false;
-  const long long bad_row = rg.first_bad_row(g);
-  return bad_row < 0 || (long long)(err >> 32) < bad_row;
 }
 
 // a site that cannot be called (the reference raises there): its place in stats, the reason in words
@@ -1350,7 +1401,9 @@ extern "C" int32_t midas_sites_consensus_pairs(midas_snps_ctx* ctx, const char* 
   float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, site, planes (order, list, planes), pairs, -, download
   RowGroups rg(ctx, dev, ev, ms, out_stats16);
   {
-    const int32_t rc = rg.init(freq, freq_bytes, depth, depth_bytes, n_sites_max, S, col_slot, iparams8[4], iparams8[5], per_row);
+    // (max_sites 0: the reference converts the first row's cells and stops)
+    const int32_t rc = rg.init(freq, freq_bytes, depth, depth_bytes, max_sites == 0 ? std::min<int64_t>(n_sites_max, 1) : n_sites_max, S,
+                               col_slot, iparams8[4], iparams8[5], per_row);
     if (rc != MIDAS_SNPS_OK) return rc;
   }
   const long long G = rg.G, wstride = (G + 63) / 64;
@@ -1395,6 +1448,7 @@ extern "C" int32_t midas_sites_consensus_pairs(midas_snps_ctx* ctx, const char* 
     sp.fv = rg.d_fv; sp.dv = rg.d_dv; sp.cell = d_cell; sp.mean_depth = d_mean; sp.mask = d_mask; sp.g = g; sp.stride = G; sp.S = S;
     sp.site_depth = site_depth; sp.site_ratio = fparams5[0]; sp.allele_support = fparams5[1]; sp.site_prev = fparams5[2];
     sp.site_maf = fparams5[3]; sp.weight = 0; sp.round_freq = 0; sp.mask_only = mask_only; sp.keep = d_keep; sp.pooled = d_pooled;
+    sp.err = nullptr;                            // (neither rounded nor weighted: nothing the reference raises on)
     hipLaunchKernelGGL(ss_site_kernel, dim3(nblocks(g, 256)), dim3(256), 0, st, sp);
     SS_TRY(hipGetLastError());
     SS_TRY(hipEventRecord(ev.e[4], st));
@@ -1444,7 +1498,11 @@ extern "C" int32_t midas_sites_consensus_pairs(midas_snps_ctx* ctx, const char* 
     }
     kept += kept_g;
     rg.advance(g);
-    if (last_row >= 0) stop = true;
+    if (last_row >= 0) {
+      stop = true;
+      const int32_t rc = last_row == g - 1 ? rg.check_row_behind() : MIDAS_SNPS_OK;
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
   }
   SS_TRY(hipEventRecord(ev.e[0], st));
   SS_TRY(hipMemcpyAsync(out_both, d_both, n_acc * 8, hipMemcpyDeviceToHost, st));

@@ -70,6 +70,14 @@ def _py_min(a, b):
     return b if b < a else a
 
 
+def _py_round(x, i, s):
+    """call_consensus: sample.freq = round(sample.freq), which raises on nan and inf."""
+    try:
+        return float(round(x))
+    except (OverflowError, ValueError):
+        raise BadCell((3, i, s), "data row %d, sample %d: the frequency to round is not a finite number" % (i, s))
+
+
 def is_fast_float(cell):
     """Whether the device's own converter takes the cell: [+-]digits[.digits][e[+-]digits], mantissa < 2^53, |p10| <= 22."""
     import re
@@ -142,7 +150,7 @@ def sites_scan(freq_text, depth_text, site_mask, sample_col, mean_depth, site_de
             if _py_max(f[s], 1 - f[s]) < allele_support:
                 k = False
             keep.append(k)
-        f2 = [float(round(x)) if rnd else x for x in f]
+        f2 = [_py_round(x, i, s) if rnd else x for s, x in enumerate(f)]
         count = sum(keep)
         if count == 0:
             pooled = 0.0
@@ -152,7 +160,10 @@ def sites_scan(freq_text, depth_text, site_mask, sample_col, mean_depth, site_de
                 if keep[s]:
                     dsum += d[s]
                     msum += d[s] * f2[s]
-            pooled = msum / dsum
+            try:
+                pooled = msum / dsum
+            except ZeroDivisionError:
+                raise BadCell((6, i, -1), "data row %d: the depths of the kept samples sum to 0, so no depth-weighted frequency" % i)
         else:
             pooled = pairwise_mean([f2[s] for s in range(S) if keep[s]])
         site_keep = bool(mask[i])

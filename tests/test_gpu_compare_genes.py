@@ -185,3 +185,47 @@ def test_merge_midas_genes_then_compare_genes_chain(tmp_path):
                                capture_output=True, text=True, timeout=600)
             assert r.returncode == 0, r.stderr
             assert open(dist).read() == M.model_table(text, M.case_options(dict(options=options))), (sp, options)
+
+
+# ---- gc_parse_kernel's converter (pandas_f64.h as device code) on the cells the host build alone has seen ------------------------------
+from tests.test_compare_genes_host import EDGE, NOT_NUMBERS                           # noqa: E402
+
+
+def _body(rows, eol='\n'):
+    return np.frombuffer(''.join('g%d\t%s%s' % (r, '\t'.join(row), eol) for r, row in enumerate(rows)).encode(), np.uint8)
+
+
+def test_edge_cells_on_the_device_are_the_models_bit_for_bit(ctx):
+    """Every EDGE cell as the first, a middle and the last cell of a row: 1e-400 and 4.9e-324, the two-step division below
+    1e-308 (a division with a subnormal quotient), 24-digit cells, padded cells, with \\n and with \\r\\n row ends."""
+    S = 3
+    rows = [[cell if c == at else ('1.5', '2', '7e-1')[(k + c) % 3] for c in range(S)] for k, cell in enumerate(EDGE) for at in range(S)]
+    exp, col_float = M.read_cells(_body(rows), len(rows), S, S)
+    assert (exp == 0).any() and (np.abs(exp[exp != 0]) < 2.3e-308).any() and col_float.all()
+    for eol in ('\n', '\r\n'):
+        for group_rows, chunk in GROUPS + ((7, 256),):
+            got = ctx.genes_compare(_body(rows, eol), len(rows), S, S, group_rows=group_rows, chunk_bytes=chunk, dump=True)
+            assert got['n_rows'] == len(rows)
+            wrong = np.argwhere(got['cells'].view(np.uint64) != exp.view(np.uint64))
+            assert wrong.shape[0] == 0, (eol, group_rows, [rows[r][c] for c, r in wrong.tolist()])
+            assert np.array_equal(got['col_float'], col_float.astype(np.uint8))
+    # a column of plain integers stays one
+    ints = [['3', '1.5', '-12'], [' 4', '2', '7']]
+    got = ctx.genes_compare(_body(ints), 2, S, S, dump=True)
+    assert got['col_float'].tolist() == M.read_cells(_body(ints), 2, S, S)[1].astype(np.uint8).tolist() == [0, 1, 0]
+
+
+@pytest.mark.parametrize("eol", ['\n', '\r\n'])
+def test_cells_that_are_no_number_are_refused_with_their_place_on_the_device(ctx, eol):
+    S, N = 3, 5
+    for k, cell in enumerate(NOT_NUMBERS):
+        for at in range(S):
+            rows = [['1.5', '2', '0.25'] for _ in range(N)]
+            r = (k + at) % N
+            rows[r][at] = cell
+            with pytest.raises(M.BadMatrix) as em:
+                M.read_cells(_body(rows, eol), N, S, S)
+            assert em.value.bad == (2, r, at)
+            with pytest.raises(abi.MidasSnpsError) as ei:
+                ctx.genes_compare(_body(rows, eol), N, S, S, group_rows=(0, 2)[k % 2])
+            assert ei.value.status == abi.ERR_BAD_LAYOUT and ei.value.bad == (2, r, at), (cell, at, eol)
