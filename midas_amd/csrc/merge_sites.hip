@@ -127,6 +127,8 @@ __device__ __forceinline__ void finish_site(const MergeKParams& p, uint32_t i, c
 
 // Thread-per-site form: two passes over the site's count rows -- pooling, then per-sample depth.  The second pass hits
 // L2 / Infinity Cache while the rows of all resident threads fit there (up to a couple of dozen samples).
+// launch_merge_kernel reaches it only in a build with MIDAS_MERGE_TWO_PASS (the round-1 kernels, for A/B runs): every
+// sample count has a register or a split form in front of it, and no test runs it.
 __global__ __launch_bounds__(256) void merge_sites_kernel(MergeKParams p) {
   const uint32_t stride = gridDim.x * 256u;
   for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < p.n_sites; i += stride) {
@@ -357,28 +359,62 @@ SampleLimit sample_limits(double mean_depth, double site_ratio, int site_depth) 
 
 // the kernel form for n_samples (see above) on the context's stream
 void launch_merge_kernel(midas_snps_ctx* ctx, const MergeKParams& k, long long m, int n_samples, bool shallow) {
-  const int grid = (int)((m + 255) / 256 < 4096 ? (m + 255) / 256 : 4096);
+  long long grid_cap = 4096, tile_cap = 16384;
+  if (const char* e = getenv("MIDAS_SNPS_MERGE_GRID_BLOCKS")) {      // developer knob: several passes with small inputs
+    const long long v = atoll(e);
+    if (v > 0 && v < grid_cap) grid_cap = v;
+    if (v > 0 && v < tile_cap) tile_cap = v;
+  }
+  const int grid = (int)((m + 255) / 256 < grid_cap ? (m + 255) / 256 : grid_cap);
   const dim3 g(grid > 0 ? grid : 1), b(256);
+  // one line per launch: the form taken, samples, blocks x threads, the chunk's sites
+  const bool trace = getenv("MIDAS_SNPS_TRACE") != nullptr;
+  auto say = [&](const char* form, int arg, const dim3& blocks, unsigned threads) {
+    if (!trace) return;
+    char name[32];
+    if (arg > 0) snprintf(name, sizeof name, "%s%d", form, arg);
+    else snprintf(name, sizeof name, "%s", form);
+    fprintf(stderr, "[merge kernel] form %s, %d samples, %u blocks x %u threads, %lld sites\n", name, n_samples, blocks.x, threads, m);
+  };
 #ifndef MIDAS_MERGE_TWO_PASS
   if (n_samples <= kRegsUpTo) {     // rows in registers: every count row is read once
+    say(n_samples <= 8 ? "regs32" : "regs16", 0, g, 256u);
     hipLaunchKernelGGL(regs_kernel_for(n_samples, std::make_integer_sequence<int, kRegsUpTo>{}), g, b, 0, ctx->stream, k);
   } else if (n_samples <= 128 && kRegsUpTo >= 64 && shallow) {   // the same with a byte per count
+    say("bytes S=", (n_samples + 7) / 8 * 8, g, 256u);
     hipLaunchKernelGGL(bytes_kernel_for(n_samples, std::make_integer_sequence<int, 8>{}), g, b, 0, ctx->stream, k);
   } else {
 #endif
   if (n_samples >= kSplitFrom) {
     // waves per site group: enough that the rows resident between the passes stay below ~100 MB
     const long long n_tiles = (m + 63) / 64;
-    const dim3 tg((unsigned)(n_tiles < 16384 ? (n_tiles > 0 ? n_tiles : 1) : 16384));
-    if (n_samples < 2 * kSplitFrom) hipLaunchKernelGGL(merge_sites_split_kernel<4>, tg, dim3(256), 0, ctx->stream, k);
-    else if (n_samples < 4 * kSplitFrom) hipLaunchKernelGGL(merge_sites_split_kernel<8>, tg, dim3(512), 0, ctx->stream, k);
+    const dim3 tg((unsigned)(n_tiles < tile_cap ? (n_tiles > 0 ? n_tiles : 1) : tile_cap));
+    const int waves = n_samples < 2 * kSplitFrom ? 4 : (n_samples < 4 * kSplitFrom ? 8 : 16);
+    say("split G=", waves, tg, 64u * (unsigned)waves);
+    if (waves == 4) hipLaunchKernelGGL(merge_sites_split_kernel<4>, tg, dim3(256), 0, ctx->stream, k);
+    else if (waves == 8) hipLaunchKernelGGL(merge_sites_split_kernel<8>, tg, dim3(512), 0, ctx->stream, k);
     else hipLaunchKernelGGL(merge_sites_split_kernel<16>, tg, dim3(1024), 0, ctx->stream, k);
   } else {
+    say("two_pass", 0, g, 256u);
     hipLaunchKernelGGL(merge_sites_kernel, g, b, 0, ctx->stream, k);
   }
 #ifndef MIDAS_MERGE_TWO_PASS   // (developer variants: the round-1 kernels, for A/B runs)
   }
 #endif
+}
+
+// Sites are processed in chunks -- windows of the resident set of <= ~4 GiB of counts -- which bound the per-site results'
+// buffers.  One rule for both entries.
+long long merge_chunk_sites(int n_samples, long long n_sites) {
+  long long chunk = (long long)((4ull << 30) / (16ull * (unsigned long long)n_samples));
+  if (chunk < 1024) chunk = 1024;
+  if (chunk > kMaxChunkSites) chunk = kMaxChunkSites;
+  if (const char* e = getenv("MIDAS_SNPS_MERGE_CHUNK_SITES")) {      // developer knob: chunk borders with small inputs
+    const long long v = atoll(e);
+    if (v > 0 && v < chunk) chunk = v;
+  }
+  if (chunk > n_sites) chunk = n_sites > 0 ? n_sites : 1;
+  return chunk;
 }
 
 int32_t mfail(midas_snps_ctx* ctx, int32_t st, const char* what, hipError_t e) {
@@ -435,11 +471,7 @@ extern "C" int32_t midas_merge_sites_resident(midas_snps_ctx* ctx, const midas_m
   if (out_kernel_ms) *out_kernel_ms = 0.f;
   std::vector<void*> dev;
   M_TRY(hipSetDevice(ctx->device));
-  // sites are processed in chunks -- windows of the resident set of <= ~4 GiB of counts -- which bound the per-site results' buffers
-  long long chunk = (long long)((4ull << 30) / (16ull * (unsigned long long)n_samples));
-  if (chunk < 1024) chunk = 1024;
-  if (chunk > kMaxChunkSites) chunk = kMaxChunkSites;
-  if (chunk > n_sites) chunk = n_sites > 0 ? n_sites : 1;
+  const long long chunk = merge_chunk_sites(n_samples, n_sites);
   // 65..128 samples: a byte per count holds a site's rows when the samples are shallow (a site with a count >= 256 takes
   // the long way round by itself, which only pays while such sites are rare: mean depths well below 256)
   bool shallow = true;
@@ -545,14 +577,7 @@ extern "C" int32_t midas_merge_sites_tables_resident(midas_snps_ctx* ctx, const 
   std::lock_guard<std::mutex> ring(ctx->copy_mutex);      // the text's way down owns the pinned ring for the whole call
   std::vector<void*> dev;
   M_TRY(hipSetDevice(ctx->device));
-  long long chunk = (long long)((4ull << 30) / (16ull * (unsigned long long)n_samples));
-  if (chunk < 1024) chunk = 1024;
-  if (chunk > kMaxChunkSites) chunk = kMaxChunkSites;
-  if (const char* e = getenv("MIDAS_SNPS_MERGE_CHUNK_SITES")) {      // developer knob: chunk borders with small inputs
-    const long long v = atoll(e);
-    if (v > 0 && v < chunk) chunk = v;
-  }
-  if (chunk > n_sites) chunk = n_sites > 0 ? n_sites : 1;
+  const long long chunk = merge_chunk_sites(n_samples, n_sites);
   bool shallow = true;
   for (int s = 0; s < n_samples; ++s) shallow = shallow && mean_depth[s] <= 64.0;
   std::vector<SampleLimit> limits((size_t)n_samples);

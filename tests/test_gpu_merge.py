@@ -185,7 +185,8 @@ def test_merge_sites_edge_shapes(ctx):
     assert r['pooled'][0].tolist() == [3 * (2**31 - 1), 3 * (2**31 - 1), 15, 0]
     assert (r['major'][0], r['minor'][0], r['snp_type'][0]) == (0, 1, 2)     # tie -> A before C; G's 15/1.3e10 < 0.01
     assert r['depth'][:, 0].tolist() == [2**32 - 2] * 3 and r['count_samples'][0] == 3
-    # ragged sample count vs grid: 3 samples x 100003 sites (grid-stride tail)
+    # 3 samples x 100003 sites: 391 blocks, the last one ragged (67 live threads).  One pass of the grid: no thread takes a
+    # second site below 1 048 576 sites -- tests/test_gpu_merge_borders.py strides
     rng = np.random.default_rng(2)
     counts = [rng.integers(0, 9, (100003, 4)).astype(np.uint32) for _ in range(3)]
     args = dict(abi.DEFAULT_MERGE_ARGS, snp_type=['any'], site_prev=0.5)
