@@ -311,6 +311,40 @@ int32_t midas_snps_batch_pack(midas_snps_batch* batch);
  * are always returned.                                                                                            */
 int32_t midas_snps_batch_fetch_packed(midas_snps_batch* batch, void* rec16, void* blob, uint32_t* orig_index,
                                       uint32_t* key, int64_t* out_n_records, int64_t* out_blob_bytes);
+/* The direct path's index pass, looked at from outside (tests/test_gpu_index.py holds it to a model word for word): runs ONE
+ * ranges pass on the batch's current parity exactly as a run on the direct path starts -- the same function: the ranges kernel,
+ * then the listed outliers when the ranges keep to the common span -- advances the parity as a run does, and copies down
+ *   tbegin, tend   [n_tiles]  the run of reads [tbegin, tend) every 2048-site tile streams (tbegin 0xFFFFFFFF: none reaches it);
+ *   out_facts      [MIDAS_SNPS_INDEX_FACTS]  MIDAS_SNPS_INDEX_* order: the facts pass of batch_create as it was summed, and
+ *                  what the batch derived from it;
+ *   outliers3      [3 * n_outliers_listed]  (read, first tile, last tile) of every listed read that spans more than the
+ *                  overhang, in the order the device listed them (any); never more than 3 * max(4096, n_reads / 64) words;
+ *   tile_flag      [n_tiles]  1: an outlier leaves the tile's overhang here (such a tile's chunk is dealt tile by tile);
+ *   chunk_ok       [*out_n_chunk_ok]  0: the chunk of four tiles holds a flagged tile; at most max(1, n_tiles / 4) bytes, and
+ *                  *out_n_chunk_ok == 0 when the batch has no such table (every chunk carries its overhang, or no chunks).
+ * Any output pointer may be NULL (chunk_ok only together with its length).  MIDAS_SNPS_ERR_INVALID_ARG: a null batch, chunk_ok
+ * without out_n_chunk_ok; MIDAS_SNPS_ERR_UNSUPPORTED: a batch on the long path -- no ranges were ever built.  The per-species
+ * counters of the last run are reset, as by a run: fetch results first (test aid; no reference counterpart).                 */
+enum {
+  MIDAS_SNPS_INDEX_STATUS = 0,        /* lowest (read << 8 | code) of a malformed read, -1 when every read is well-formed */
+  MIDAS_SNPS_INDEX_ALG = 1,           /* sum(ceil(l/2) + l + 4 * n_cigar + 16)                                           */
+  MIDAS_SNPS_INDEX_N_GENERAL = 2,
+  MIDAS_SNPS_INDEX_N_LONG = 3,
+  MIDAS_SNPS_INDEX_N_OUTLIERS = 4,    /* reads whose reference span exceeds the overhang                                  */
+  MIDAS_SNPS_INDEX_MAX_L = 5,
+  MIDAS_SNPS_INDEX_MAX_SPAN = 6,
+  MIDAS_SNPS_INDEX_MAX_COMMON = 7,    /* longest reference span of a read that is no outlier                             */
+  MIDAS_SNPS_INDEX_UNSORTED = 8,
+  MIDAS_SNPS_INDEX_REACH = 9,
+  MIDAS_SNPS_INDEX_REACH_RANGES = 10, /* what the ranges pass reaches back over                                          */
+  MIDAS_SNPS_INDEX_OVERHANG = 11,     /* the overhang the facts pass judged the outliers by                              */
+  MIDAS_SNPS_INDEX_CHUNKS = 12,
+  MIDAS_SNPS_INDEX_N_LISTED = 13,
+  MIDAS_SNPS_INDEX_OUTLIER_CAP = 14,
+  MIDAS_SNPS_INDEX_FACTS = 15
+};
+int32_t midas_snps_batch_fetch_index(midas_snps_batch* batch, uint32_t* tbegin, uint32_t* tend, int64_t* out_facts, uint32_t* outliers3,
+                                     uint8_t* tile_flag, uint8_t* chunk_ok, int64_t* out_n_chunk_ok);
 /* Device-side durations of a timed pack (enable_timing slots, like batch_timing): [0] whole pack, [1] its scatter
  * kernel (the dominant one: raw reads in, records + payload out).                                                 */
 int32_t midas_snps_batch_pack_timing(midas_snps_batch* batch, int32_t slot, float out_ms[2]);

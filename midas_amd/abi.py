@@ -93,6 +93,9 @@ class BatchInfo(C.Structure):
 ROWS_DEVICE, ROWS_HOST = 0, 1    # who formats and deflates a batch's rows (midas_snps_set_row_coder)
 PAD_SPEC, PAD_PYSAM = 0, 1       # what the CIGAR op P does to the query position (midas_snps_set_pad_rule)
 PATH_AUTO, PATH_DIRECT, PATH_PACKED, PATH_LONG = 0, 1, 2, 3
+# midas_snps_batch_fetch_index's out_facts (MIDAS_SNPS_INDEX_* order)
+INDEX_FACTS = ('status', 'alg', 'n_general', 'n_long', 'n_outliers', 'max_l', 'max_span', 'max_common', 'unsorted', 'direct_reach',
+               'direct_reach_ranges', 'direct_overhang', 'direct_chunks', 'n_outliers_listed', 'outlier_cap')
 PATH_NAMES = {PATH_AUTO: "auto", PATH_DIRECT: "direct", PATH_PACKED: "packed", PATH_LONG: "long"}
 
 
@@ -272,6 +275,7 @@ def load_library(build_if_missing: bool = True):
         'midas_snps_copy_rate': (i32, [vp, i64, i32, C.POINTER(C.c_double)]),
         'midas_snps_batch_fetch_packed': (i32, [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]),
         'midas_snps_batch_pack_timing': (i32, [vp, i32, C.POINTER(C.c_float)]),
+        'midas_snps_batch_fetch_index': (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64)]),
     }
     sig.update({
         'midas_bam_open': (i32, [C.c_char_p, C.POINTER(vp), C.c_char_p]),
@@ -421,7 +425,7 @@ EXPORTED_SYMBOLS = [
     'midas_snps_batch_stats_to_device', 'midas_snps_batch_pack', 'midas_snps_batch_fetch_packed',
     'midas_snps_batch_select_path', 'midas_snps_set_default_path', 'midas_snps_copy_rate', 'midas_snps_stream_rates', 'midas_snps_calibration_pass', 'midas_snps_set_pad_rule', 'midas_snps_set_row_coder',
     'midas_snps_row_coder_counts', 'midas_snps_rows_code', 'midas_snps_scan_u32', 'midas_snps_sort_pairs',
-    'midas_snps_batch_pack_timing',
+    'midas_snps_batch_pack_timing', 'midas_snps_batch_fetch_index',
     'midas_bam_open', 'midas_bam_close', 'midas_bam_write', 'midas_bam_n_refs', 'midas_bam_ref', 'midas_bam_load', 'midas_bam_copy', 'midas_bam_columns',
     'midas_bam_open_slice', 'midas_bam_slice_facts', 'midas_bam_slice_marks', 'midas_bam_load_ranges',
     'midas_bam_open_device', 'midas_bam_open_slice_device', 'midas_bam_load_ranges_device', 'midas_snps_inflate_blocks', 'midas_bam_load_device',
@@ -2391,6 +2395,24 @@ class Batch:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         self.ctx._check(self._lib.midas_snps_batch_fetch_packed(self._h, p(rec), p(blob), p(orig), p(key), C.byref(n), C.byref(nb)))
         return rec, blob[:nb.value], orig[:n.value], key[:n.value]
+
+    def fetch_index(self):
+        """One ranges pass of the direct path on the batch's current parity, and what the index pass left on the device
+        (midas_snps_batch_fetch_index; test aid): a dict of tbegin / tend [n_tiles] u32, facts {name: int} in INDEX_FACTS order,
+        outliers [n_listed, 3] u32 (read, first tile, last tile; device order), tile_flag [n_tiles] u8 and chunk_ok u8 (empty when
+        the batch has no such table)."""
+        bi = self.info()
+        nt, cap = int(bi.n_tiles), max(4096, int(bi.n_reads) // 64)
+        tb, te = np.zeros(max(nt, 1), np.uint32), np.zeros(max(nt, 1), np.uint32)
+        facts = np.zeros(len(INDEX_FACTS), np.int64)
+        out3 = np.zeros((cap, 3), np.uint32)
+        flag, ok = np.zeros(max(nt, 1), np.uint8), np.zeros(max(nt // 4, 1), np.uint8)
+        n_ok = C.c_int64(0)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self.ctx._check(self._lib.midas_snps_batch_fetch_index(self._h, p(tb), p(te), p(facts), p(out3), p(flag), p(ok), C.byref(n_ok)))
+        f = dict(zip(INDEX_FACTS, (int(x) for x in facts)))
+        return dict(tbegin=tb[:nt], tend=te[:nt], facts=f, outliers=out3[:min(f['n_outliers_listed'], cap)].copy(), tile_flag=flag[:nt],
+                    chunk_ok=ok[:n_ok.value].copy())
 
     def stats_to_device(self, dst_device_ptr: int):
         """Enqueue a D2D copy of the [n_species,4] int64 counters into caller-owned device memory."""

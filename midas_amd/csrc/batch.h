@@ -10,6 +10,12 @@
 #include "layout.h"
 #include "hostio.h"
 
+// What the direct path's facts pass found (index_direct.hip, direct_facts_kernel), its slots added up.
+struct DirectFactsSum {
+  unsigned long long status = midas::kNoError, alg = 0, n_general = 0, n_long = 0, n_outliers = 0;
+  uint32_t max_l = 0, max_span = 0, unsorted = 0, max_common = 0;
+};
+
 struct midas_snps_batch {
   midas_snps_ctx* ctx = nullptr;
   // Every device allocation of the batch (batch_alloc), freed by batch_destroy.  Pointers below that are NOT in it are borrowed:
@@ -97,6 +103,7 @@ struct midas_snps_batch {
   int64_t direct_run_count = 0;
   bool pad_advances = false;    // the context's pad rule when the batch was created (MIDAS_SNPS_PAD_PYSAM)
   int64_t n_long = 0;           // reads beyond the fast paths' limits: > 0 and the batch runs on the long path only (pileup_long.hip)
+  DirectFactsSum direct_facts;  // the last facts pass, as it was summed (midas_snps_batch_fetch_index hands it out)
   bool direct_sorted = false;   // every contig's reads in position order (found by the first index pass): tile ranges need no atomics
   // timing
   std::vector<hipEvent_t> ev;  // 3 per slot: before the index kernel, before and after the pileup kernel

@@ -71,11 +71,7 @@ int32_t allocate_and_reset(midas_snps_batch* b) {
   return reset_facts(b);
 }
 
-// What the facts pass found, its slots added up.
-struct FactsSum {
-  unsigned long long status = kNoError, alg = 0, n_general = 0, n_long = 0, n_outliers = 0;
-  uint32_t max_l = 0, max_span = 0, unsorted = 0, max_common = 0;
-};
+using FactsSum = DirectFactsSum;      // (batch.h: the batch keeps the last one)
 int32_t facts_pass(midas_snps_batch* b, FactsSum* sum) {
   midas_snps_ctx* ctx = b->ctx;
   hipStream_t s = ctx->stream;
@@ -116,6 +112,7 @@ int32_t facts_and_summary(midas_snps_batch* b) {
     ST_TRY(reset_facts(b));
     ST_TRY(facts_pass(b, &f));
   }
+  b->direct_facts = f;
   b->max_l_seq = (int32_t)f.max_l;
   b->direct_sorted = f.unsorted == 0;
   b->direct_general = (int64_t)f.n_general;
@@ -205,6 +202,18 @@ int32_t build_layout(midas_snps_batch* b) {
   return MIDAS_SNPS_OK;
 }
 
+// One ranges pass on the batch's current parity, as every run of the direct path starts: the tile ranges from the positions, then
+// the listed outliers added to the tiles they reach (when the ranges kept to the common span).  The caller advances
+// direct_run_count once the pass's consumers are enqueued.
+int32_t ranges_pass(midas_snps_batch* b, DirectIndexParams* ip) {
+  midas_snps_ctx* ctx = b->ctx;
+  hipStream_t s = ctx->stream;
+  fill_direct_index(b, ip);
+  HIP_TRY(ctx, launch_direct_ranges(*ip, s));
+  if (b->direct_reach_ranges != b->direct_reach) HIP_TRY(ctx, launch_direct_outliers(b->d_outliers, b->n_outliers_listed, ip->tbegin, s));
+  return MIDAS_SNPS_OK;
+}
+
 // step 4: the tile ranges once, to see how well the reads are ordered -- a tile's stream holds every read between the first and
 // the last that can touch it -- and the path the batch's own numbers recommend
 int32_t probe_ranges_and_choose(midas_snps_batch* b) {
@@ -212,9 +221,7 @@ int32_t probe_ranges_and_choose(midas_snps_batch* b) {
   hipStream_t s = ctx->stream;
   const size_t nt = (size_t)(b->n_tiles > 0 ? b->n_tiles : 1);
   DirectIndexParams ip;
-  fill_direct_index(b, &ip);
-  HIP_TRY(ctx, launch_direct_ranges(ip, s));
-  if (b->direct_reach_ranges != b->direct_reach) HIP_TRY(ctx, launch_direct_outliers(b->d_outliers, b->n_outliers_listed, ip.tbegin, s));
+  ST_TRY(ranges_pass(b, &ip));
   std::vector<uint32_t> tb(nt), te(nt);
   HIP_TRY(ctx, hipMemcpyAsync(tb.data(), ip.tbegin, nt * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(te.data(), ip.tend, nt * 4, hipMemcpyDeviceToHost, s));
@@ -268,9 +275,7 @@ int32_t midas_batch::run_direct(midas_snps_batch* b, const midas_snps_thresholds
   midas_snps_ctx* ctx = b->ctx;
   hipStream_t s = ctx->stream;
   DirectIndexParams dip;
-  fill_direct_index(b, &dip);
-  HIP_TRY(ctx, launch_direct_ranges(dip, s));
-  if (b->direct_reach_ranges != b->direct_reach) HIP_TRY(ctx, launch_direct_outliers(b->d_outliers, b->n_outliers_listed, dip.tbegin, s));
+  ST_TRY(ranges_pass(b, &dip));
   if (ev) HIP_TRY(ctx, hipEventRecord(ev[1], s));
   DirectParams dp;
   dp.rec = b->d_drec; dp.payload = b->d_dpay;
@@ -306,3 +311,43 @@ int32_t midas_batch::run_direct(midas_snps_batch* b, const midas_snps_thresholds
   b->direct_run_count += 1;
   return MIDAS_SNPS_OK;
 }
+
+extern "C" {
+
+// Test aid (tests/test_gpu_index.py): the ranges pass of a run -- ranges_pass, not a copy of it -- on the current parity, then the
+// ranges, the facts and what the batch derived from them, the outlier list, the tile flags and chunk_ok on the host.
+int32_t midas_snps_batch_fetch_index(midas_snps_batch* b, uint32_t* tbegin, uint32_t* tend, int64_t* facts, uint32_t* outliers3, uint8_t* tile_flag,
+                                     uint8_t* chunk_ok, int64_t* out_n_chunk_ok) {
+  if (!b || (chunk_ok && !out_n_chunk_ok)) return MIDAS_SNPS_ERR_INVALID_ARG;
+  midas_snps_ctx* ctx = b->ctx;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (b->n_long > 0 || !b->d_trange) return fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "the batch has the long path only: no tile ranges were built");
+  hipStream_t s = ctx->stream;
+  DirectIndexParams ip;
+  ST_TRY(ranges_pass(b, &ip));
+  b->direct_run_count += 1;
+  const size_t nt = (size_t)b->n_tiles;
+  if (tbegin && nt) HIP_TRY(ctx, hipMemcpyAsync(tbegin, ip.tbegin, nt * 4, hipMemcpyDeviceToHost, s));
+  if (tend && nt) HIP_TRY(ctx, hipMemcpyAsync(tend, ip.tend, nt * 4, hipMemcpyDeviceToHost, s));
+  if (tile_flag && nt) HIP_TRY(ctx, hipMemcpyAsync(tile_flag, b->d_tile_flag, nt, hipMemcpyDeviceToHost, s));
+  const uint32_t n_out = std::min(b->n_outliers_listed, b->outlier_cap);
+  std::vector<DirectOutlier> list(outliers3 ? n_out : 0u);
+  if (!list.empty()) HIP_TRY(ctx, hipMemcpyAsync(list.data(), b->d_outliers, list.size() * sizeof(DirectOutlier), hipMemcpyDeviceToHost, s));
+  const int64_t n_ok = b->d_chunk_ok ? std::max<int64_t>(1, (b->n_tiles - b->n_tiles / kDirectTailDiv) / kDirectChunkTiles) : 0;
+  if (chunk_ok && n_ok) HIP_TRY(ctx, hipMemcpyAsync(chunk_ok, b->d_chunk_ok, (size_t)n_ok, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  for (size_t k = 0; k < list.size(); ++k) {
+    outliers3[3 * k] = list[k].read; outliers3[3 * k + 1] = list[k].t_first; outliers3[3 * k + 2] = list[k].t_last;
+  }
+  if (out_n_chunk_ok) *out_n_chunk_ok = n_ok;
+  if (facts) {
+    const DirectFactsSum& f = b->direct_facts;
+    const int64_t v[MIDAS_SNPS_INDEX_FACTS] = {
+        (int64_t)f.status, (int64_t)f.alg, (int64_t)f.n_general, (int64_t)f.n_long, (int64_t)f.n_outliers, f.max_l, f.max_span, f.max_common,
+        f.unsorted, b->direct_reach, b->direct_reach_ranges, b->direct_overhang, b->direct_chunks ? 1 : 0, b->n_outliers_listed, b->outlier_cap};
+    std::copy(v, v + MIDAS_SNPS_INDEX_FACTS, facts);
+  }
+  return MIDAS_SNPS_OK;
+}
+
+}  // extern "C"
