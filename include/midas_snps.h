@@ -999,7 +999,8 @@ int32_t midas_sites_parse_cell(int32_t kind, const char* text, int64_t n, void* 
  * dump_* (nullable, tests): the parsed cells [n_samples][n_sites_max], the sites' final keep flag and pooled frequency.
  * out_stats16: [0] sites read, [1] sites kept, [2] / [3] freq / depth cells converted by the host, [7] row groups, [8] kept
  * sites without a gene under MIDAS_SITES_PER_GENE, [9] group_rows and [10] chunk_bytes in use.  out_ms8 (nullable): upload +
- * index (host clock), index, parse, site, order, sums, sequences, download (device events).                               */
+ * index (host clock), index, parse, site, order, sums, sequences, download (device events).
+ * A matrix column selected twice in sample_col is MIDAS_SNPS_ERR_INVALID_ARG here and below, with n_sites_max 0 too.       */
 #define MIDAS_SITES_WEIGHT 1
 #define MIDAS_SITES_ROUND 2
 #define MIDAS_SITES_POOLED 4

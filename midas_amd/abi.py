@@ -1488,6 +1488,14 @@ class Context:
                 self._lib.midas_snps_status_string(st).decode()
             raise MidasSnpsError(st, msg, int(self._lib.midas_snps_last_error_read(self._h)))
 
+    def _check_bad(self, st: int, stats):
+        """_check() for a call that reports the place of a bad row: the error carries .bad = stats[4..6], None where [4] is 0."""
+        try:
+            self._check(st)
+        except MidasSnpsError as e:
+            e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
+            raise
+
     def set_stream(self, hip_stream: Optional[int]):
         self._check(self._lib.midas_snps_set_stream(self._h, C.c_void_p(hip_stream or 0)))
 
@@ -1933,12 +1941,7 @@ class Context:
                                         p(mean), p(fp), p(ip), p(out.get('pi')), p(out.get('snps')), p(out.get('sites')),
                                         p(out.get('depth')), p(seq), p(out.get('freq')), p(out.get('depthv')), p(out.get('keep')),
                                         p(out.get('pooled')), p(stats), p(ms))
-        if st != 0:
-            try:
-                self._check(st)
-            except MidasSnpsError as e:
-                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
-                raise
+        self._check_bad(st, stats)
         n = int(stats[0])
         out.update(n_sites=n, n_kept=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]), groups=int(stats[7]),
                    no_gene=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), ms=ms.tolist())
@@ -1961,12 +1964,7 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
         st = fn(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], int(n_parse), int(n_call), *[p(a) for a in site_arrays], cols.shape[0],
                 p(cols), p(fp), p(ip), p(out), p(stats), p(ms))
-        if st != 0:
-            try:
-                self._check(st)
-            except MidasSnpsError as e:
-                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
-                raise
+        self._check_bad(st, stats)
         return dict(n_sites=int(stats[0]), groups=int(stats[7]), side_freq=int(stats[2]), side_depth=int(stats[3]),
                     group_rows=int(stats[9]), chunk_bytes=int(stats[10]), ms=ms.tolist()), stats
 
@@ -2026,13 +2024,11 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
         st = self._lib.midas_sites_consensus_pairs(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], int(mask.shape[0]), p(mask), S, p(cols),
                                                    p(mean), p(fp), p(ip), p(both), p(diff), p(stats), p(ms))
-        if st != 0:
-            try:
-                self._check(st)
-            except MidasSnpsError as e:
-                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
-                e.limit = int(stats[13]) if st == ERR_OUT_OF_MEMORY and stats[13] < S else None
-                raise
+        try:
+            self._check_bad(st, stats)
+        except MidasSnpsError as e:
+            e.limit = int(stats[13]) if st == ERR_OUT_OF_MEMORY and stats[13] < S else None
+            raise
         return dict(both=both, diff=diff, n_sites=int(stats[0]), n_kept=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]),
                     groups=int(stats[7]), word_pairs=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]),
                     pair_runs=int(stats[11]), pair_steps=int(stats[12]), sample_limit=int(stats[13]), ms=ms.tolist())
@@ -2081,12 +2077,7 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
         st = self._lib.midas_genes_compare(self._h, p(tx), tx.shape[0], N, S, int(n_columns), GENES_DTYPES[dtype], kd, float(cutoff), p(ip),
                                            p(count), p(both), p(either), p(dist), p(col_float), p(cells), p(stats), p(ms))
-        if st != 0:
-            try:
-                self._check(st)
-            except MidasSnpsError as e:
-                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
-                raise
+        self._check_bad(st, stats)
         n = int(stats[0])
         out = dict(dtype=dtype, distance=distance, n_samples=S, n_rows=n, col_float=col_float, groups=int(stats[7]), steps=int(stats[8]),
                    tiles=int(stats[11]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), ms=ms.tolist(), count=count, both=both,
@@ -2158,12 +2149,7 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         st = self._lib.midas_species_merge(self._h, len(paths), C.cast(arr, C.c_void_p), len(ids), p(names), p(off), float(sample_depth), p(ip), p(stats),
                                            p(ms), C.byref(res))
-        if st != 0:
-            try:
-                self._check(st)
-            except MidasSnpsError as e:
-                e.bad = (int(stats[4]), int(stats[5]), int(stats[6])) if stats[4] else None
-                raise
+        self._check_bad(st, stats)
         return SpeciesMerge(self._lib, res, len(ids), len(paths), stats, ms)
 
     def batch(self, contigs: ContigTable, reads: ReadsSoA) -> "Batch":

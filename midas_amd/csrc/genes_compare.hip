@@ -1,7 +1,7 @@
 // compare_genes.py on MI355X: the distance of the gene content of every pair of samples, from genes_copynum.txt as text.
 //
 //   open     the matrix is mapped; its header gives the sample ids, its newlines the row count (host)
-//   chunks   a run of bytes is uploaded; its complete rows are the group's candidates        (text_rows.h, as sites_scan.hip)
+//   chunks   a run of bytes is uploaded; its complete rows are the group's candidates        (text_rows.h, as sites_rows.h)
 //   index    newlines counted per 16 bytes, exclusive scan, newline k's position -> ends[k]   (text_rows.h)
 //   parse    one thread a row walks its fields; the cells of the first S sample columns are converted as pandas' C reader
 //            converts them (pandas_f64.h: NOT float()), sample-major [sample][G].  A row of another width or a cell that is
@@ -396,13 +396,9 @@ int32_t midas_genes_compare(midas_snps_ctx* ctx, const char* text, int64_t text_
       hipLaunchKernelGGL(gc_bits_kernel, dim3((unsigned)n_words, (unsigned)((S + 3) / 4)), dim3(256), 0, st, d_val, g, G, S, cutoff, d_bits, wstride);
       SS_TRY(hipGetLastError());
       SS_TRY(hipEventRecord(ev.e[4], st));
-      // word runs: enough workgroups to fill the device when the tiles are few, each run whole staging steps
-      long long runs = std::max<long long>(1, std::min<long long>((pair_blocks + n_tiles - 1) / n_tiles, (n_words + kPairRun - 1) / kPairRun));
-      runs = std::min<long long>(runs, 65535);
-      const long long run_words = ((n_words + runs - 1) / runs + kPairRun - 1) / kPairRun * kPairRun;
-      runs = (n_words + run_words - 1) / run_words;
-      hipLaunchKernelGGL(ss_pairs_kernel, dim3((unsigned)n_tiles, (unsigned)runs), dim3(256), 0, st, d_bits, wstride, n_words, run_words, S,
-                         tiles_side, d_count);
+      const PairRuns pr = pair_runs(n_words, n_tiles, pair_blocks, kPairRun);
+      hipLaunchKernelGGL(ss_pairs_kernel, dim3((unsigned)n_tiles, (unsigned)pr.runs), dim3(256), 0, st, d_bits, wstride, n_words, pr.run_words,
+                         S, tiles_side, d_count);
       SS_TRY(hipGetLastError());
       SS_TRY(hipEventRecord(ev.e[5], st));
       steps += (long long)S * (S + 1) / 2 * n_words;

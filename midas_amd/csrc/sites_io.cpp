@@ -4,7 +4,7 @@
 //                     (fetch_samples, midas/analyze/parse_snps.py:181-194);
 //   snps_info.txt     as columns: site_id, ref_allele, major_allele, minor_allele, locus_type, site_type and a gene index
 //                     (gene ids numbered in order of first appearance, -1 for an empty id);
-//   snps_freq.txt, snps_depth.txt   mapped, NOT parsed: their rows go to the device as bytes (sites_scan.hip).  The header
+//   snps_freq.txt, snps_depth.txt   mapped, NOT parsed: their rows go to the device as bytes (sites_rows.h).  The header
 //                     row gives the sample ids; the reference keeps the depth file's (parse_snps.py:55-58).
 //
 // strain_tracking.py's two output tables are written here too (midas_sites_write_markers / _pairs): integers and strings.

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void sm_missing_kernel(const uint32_t* seen, l
   if (s < sample_limit && seen[i] == 0xFFFFFFFFu) atomicMin(miss, ((unsigned long long)s << 32) | (unsigned long long)sp);
 }
 
-// numpy's pairwise_sum over n <= 128 values (eight partial sums, then the tail), as sites_scan.hip forms it
+// numpy's pairwise_sum over n <= 128 values (eight partial sums, then the tail), as sites_call.h forms it
 __device__ double sm_pairwise_leaf(const double* a, long long n) {
   if (n < 8) {
     double res = 0.0;

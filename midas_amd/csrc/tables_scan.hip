@@ -3,7 +3,7 @@
 // counts[row][4] -- the layout merge_sites.hip reads.  What midas_snps_tableset_read_counts does on the host's threads.
 //
 // A GROUP of members lies in one text buffer, every member at a multiple of 16 bytes.  The line index is built the way
-// sites_scan.hip and sam_scan.hip build theirs: line ends counted per 16-byte load, the library's exclusive scan, every end to its
+// sites_rows.h and sam_scan.hip build theirs: line ends counted per 16-byte load, the library's exclusive scan, every end to its
 // place.  Two things differ from a plain newline index, both because a member is a text of its own:
 //   * a word belongs to ONE member (found by bisection over the members' starts) and only its bytes below the member's ISIZE
 //     count: what lies between a member's end and the next member's start is never interpreted;

@@ -1,4 +1,4 @@
-// The text-matrix walker's parts that sites_scan.hip and genes_compare.hip share: a run of bytes of a tab-separated matrix
+// The text-matrix walker's parts that sites_rows.h and genes_compare.hip share: a run of bytes of a tab-separated matrix
 // uploaded as a chunk, its newline index (newlines counted per 16 bytes, the library's exclusive scan, newline k's position ->
 // ends[k]), the device buffer and event holders, and the popcount pair kernel over a bit matrix [sample][64 rows a word].
 // species_hits.hip and species_merge.hip take the index kernels and the exact one-multiply float() decoder from here too.
@@ -204,6 +204,16 @@ __global__ __launch_bounds__(256) void ss_pairs_kernel(const unsigned long long*
       const int gi = ti * kPairTile + ty + 16 * i, gj = tj * kPairTile + tx + 16 * j;
       if (gi <= gj && gj < S && sum[i][j]) atomicAdd(&both[(long long)gi * S + gj], (unsigned long long)sum[i][j]);
     }
+}
+
+// The word runs of a pair kernel's launch (its blockIdx.y): enough workgroups to fill the device when the tiles are few --
+// pair_blocks is the aim -- each run whole staging steps of `step` words (kPairRun, or the planes' own)
+struct PairRuns { long long runs, run_words; };
+PairRuns pair_runs(long long n_words, long long n_tiles, long long pair_blocks, int step) {
+  long long runs = std::max<long long>(1, std::min<long long>((pair_blocks + n_tiles - 1) / n_tiles, (n_words + step - 1) / step));
+  runs = std::min<long long>(runs, 65535);
+  const long long run_words = ((n_words + runs - 1) / runs + step - 1) / step * step;
+  return PairRuns{(n_words + run_words - 1) / run_words, run_words};
 }
 
 // device room for a chunk of cb bytes (the text padded to 16 and one terminator, the per-16-byte newline counts)

@@ -1,4 +1,4 @@
-"""Chosen tables for the per-site kernels (sites_scan.hip): every case puts rows or samples ON a decision of the site loop and
+"""Chosen tables for the per-site kernels (sites_rows.h, sites_call.h, sites_scan.hip, sites_strains.hip): every case puts rows or samples ON a decision of the site loop and
 one step to either side of it, where random tables almost never land.  Plain data and the searches that find it -- nothing
 here knows the kernels.  tests/test_site_cases_host.py asserts with the sequential model alone that every case sits where its
 name says; tests/test_gpu_site_borders.py holds the device to the model on them, bit for bit.

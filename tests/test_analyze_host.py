@@ -105,6 +105,13 @@ def test_every_sites_symbol_is_declared_exported_and_bound():
     from midas_amd import build
     assert 'sites_scan.hip' in build.SOURCES and 'sites_io.cpp' in build.SOURCES and 'text_numbers.h' in build.HEADERS
     assert '-ffp-contract=off' in build.SOURCE_FLAGS['sites_scan.hip']
+    # the row walker and the site step are headers: an edit rebuilds, and every file that compiles a copy keeps one rounding
+    assert 'sites_rows.h' in build.HEADERS and 'sites_call.h' in build.HEADERS
+    users = [s for s in build.SOURCES
+             if re.search(r'#include "sites_(rows|call)\.h"', open(os.path.join(ROOT, 'midas_amd', 'csrc', s), errors='replace').read())]
+    assert {'sites_scan.hip', 'sites_strains.hip', 'sites_trees.hip'} <= set(users)
+    for s in users:
+        assert '-ffp-contract=off' in build.SOURCE_FLAGS.get(s, []), s
 
 
 def test_the_golden_covers_what_it_must():

@@ -95,6 +95,18 @@ def test_malformed_cells_and_short_rows_are_reported_with_their_place(ctx, bad, 
     assert res['n_kept'] == 2
 
 
+def test_a_column_selected_twice_is_refused_even_where_there_is_no_row(ctx):
+    none, cols = np.zeros(0, np.uint8), np.array([0, 0])
+    calls = [lambda: ctx.sites_scan(none, none, none, cols, np.full(2, 10.0), 2, float('inf'), 0.5, 0.0, 0.0),
+             lambda: ctx.sites_id_markers(none, none, none, none, cols, 0.1, 3, 1),
+             lambda: ctx.sites_track_markers(none, none, none, cols, 0.1, 3),
+             lambda: ctx.sites_consensus_pairs(none, none, none, cols, np.full(2, 10.0), 2, float('inf'), 0.5, 0.0, 0.0)]
+    for call in calls:
+        with pytest.raises(abi.MidasSnpsError) as e:
+            call()
+        assert e.value.status == abi.ERR_INVALID_ARG and 'selected twice' in str(e.value) and e.value.bad is None
+
+
 def _species(tmp_path_factory, n_sites, n_samples, seed, n_genes):
     d = str(tmp_path_factory.mktemp("sp") / "species_1")
     synth.write_species_dir(d, n_sites, n_samples, seed=seed, n_genes=n_genes, block=7000)

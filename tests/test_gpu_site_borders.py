@@ -1,4 +1,4 @@
-"""The per-site kernels of sites_scan.hip on the GPU box, on the chosen tables of tests/site_cases.py: every decision of the site
+"""The per-site kernels (sites_rows.h, sites_call.h, sites_scan.hip, sites_strains.hip) on the GPU box, on the chosen tables of tests/site_cases.py: every decision of the site
 loop on its border and to either side of it, the pooled frequency at every change of the pairwise reduce's shape, the sums at
 every place a gene can change, the marker calls at their rounding cases and the device's own converters at the ends of their
 fast paths -- device against the sequential models, bit for bit, with one row group and with several.  Where the model raises
