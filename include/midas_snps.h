@@ -298,6 +298,12 @@ int32_t midas_snps_scan_u32(midas_snps_ctx* ctx, int64_t n, const uint32_t* in, 
  * pair the launch named as the result -- 0 the pair the input was uploaded to, 1 the other one.                             */
 int32_t midas_snps_sort_pairs(midas_snps_ctx* ctx, int64_t n, int32_t bits, int32_t value_kind, const uint32_t* key, const void* val,
                               uint32_t* out_key, void* out_val, int32_t* out_which, int32_t* out_guards_ok);
+/* midas_snps_mt19937_stream: the device's MT19937 generator (mt19937_stream.hip; snp_diversity.py --rand_reads) on host arrays
+ * (test aid).  From numpy's legacy state (key624, pos 0 .. 624) n_words words are generated, per_launch a launch (0: one launch):
+ * out_raw [n] the tempered words, out_flag [n] (nullable) 1 where (word & mask) <= bound with mask the smallest 2^j - 1 >= bound,
+ * out_masked [n] (nullable) word & mask; out_key624 / out_pos: the state behind the last word.                                 */
+int32_t midas_snps_mt19937_stream(midas_snps_ctx* ctx, const uint32_t* key624, int32_t pos, int64_t n_words, int64_t per_launch, int64_t bound,
+                                  uint32_t* out_raw, uint8_t* out_flag, uint32_t* out_masked, uint32_t* out_key624, int32_t* out_pos);
 /* Re-run the device packer over the batch's resident BAM-native arrays (the arrays batch_create uploaded, unchanged):
  * per read the CIGAR walk into gap-free match segments (pysam get_aligned_pairs(matches_only=True), reached from
  * midas/run/snps.py:194-199), the clip structure (query_alignment_sequence, :145), floor(mean(query_qualities))
@@ -1014,6 +1020,32 @@ int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_byt
                          const int64_t* iparams8, double* out_pi, int64_t* out_snps, int64_t* out_sites, int64_t* out_depth,
                          uint8_t* out_seq, double* dump_freq, int64_t* dump_depth, uint8_t* dump_keep, double* dump_pooled,
                          int64_t* out_stats16, float* out_ms8);
+
+/* midas_sites_scan with snp_diversity.py's --rand_reads N [--replace_reads] (GenomicSite.resample_reads): the arguments of
+ * midas_sites_scan, then rand_reads = N (1 .. 2^31 - 1), replace, numpy's global legacy generator as np.random.get_state() gives
+ * it (mt_key 624 words, mt_pos 0 .. 624), the state the reference's loop would leave it in (mt_key_out, mt_pos_out; they may be
+ * mt_key's memory) and out_draw8 (nullable).  iparams8[7]: the most raw words one launch of the generator makes (0: chosen; the
+ * outputs and the returned state depend neither on it nor on group_rows).  MIDAS_SITES_SEQ is MIDAS_SNPS_ERR_INVALID_ARG:
+ * call_consensus.py has no such option.
+ * A site is resampled when it is retained (max_sites counted) and its pooled frequency is > 0.  There every sample, kept or
+ * not, gets depth N, and a cell with 0 < f < 1 (after rounding under MIDAS_SITES_ROUND: none) gets f = k / N with
+ * count_minor = round(f * N), half to even, and k = count_minor without replacement, or with replacement the number of the
+ * cell's N draws below count_minor.  The draws are np.random.randint(0, N, N)'s: 32-bit MT19937 words ANDed with the smallest
+ * 2^j - 1 >= N - 1, those <= N - 1 accepted; the c-th cell that draws, sites in file order and samples in theirs, takes accepted
+ * words [c N, (c + 1) N).  N = 1 draws nothing.  The site's pooled frequency is then formed again over the same kept samples,
+ * and the sums see the new cells.  The state returned stands right behind the last accepted word used (rejected words before it
+ * are consumed, none after it); without replacement, with N = 1 or when no cell draws it is the state given.
+ * dump_*: the cells and pooled frequencies after resampling.  out_stats16 as midas_sites_scan, and [11] sites resampled,
+ * [12] cells with 0 < f < 1 among them (the cells that draw, with replacement and N > 1).  out_draw8: [0] raw words generated,
+ * [1] accepted words used, [2] raw words consumed (to the returned state), then ms of [3] eligibility, [4] generation,
+ * [5] compaction, [6] resampling, [7] the pooled frequencies (device events; midas_sites_scan's out_ms8 holds the rest).       */
+int32_t midas_sites_scan_resampled(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                   int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                                   const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                                   const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps, int64_t* out_sites,
+                                   int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth, uint8_t* dump_keep,
+                                   double* dump_pooled, int64_t* out_stats16, float* out_ms8, int64_t rand_reads, int32_t replace,
+                                   const uint32_t* mt_key, int32_t mt_pos, uint32_t* mt_key_out, int32_t* mt_pos_out, double* out_draw8);
 
 /* ---- strain_tracking.py: marker alleles (id_markers) and their sharing between all pairs of samples (track_markers) ----------
  * Both walk the two matrices as midas_sites_scan does (same text, same cell parsers, same row groups, same place of a bad row

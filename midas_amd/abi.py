@@ -379,6 +379,8 @@ def load_library(build_if_missing: bool = True):
         'midas_sites_tables_close': (None, [vp]),
         'midas_sites_parse_cell': (i32, [i32, C.c_char_p, i64, vp]),
         'midas_sites_scan': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15),
+        'midas_sites_scan_resampled': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15 + [i64, i32, vp, i32, vp, vp, vp]),
+        'midas_snps_mt19937_stream': (i32, [vp, vp, i32, i64, i64, i64, vp, vp, vp, vp, vp]),
         'midas_sites_id_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, vp, i32] + [vp] * 6),
         'midas_sites_track_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, i32] + [vp] * 6),
         'midas_sites_consensus_pairs': (i32, [vp, vp, i64, vp, i64, i64, vp, i32] + [vp] * 8),
@@ -424,7 +426,7 @@ EXPORTED_SYMBOLS = [
     'midas_snps_batch_enable_timing', 'midas_snps_batch_timing', 'midas_snps_batch_time_pileup_only',
     'midas_snps_batch_stats_to_device', 'midas_snps_batch_pack', 'midas_snps_batch_fetch_packed',
     'midas_snps_batch_select_path', 'midas_snps_set_default_path', 'midas_snps_copy_rate', 'midas_snps_stream_rates', 'midas_snps_calibration_pass', 'midas_snps_set_pad_rule', 'midas_snps_set_row_coder',
-    'midas_snps_row_coder_counts', 'midas_snps_rows_code', 'midas_snps_scan_u32', 'midas_snps_sort_pairs',
+    'midas_snps_row_coder_counts', 'midas_snps_rows_code', 'midas_snps_scan_u32', 'midas_snps_sort_pairs', 'midas_snps_mt19937_stream',
     'midas_snps_batch_pack_timing', 'midas_snps_batch_fetch_index',
     'midas_bam_open', 'midas_bam_close', 'midas_bam_write', 'midas_bam_n_refs', 'midas_bam_ref', 'midas_bam_load', 'midas_bam_copy', 'midas_bam_columns',
     'midas_bam_open_slice', 'midas_bam_slice_facts', 'midas_bam_slice_marks', 'midas_bam_load_ranges',
@@ -452,7 +454,7 @@ EXPORTED_SYMBOLS = [
 ]
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
-                 'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_id_markers', 'midas_sites_track_markers',
+                 'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_scan_resampled', 'midas_sites_id_markers', 'midas_sites_track_markers',
                  'midas_sites_write_markers', 'midas_sites_write_pairs', 'midas_sites_consensus_pairs']
 # snp_trees.py (neighbour joining over the consensus distances): bound above like the rest, listed by itself
 TREE_SYMBOLS = ['midas_nj_tree']
@@ -1618,6 +1620,19 @@ class Context:
                                                     p(key), p(val), p(out_key), p(out_val), C.byref(which), C.byref(ok)))
         return out_key, out_val, which.value, ok.value == 1
 
+    def mt19937_stream(self, key, pos: int, n_words: int, per_launch: int = 0, bound: int = 0xFFFFFFFF):
+        """The device's MT19937 generator from numpy's legacy state (key uint32 [624], pos), n_words words, per_launch a launch
+        (midas_snps_mt19937_stream; test aid).  -> (raw uint32 [n], accepted uint8 [n], masked uint32 [n], key uint32 [624], pos)."""
+        key = np.ascontiguousarray(key, np.uint32).reshape(-1)
+        assert key.size == 624
+        n = int(n_words)
+        raw, flag, masked = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32)
+        key_out, pos_out = np.zeros(624, np.uint32), C.c_int32(-1)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.midas_snps_mt19937_stream(self._h, p(key), int(pos), n, int(per_launch), int(bound), p(raw), p(flag), p(masked),
+                                                        p(key_out), C.byref(pos_out)))
+        return raw[:n], flag[:n], masked[:n], key_out, pos_out.value
+
     def copy_rate(self, nbytes: int = 1 << 30, reps: int = 10) -> float:
         """GB/s (read + written) of a device-to-device copy with the library's 16-bytes-per-lane copy kernel."""
         out = C.c_double(0.0)
@@ -1898,14 +1913,20 @@ class Context:
     def sites_scan(self, freq_text, depth_text, site_mask, sample_col, mean_depth, site_depth: int, site_ratio: float,
                    allele_support: float, site_prev: float, site_maf: float, snp_maf: float = 0.01, max_sites: int = -1,
                    flags: int = 0, site_gene=None, n_genes: int = 0, minor=None, major=None, group_rows: int = 0,
-                   chunk_bytes: int = 0, dump: bool = False, dump_keep: bool = False):
+                   chunk_bytes: int = 0, dump: bool = False, dump_keep: bool = False, rand_reads: int = 0, replace_reads: bool = False,
+                   np_state=None, draw_chunk: int = 0):
         """midas_sites_scan(): the per-site loop of snp_diversity.py / call_consensus.py over the text rows of snps_freq.txt
         and snps_depth.txt (uint8 arrays, header line excluded).  site_mask [N] uint8; sample_col / mean_depth [S].  -> dict
         (n_sites, n_kept, side_freq, side_depth, groups, no_gene, ms [8]; with SITES_SUMS pi f64, snps / sites / depth i64
         [chains, genes]; with SITES_SEQ seq uint8 [S, n_kept]; with dump: freq f64 / depthv i64 [S, n_sites], keep uint8 and
         pooled f64 [n_sites]; with dump_keep: keep alone).  A malformed row raises MidasSnpsError with .bad = (matrix 1|2, data row, sample or -1);
         a site the reference raises on, with .bad = (3, data row, sample): a frequency that is not finite under SITES_ROUND, or
-        (6, data row, -1): kept samples whose depths sum to 0 under SITES_WEIGHT."""
+        (6, data row, -1): kept samples whose depths sum to 0 under SITES_WEIGHT.
+        rand_reads N > 0: midas_sites_scan_resampled(), snp_diversity.py's --rand_reads N [--replace_reads] from numpy's legacy
+        generator state np_state (np.random.get_state(); read, not advanced: None takes the global one).  The result also holds
+        np_state = the state the reference's loop leaves (for np.random.set_state), n_resampled sites, n_drew cells, raw_made /
+        accepted_used / raw_consumed words and draw_ms [5] (eligibility, generation, compaction, resampling, pooled frequencies);
+        draw_chunk: the raw words a launch of the generator makes at most (0: chosen; no output depends on it)."""
         ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
         dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
         mask = np.ascontiguousarray(site_mask, dtype=np.uint8)
@@ -1924,7 +1945,7 @@ class Context:
         ma = np.ascontiguousarray(major, dtype=np.uint8) if flags & SITES_SEQ else None
         assert mi is None or (mi.shape[0] == N and ma.shape[0] == N)
         fp = np.array([site_ratio, allele_support, site_prev, site_maf, snp_maf], np.float64)
-        ip = np.array([site_depth, max_sites, flags, G if per_gene else 0, group_rows, chunk_bytes, cap, 0], np.int64)
+        ip = np.array([site_depth, max_sites, flags, G if per_gene else 0, group_rows, chunk_bytes, cap, draw_chunk if rand_reads else 0], np.int64)
         out = {}
         if flags & SITES_SUMS:
             out.update(pi=np.zeros((chains, G), np.float64), snps=np.zeros((chains, G), np.int64), sites=np.zeros((chains, G), np.int64),
@@ -1937,11 +1958,21 @@ class Context:
             out.update(keep=np.zeros(N, np.uint8))
         stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
         p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
-        st = self._lib.midas_sites_scan(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], N, p(mask), p(gene), p(mi), p(ma), S, p(cols),
-                                        p(mean), p(fp), p(ip), p(out.get('pi')), p(out.get('snps')), p(out.get('sites')),
-                                        p(out.get('depth')), p(seq), p(out.get('freq')), p(out.get('depthv')), p(out.get('keep')),
-                                        p(out.get('pooled')), p(stats), p(ms))
+        common = (self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], N, p(mask), p(gene), p(mi), p(ma), S, p(cols), p(mean), p(fp), p(ip),
+                  p(out.get('pi')), p(out.get('snps')), p(out.get('sites')), p(out.get('depth')), p(seq), p(out.get('freq')),
+                  p(out.get('depthv')), p(out.get('keep')), p(out.get('pooled')), p(stats), p(ms))
+        if rand_reads:
+            state = np_state if np_state is not None else np.random.get_state()
+            (_, _), (key, pos) = mt_states(np_state=state)
+            key_out, pos_out, draw = np.zeros(624, np.uint32), C.c_int32(-1), np.zeros(8, np.float64)
+            st = self._lib.midas_sites_scan_resampled(*common, int(rand_reads), int(bool(replace_reads)), p(key), pos, p(key_out),
+                                                      C.byref(pos_out), p(draw))
+        else:
+            st = self._lib.midas_sites_scan(*common)
         self._check_bad(st, stats)
+        if rand_reads:
+            out.update(np_state=(state[0], key_out, pos_out.value) + tuple(state[3:]), n_resampled=int(stats[11]), n_drew=int(stats[12]),
+                       raw_made=int(draw[0]), accepted_used=int(draw[1]), raw_consumed=int(draw[2]), draw_ms=draw[3:].tolist())
         n = int(stats[0])
         out.update(n_sites=n, n_kept=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]), groups=int(stats[7]),
                    no_gene=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), ms=ms.tolist())

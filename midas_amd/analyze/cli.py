@@ -6,6 +6,7 @@ import os
 import sys
 
 INF = float('Inf')
+MAX_RAND_READS = 2 ** 31 - 1
 
 SAMPLE_OPTIONS = [
     (['--sample_depth'], dict(dest='sample_depth', type=float, default=0.0, metavar='FLOAT', help="samples with at least this mean_coverage (0.0)")),
@@ -37,12 +38,20 @@ DIVERSITY_OPTIONS = [
     (['--sample_type'], dict(choices=['per-sample', 'pooled-samples'], default='per-sample',
                              help="one result per sample, or one for the samples pooled (per-sample)")),
     (['--weight_by_depth'], dict(action='store_true', default=False, help="pooled-samples: weight each sample by its depth at the site")),
-    (['--rand_reads'], dict(type=int, metavar='INT', help="(resampling N reads per site and sample is not part of this build)")),
-    (['--replace_reads'], dict(action='store_true', default=False, help="(not part of this build)")),
+    (['--rand_reads'], dict(type=int, metavar='INT',
+                            help="rarefy: at every retained variable site give each sample N reads, round(freq x N) of them the minor\n"
+                                 "allele, and compute from these; --site_depth is raised to N (numpy's global random stream)")),
+    (['--replace_reads'], dict(action='store_true', default=False,
+                               help="with --rand_reads: draw the N reads with replacement (without, the N reads are all of them)")),
     (['--rand_samples'], dict(type=int, metavar='INT', help="use a random subset of N samples (numpy's global random stream)")),
     (['--rand_sites'], dict(type=float, metavar='FLOAT', help="use a random share X of the sites (Python's global random stream)")),
     (['--snp_maf'], dict(type=float, metavar='FLOAT', default=0.01, help="a site is a SNP at or above this minor allele frequency (0.01)")),
     (['--consensus'], dict(action='store_true', default=False, help="round every frequency to 0 or 1 before anything is computed from it")),
+]
+
+SEED_OPTIONS = [
+    (['--seed'], dict(type=int, metavar='INT', help="seed numpy's and Python's global random streams with INT first: --rand_samples,\n"
+                                                    "--rand_sites and --rand_reads then give the same result every run")),
 ]
 
 DEVICE_OPTIONS = [
@@ -71,9 +80,14 @@ def diversity_arguments(argv=None):
                      "  snp_diversity.py OUT/species_1 --genomic_type per-gene --sample_type pooled-samples --locus_type CDS --out pi.txt\n"
                      "  snp_diversity.py OUT/species_1 --sample_type pooled-samples --locus_type CDS --site_type 4D --out pi.txt\n"
                      "  snp_diversity.py OUT/species_1 --max_sites 10000 --out pi.txt",
-                     [("Diversity options", DIVERSITY_OPTIONS), ("Sample filters", SAMPLE_OPTIONS), ("Site filters", SITE_OPTIONS),
+                     [("Diversity options", DIVERSITY_OPTIONS + SEED_OPTIONS), ("Sample filters", SAMPLE_OPTIONS), ("Site filters", SITE_OPTIONS),
                       ("Device", DEVICE_OPTIONS)])
-    return vars(parser.parse_args(argv))
+    args = vars(parser.parse_args(argv))
+    if args['rand_reads'] is not None and not 0 <= args['rand_reads'] <= MAX_RAND_READS:
+        parser.error("--rand_reads must be between 0 and %d" % MAX_RAND_READS)
+    if args['rand_reads']:          # (parse_arguments: a sample counts at a site only with N reads to pick from)
+        args['site_depth'] = max(args['site_depth'], args['rand_reads'])
+    return args
 
 
 def consensus_arguments(argv=None):
@@ -128,16 +142,20 @@ def _common_checks(args):
         _exit("--fract_cov must be between 0 and 1")
 
 
-def check_diversity_args(args):
+def check_diversity_args(args, resampling=False):
     """check_args of snp_diversity.py, in its order.  Its --rand_reads comparison cannot run under Python 3 without the
-    option; here the option itself is out: resampling reads needs numpy's legacy random stream per (site, sample)."""
-    if args['rand_reads'] is not None or args['replace_reads']:
+    option, and with it never fires: diversity_arguments has raised --site_depth to --rand_reads.  It keeps its place.
+    resampling: what follows runs --rand_reads / --replace_reads (diversity.run_pipeline does; the command passes True).  A
+    caller that does not say so gets the answer these options had before the device could resample: the exit below."""
+    if not resampling and (args['rand_reads'] is not None or args['replace_reads']):
         _exit("--rand_reads / --replace_reads are not part of this build")
     if not os.path.isdir(args['indir']):
         _exit("Specified input directory '%s' does not exist" % args['indir'])
     if args['site_depth'] < 2:
         _exit("--site_depth must be >=2 to calculate nucleotide variation")
     _common_checks(args)
+    if args['rand_reads'] and args['rand_reads'] > args['site_depth'] and not args['replace_reads']:
+        _exit("--rand_reads cannot exceed --site_depth when --replace_reads=False")
     if args['rand_sites'] and (args['rand_sites'] < 0 or args['rand_sites'] > 1):
         _exit("--rand_sites must be between 0 and 1")
     if args['locus_type'] != 'CDS' and args['genomic_type'] == 'per-gene':

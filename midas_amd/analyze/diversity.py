@@ -3,7 +3,9 @@
 Mirrors scripts/snp_diversity.py: compute_snp_diversity (:182-258) becomes one device call -- the matrices
 parsed, every site's samples flagged, pooled and filtered, and pi / snps / sites / depth summed in site order per chain -- and
 write_pi (:260-297) formats the chains as str() does.  The sequential rules that need no frequency (--site_list walked with one
-cursor, --rand_sites drawn with random.uniform per site that gets past the list) are applied here, as a mask.
+cursor, --rand_sites drawn with random.uniform per site that gets past the list) are applied here, as a mask.  --rand_reads
+hands numpy's global generator state to the device call, which resamples the reads of every retained variable site from it, and
+takes the state back that the reference's loop would have left.
 """
 import random
 import sys
@@ -44,8 +46,15 @@ def compute(args, tables, samples, ctx):
     flags = abi.SITES_SUMS | (abi.SITES_POOLED if pooled else 0) | (abi.SITES_PER_GENE if per_gene else 0) | \
         (abi.SITES_WEIGHT if args['weight_by_depth'] else 0) | (abi.SITES_ROUND if args['consensus'] else 0)
     mask, n = site_mask(tables, args)
+    kw = {}
+    if args.get('rand_reads'):
+        # numpy's global stream as it stands when the site loop begins: the device continues it, and the loop's end state goes back
+        kw = dict(rand_reads=int(args['rand_reads']), replace_reads=bool(args['replace_reads']), np_state=np.random.get_state(),
+                  draw_chunk=int(args.get('draw_chunk', 0) or 0))
     res = S.scan(ctx, tables, samples, mask, n, args, flags, snp_maf=float(args['snp_maf']),
-                 site_gene=tables.gene[:n] if per_gene else None, n_genes=tables.n_genes)
+                 site_gene=tables.gene[:n] if per_gene else None, n_genes=tables.n_genes, **kw)
+    if kw:
+        np.random.set_state(res['np_state'])
     if res['no_gene']:
         sys.exit("\nError: %s/snps_info.txt: %d retained sites have no gene_id (--genomic_type per-gene)\n" % (tables.dir, res['no_gene']))
     return res
@@ -82,7 +91,11 @@ def write_pi(args, tables, samples, res):
 
 
 def run_pipeline(args, make_context=S.device_context):
-    """scripts/snp_diversity.py:299-315.  make_context: tests substitute a CPU double of the device."""
+    """scripts/snp_diversity.py:299-315.  make_context: tests substitute a CPU double of the device.  --seed: both global random
+    streams are seeded before anything draws from them."""
+    if args.get('seed') is not None:
+        np.random.seed(args['seed'])
+        random.seed(args['seed'])
     print("\nSelecting subset of samples...")
     tables = S.open_tables(args['indir'])
     samples = S.fetch_samples(tables, args['sample_depth'], args['fract_cov'], args['max_samples'], args['keep_samples'],

@@ -254,6 +254,16 @@ hipError_t launch_sort_pairs_u32(uint32_t* key_a, uint32_t* val_a, uint32_t* key
 hipError_t launch_sort_pairs_f64(uint32_t* key_a, double* val_a, uint32_t* key_b, double* val_b, long long n, int bits, uint32_t* scratch,
                                  hipStream_t s, uint32_t** key_sorted, double** val_sorted);
 
+// mt19937_stream.hip: numpy's legacy MT19937 stream continued on the device by one workgroup.  state625: 624 key words and the
+// position (device memory, advanced by the launch).  n words are written: raw (tempered; nullable), flag = ((w & mask) <= bound),
+// masked = w & mask (both nullable together)
+hipError_t launch_mt_stream(uint32_t* state625, long long n, uint32_t* raw, uint32_t* flag, uint32_t* masked, uint32_t mask, uint32_t bound,
+                            hipStream_t s);
+// the accepted words of a launch in stream order: accepted[place[i]] = masked[i], accepted_at[place[i]] = i where flag[i]
+// (place: the exclusive scan of flag)
+hipError_t launch_mt_scatter(const uint32_t* flag, const uint32_t* place, const uint32_t* masked, long long n, uint32_t* accepted,
+                             uint32_t* accepted_at, hipStream_t s);
+
 // rows_deflate.hip: the table's rows formatted and deflated on the device, one gzip member (<= 16 384 rows of one contig) at a time
 struct RowsMember {
   long long site0;                 // the member's first site in the batch's counts / alleles

@@ -100,11 +100,34 @@ __device__ double pairwise_sum(KeptIter& it, long long n) {
   return ret;
 }
 
+// compute_pooled_maf over the `count` kept samples of one site (fv, dv, cell point at the site's first cell): the weighted form
+// is sum(d * f) / sum(d) left to right, the unweighted one numpy's mean.  *zero_depth: the weighted form has no value, the kept
+// depths sum to 0.  The site kernel calls it, and so does the pass that resamples a site's reads (sites_resample.h).
+__device__ double site_pooled(const double* fv, const long long* dv, const uint8_t* cell, long long stride, int S, long long count,
+                              int weight, int round_freq, bool* zero_depth) {
+  if (count == 0) return 0.0;
+  if (!weight) {
+    KeptIter it{fv, cell, stride, 0, round_freq};
+    return __ddiv_rn(pairwise_sum(it, count), (double)count);
+  }
+  long long dsum = 0;
+  double msum = 0.0;
+  for (int s = 0; s < S; ++s) {
+    const long long at = (long long)s * stride;
+    if (!(cell[at] & 1)) continue;
+    const double f = fv[at];
+    const long long d = dv[at];
+    dsum += d;
+    msum += (double)d * (round_freq ? rint(f) + 0.0 : f);
+  }
+  if (dsum == 0) { *zero_depth = true; return 0.0; }
+  return __ddiv_rn(msum, (double)dsum);
+}
+
 __global__ __launch_bounds__(256) void ss_site_kernel(SiteP p) {
   const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
   if (r >= p.g) return;
-  long long count = 0, dsum = 0;
-  double msum = 0.0;
+  long long count = 0;
   unsigned long long why = 0;                   // the first sample whose frequency round() refuses, kept or not
   for (int s = 0; s < p.S; ++s) {
     const long long at = (long long)s * p.stride + r;
@@ -118,25 +141,11 @@ __global__ __launch_bounds__(256) void ss_site_kernel(SiteP p) {
     if (1.0 - f > m) m = 1.0 - f;
     if (m < p.allele_support) keep = false;
     p.cell[at] = keep ? 1 : 0;
-    if (keep) {
-      ++count;
-      if (p.weight) {
-        const double f2 = p.round_freq ? rint(f) + 0.0 : f;
-        dsum += d;
-        msum += (double)d * f2;
-      }
-    }
+    if (keep) ++count;
   }
-  double pooled = 0.0;
-  if (count > 0) {
-    if (p.weight) {
-      if (dsum == 0) { if (why == 0) why = kSiteZeroDepth; }
-      else pooled = __ddiv_rn(msum, (double)dsum);
-    } else {
-      KeptIter it{p.fv + r, p.cell + r, p.stride, 0, p.round_freq};
-      pooled = __ddiv_rn(pairwise_sum(it, count), (double)count);
-    }
-  }
+  bool zero_depth = false;
+  const double pooled = site_pooled(p.fv + r, p.dv + r, p.cell + r, p.stride, p.S, count, p.weight, p.round_freq, &zero_depth);
+  if (zero_depth && why == 0) why = kSiteZeroDepth;
   bool k = p.mask[r] != 0;
   if (!p.mask_only) {
     const double prev = __ddiv_rn((double)count, (double)p.S);

@@ -3,6 +3,8 @@
 //
 //   chunks, index, parse   the rows of the two matrices, a group at a time (RowGroups, sites_rows.h)
 //   site, order            the site's decisions and --max_sites (SiteStep, sites_call.h)
+//   resample --rand_reads: the reads of every retained variable site drawn again, its pooled frequency formed again
+//            (sites_resample.h; midas_sites_scan_resampled only)
 //   sums     one wave a chain (a sample, or the pool): 64 rows loaded coalesced, then folded in lane order -- the fp64 sum
 //            is the sequential one, bit for bit; per-gene chains switch accumulators where the gene index changes.
 //            Accumulators live in device memory and carry from group to group
@@ -10,6 +12,7 @@
 // strain_tracking.py walks the same rows in sites_strains.hip, snp_trees.py the same rows and site decisions in sites_trees.hip.
 // This file is compiled with -ffp-contract=off (build.py): 2*f*(1-f) and d*f round as the interpreter rounds them.
 #include "sites_call.h"
+#include "sites_resample.h"
 
 namespace midas {
 namespace {
@@ -105,17 +108,24 @@ __global__ __launch_bounds__(256) void ss_seq_kernel(const double* fv, const lon
   }
 }
 
-}  // namespace
-}  // namespace midas
+// --rand_reads as midas_sites_scan_resampled takes it; midas_sites_scan passes none
+struct ResampleArgs {
+  int64_t rand_reads;
+  int32_t replace;
+  const uint32_t* mt_key;
+  int32_t mt_pos;
+  uint32_t* mt_key_out;
+  int32_t* mt_pos_out;
+  double* out_draw8;
+};
 
-using namespace midas;
-
-extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
-                                    int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
-                                    const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
-                                    const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
-                                    int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
-                                    uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8) {
+// the two entry points' common body
+int32_t sites_scan_body(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                        int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                        const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                        const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
+                        int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
+                        uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8, const ResampleArgs* ra) {
   if (!mean_depth || !fparams5 || !iparams8 || (n_sites_max > 0 && !site_mask)) return MIDAS_SNPS_ERR_INVALID_ARG;
   const long long site_depth = iparams8[0], max_sites = iparams8[1], flags = iparams8[2], seq_cap = iparams8[6];
   const long long n_genes_in = iparams8[3];
@@ -143,7 +153,8 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
   if (n_sites_max == 0) return MIDAS_SNPS_OK;
   SS_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const long long per_row = (long long)S * (8 + 8 + 1 + 2 * (long long)sizeof(SideCell) + (want_seq ? 1 : 0)) + 4 + 4 + 4 + 8 + 1 + 8 + 8;
+  const long long per_row = (long long)S * (8 + 8 + 1 + 2 * (long long)sizeof(SideCell) + (want_seq ? 1 : 0)) + 4 + 4 + 4 + 8 + 1 + 8 + 8 +
+                            (ra ? ResampleStep::per_row(S) : 0);
   SsBufs dev;
   SsEvents ev;
   float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // upload, index, parse, site, order, sums, seq, download
@@ -157,6 +168,12 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
   SiteStep site(ctx, rg, site_mask, site_depth, max_sites, fparams5, weight, round_freq, mask_only);
   {
     const int32_t rc = site.init(mean_depth, true);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
+  std::unique_ptr<ResampleStep> rs;
+  if (ra) {
+    rs.reset(new ResampleStep(ctx, rg, site, ra->rand_reads, ra->replace));
+    const int32_t rc = rs->init(iparams8[7], ra->mt_key, ra->mt_pos);
     if (rc != MIDAS_SNPS_OK) return rc;
   }
   const long long G = rg.G;
@@ -203,6 +220,10 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
       const int32_t rc = site.run(g);
       if (rc != MIDAS_SNPS_OK) return rc;
     }
+    if (rs) {
+      const int32_t rc = rs->run(g);
+      if (rc != MIDAS_SNPS_OK) return rc;
+    }
     if (want_sums) {
       SumP q;
       q.fv = pooled ? site.d_pooled : d_fv; q.dv = d_dv; q.cell = site.d_cell; q.final_keep = site.d_final; q.gene = d_gene; q.g = g;
@@ -221,7 +242,15 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
     SS_TRY(hipStreamSynchronize(st));
     SS_TRY(rg.lap(3, 4, 3));
     SS_TRY(rg.lap(4, 5, 4));
-    SS_TRY(rg.lap(5, 6, 5));
+    if (rs) {                                   // (the sums start behind the resampling pass, not behind the order)
+      float t = 0.f;
+      SS_TRY(hipEventElapsedTime(&t, rs->e[7], ev.e[6]));
+      ms[5] += t;
+      const int32_t rc = rs->collect();
+      if (rc != MIDAS_SNPS_OK) return rc;
+    } else {
+      SS_TRY(rg.lap(5, 6, 5));
+    }
     SS_TRY(rg.lap(6, 7, 6));
     {
       const int32_t rc = site.check_rows();
@@ -259,6 +288,47 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
   SS_TRY(hipStreamSynchronize(st));
   out_stats16[1] = site.kept;
   out_stats16[8] = (int64_t)no_gene;
+  if (rs) {
+    const int32_t rc = rs->finish(ra->mt_key_out, ra->mt_pos_out, ra->out_draw8, out_stats16);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
   sites_end(rg, out_ms8);
   return MIDAS_SNPS_OK;
+}
+
+}  // namespace
+}  // namespace midas
+
+using namespace midas;
+
+extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                    int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                                    const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                                    const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
+                                    int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
+                                    uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8) {
+  return sites_scan_body(ctx, freq, freq_bytes, depth, depth_bytes, n_sites_max, site_mask, site_gene, minor, major, n_samples, sample_col,
+                         mean_depth, fparams5, iparams8, out_pi, out_snps, out_sites, out_depth, out_seq, dump_freq, dump_depth, dump_keep,
+                         dump_pooled, out_stats16, out_ms8, nullptr);
+}
+
+extern "C" int32_t midas_sites_scan_resampled(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                              int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                                              const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                                              const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
+                                              int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
+                                              uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8, int64_t rand_reads,
+                                              int32_t replace, const uint32_t* mt_key, int32_t mt_pos, uint32_t* mt_key_out, int32_t* mt_pos_out,
+                                              double* out_draw8) {
+  if (rand_reads < 1 || rand_reads > kDrawMaxReads || !mt_key || mt_pos < 0 || mt_pos > 624 || !mt_key_out || !mt_pos_out || !iparams8 ||
+      iparams8[7] < 0 || (iparams8[2] & MIDAS_SITES_SEQ))
+    return MIDAS_SNPS_ERR_INVALID_ARG;
+  // (an early return of the body -- no sites, an error -- leaves the stream where it was)
+  for (int i = 0; i < 624; ++i) mt_key_out[i] = mt_key[i];
+  *mt_pos_out = mt_pos;
+  if (out_draw8) for (int i = 0; i < 8; ++i) out_draw8[i] = 0.0;
+  const ResampleArgs ra{rand_reads, replace, mt_key, mt_pos, mt_key_out, mt_pos_out, out_draw8};
+  return sites_scan_body(ctx, freq, freq_bytes, depth, depth_bytes, n_sites_max, site_mask, site_gene, minor, major, n_samples, sample_col,
+                         mean_depth, fparams5, iparams8, out_pi, out_snps, out_sites, out_depth, out_seq, dump_freq, dump_depth, dump_keep,
+                         dump_pooled, out_stats16, out_ms8, &ra);
 }

@@ -2,8 +2,8 @@
 """snp_diversity.py -- nucleotide diversity and SNP density from one `merge_midas.py snps` directory, on MI355X.
 
 Drop-in for the reference's scripts/snp_diversity.py: same positional argument, option names, defaults and output table.
-The matrices are parsed and reduced on the device (midas_amd/analyze/diversity.py).  --rand_reads / --replace_reads are not
-part of this build.
+The matrices are parsed and reduced on the device (midas_amd/analyze/diversity.py), --rand_reads / --replace_reads included:
+the device continues numpy's own random stream.  --seed INT (not in the reference) seeds both global streams first.
 """
 import os
 import sys
@@ -15,7 +15,7 @@ if HERE not in sys.path:
 if __name__ == '__main__':
     from midas_amd.analyze import cli
     args = cli.diversity_arguments()
-    cli.check_diversity_args(args)
+    cli.check_diversity_args(args, resampling=True)
     cli.print_copyright()
     cli.print_args(args, 'snp_diversity.py')
     from midas_amd.analyze import diversity
