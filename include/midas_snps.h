@@ -1047,6 +1047,23 @@ int32_t midas_sites_scan_resampled(midas_snps_ctx* ctx, const char* freq, int64_
                                    double* dump_pooled, int64_t* out_stats16, float* out_ms8, int64_t rand_reads, int32_t replace,
                                    const uint32_t* mt_key, int32_t mt_pos, uint32_t* mt_key_out, int32_t* mt_pos_out, double* out_draw8);
 
+/* midas_sites_scan's sums once per site class, in one pass over the rows (snp_pnps.py: class 0 the 1D sites, class 1 the 4D
+ * sites): the arguments of midas_sites_scan, then site_class[i] = the class of site i and n_classes (1 .. 4).  With n_classes 1
+ * site_class may be NULL: every site is class 0.  A site with site_mask on and a class >= n_classes is
+ * MIDAS_SNPS_ERR_INVALID_ARG before anything runs; so is MIDAS_SITES_SEQ.  The class belongs to the sums alone: the rows, the
+ * cells, the site decisions, max_sites (retained sites of all classes together), the dumps and out_stats16 are midas_sites_scan's
+ * for the same site_mask, [8] included (a kept site without a gene counts once, whatever its class).
+ * out_pi / out_snps / out_sites / out_depth are [n_classes][chains][genes]: block c is what midas_sites_scan writes for the
+ * mask site_mask[i] && site_class[i] == c with the same retained sites -- pi the sequential sum in site order, bit for bit.       */
+#define MIDAS_SITES_MAX_CLASSES 4
+int32_t midas_sites_scan_classes(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                 int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                                 const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                                 const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps, int64_t* out_sites,
+                                 int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth, uint8_t* dump_keep,
+                                 double* dump_pooled, int64_t* out_stats16, float* out_ms8, const uint8_t* site_class,
+                                 int32_t n_classes);
+
 /* ---- strain_tracking.py: marker alleles (id_markers) and their sharing between all pairs of samples (track_markers) ----------
  * Both walk the two matrices as midas_sites_scan does (same text, same cell parsers, same row groups, same place of a bad row
  * in out_stats16[4..6]).  Rows [0, n_parse) are read and checked, rows [0, n_call) are called (n_call <= n_parse: the reference

@@ -380,6 +380,7 @@ def load_library(build_if_missing: bool = True):
         'midas_sites_parse_cell': (i32, [i32, C.c_char_p, i64, vp]),
         'midas_sites_scan': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15),
         'midas_sites_scan_resampled': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15 + [i64, i32, vp, i32, vp, vp, vp]),
+        'midas_sites_scan_classes': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15 + [vp, i32]),
         'midas_snps_mt19937_stream': (i32, [vp, vp, i32, i64, i64, i64, vp, vp, vp, vp, vp]),
         'midas_sites_id_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, vp, i32] + [vp] * 6),
         'midas_sites_track_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, i32] + [vp] * 6),
@@ -454,7 +455,7 @@ EXPORTED_SYMBOLS = [
 ]
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
-                 'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_scan_resampled', 'midas_sites_id_markers', 'midas_sites_track_markers',
+                 'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_scan_resampled', 'midas_sites_scan_classes', 'midas_sites_id_markers', 'midas_sites_track_markers',
                  'midas_sites_write_markers', 'midas_sites_write_pairs', 'midas_sites_consensus_pairs']
 # snp_trees.py (neighbour joining over the consensus distances): bound above like the rest, listed by itself
 TREE_SYMBOLS = ['midas_nj_tree']
@@ -1094,6 +1095,7 @@ def format_repr_f64(values) -> list:
 
 
 SITES_WEIGHT, SITES_ROUND, SITES_POOLED, SITES_PER_GENE, SITES_MASK_ONLY, SITES_SEQ, SITES_SUMS = 1, 2, 4, 8, 16, 32, 64
+SITES_MAX_CLASSES = 4        # MIDAS_SITES_MAX_CLASSES
 SITES_PAIR_TILE = 64         # MIDAS_SITES_PAIR_TILE: samples a side of the pair kernel's tile
 ALLELE_LETTERS = 'ATCG'      # the order of the allele codes and of the count columns of strain_tracking.py id_markers
 
@@ -1914,7 +1916,7 @@ class Context:
                    allele_support: float, site_prev: float, site_maf: float, snp_maf: float = 0.01, max_sites: int = -1,
                    flags: int = 0, site_gene=None, n_genes: int = 0, minor=None, major=None, group_rows: int = 0,
                    chunk_bytes: int = 0, dump: bool = False, dump_keep: bool = False, rand_reads: int = 0, replace_reads: bool = False,
-                   np_state=None, draw_chunk: int = 0):
+                   np_state=None, draw_chunk: int = 0, _classes=None):
         """midas_sites_scan(): the per-site loop of snp_diversity.py / call_consensus.py over the text rows of snps_freq.txt
         and snps_depth.txt (uint8 arrays, header line excluded).  site_mask [N] uint8; sample_col / mean_depth [S].  -> dict
         (n_sites, n_kept, side_freq, side_depth, groups, no_gene, ms [8]; with SITES_SUMS pi f64, snps / sites / depth i64
@@ -1926,7 +1928,8 @@ class Context:
         generator state np_state (np.random.get_state(); read, not advanced: None takes the global one).  The result also holds
         np_state = the state the reference's loop leaves (for np.random.set_state), n_resampled sites, n_drew cells, raw_made /
         accepted_used / raw_consumed words and draw_ms [5] (eligibility, generation, compaction, resampling, pooled frequencies);
-        draw_chunk: the raw words a launch of the generator makes at most (0: chosen; no output depends on it)."""
+        draw_chunk: the raw words a launch of the generator makes at most (0: chosen; no output depends on it).
+        _classes: sites_scan_classes' (site_class or None, n_classes)."""
         ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
         dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
         mask = np.ascontiguousarray(site_mask, dtype=np.uint8)
@@ -1948,8 +1951,9 @@ class Context:
         ip = np.array([site_depth, max_sites, flags, G if per_gene else 0, group_rows, chunk_bytes, cap, draw_chunk if rand_reads else 0], np.int64)
         out = {}
         if flags & SITES_SUMS:
-            out.update(pi=np.zeros((chains, G), np.float64), snps=np.zeros((chains, G), np.int64), sites=np.zeros((chains, G), np.int64),
-                       depth=np.zeros((chains, G), np.int64))
+            shape = (chains, G) if _classes is None else (max(int(_classes[1]), 0), chains, G)
+            out.update(pi=np.zeros(shape, np.float64), snps=np.zeros(shape, np.int64), sites=np.zeros(shape, np.int64),
+                       depth=np.zeros(shape, np.int64))
         seq = np.empty((S, max(cap, 1)), np.uint8) if flags & SITES_SEQ else None       # (max_sites 0: still a buffer to point at)
         if dump:
             out.update(freq=np.zeros((S, N), np.float64), depthv=np.zeros((S, N), np.int64), keep=np.zeros(N, np.uint8),
@@ -1967,6 +1971,10 @@ class Context:
             key_out, pos_out, draw = np.zeros(624, np.uint32), C.c_int32(-1), np.zeros(8, np.float64)
             st = self._lib.midas_sites_scan_resampled(*common, int(rand_reads), int(bool(replace_reads)), p(key), pos, p(key_out),
                                                       C.byref(pos_out), p(draw))
+        elif _classes is not None:
+            cls = None if _classes[0] is None else np.ascontiguousarray(_classes[0], dtype=np.uint8)
+            assert cls is None or cls.shape[0] == N
+            st = self._lib.midas_sites_scan_classes(*common, p(cls), int(_classes[1]))
         else:
             st = self._lib.midas_sites_scan(*common)
         self._check_bad(st, stats)
@@ -1983,6 +1991,16 @@ class Context:
         elif dump_keep:
             out['keep'] = out['keep'][:n]
         return out
+
+    def sites_scan_classes(self, freq_text, depth_text, site_mask, site_class, n_classes: int, sample_col, mean_depth, site_depth: int,
+                           site_ratio: float, allele_support: float, site_prev: float, site_maf: float, **kw):
+        """midas_sites_scan_classes(): sites_scan's sums once per site class in one pass.  site_class uint8 [N] (None with
+        n_classes 1: every site is class 0), n_classes 1 .. SITES_MAX_CLASSES; the other arguments and the result are sites_scan's
+        (no SITES_SEQ, no rand_reads), with pi / snps / sites / depth [n_classes, chains, genes]: block c is sites_scan's for
+        site_mask & (site_class == c) with the same retained sites.  n_kept, max_sites and no_gene count sites of every class."""
+        assert not kw.get('rand_reads')
+        return self.sites_scan(freq_text, depth_text, site_mask, sample_col, mean_depth, site_depth, site_ratio, allele_support, site_prev,
+                               site_maf, _classes=(site_class, n_classes), **kw)
 
     def _strains_call(self, fn, freq_text, depth_text, n_parse, n_call, site_arrays, sample_col, min_freq, iparams, out):
         ft = np.ascontiguousarray(freq_text, dtype=np.uint8)

@@ -1,4 +1,4 @@
-"""The command lines of snp_diversity.py, call_consensus.py, strain_tracking.py and compare_genes.py: the reference's option
+"""The command lines of snp_diversity.py, snp_pnps.py, call_consensus.py, strain_tracking.py and compare_genes.py: the reference's option
 names, defaults, check_args messages and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146,
 scripts/strain_tracking.py:10-137, scripts/compare_genes.py:10-65), shared where they agree."""
 import argparse
@@ -90,6 +90,35 @@ def diversity_arguments(argv=None):
     return args
 
 
+PNPS_LEFT_OUT = ('--rand_reads', '--replace_reads', '--locus_type', '--site_type')
+PNPS_MAX_SITES_HELP = ("stop after this many retained sites, 1D and 4D sites counted together (all): a quick test.\n"
+                       "Each of the two snp_diversity.py runs would stop at its own N-th site, so with this option the\n"
+                       "blocks are not theirs")
+
+
+def pnps_arguments(argv=None):
+    """snp_pnps.py: snp_diversity.py's options under their names and defaults, without --locus_type / --site_type (the classes
+    are CDS 1D and CDS 4D) and without --rand_reads / --replace_reads."""
+    helps = {'--max_sites': PNPS_MAX_SITES_HELP,
+             '--seed': "seed numpy's and Python's global random streams with INT first: --rand_samples and\n--rand_sites then give the same result every run"}
+    keep = lambda options: [(f, dict(kw, help=helps[f[0]]) if f[0] in helps else kw) for f, kw in options if f[0] not in PNPS_LEFT_OUT]
+    parser = _parser('snp_pnps.py',
+                     "pN/pS of one species from its merged SNP tables: nucleotide diversity and SNP density at the\n"
+                     "non-degenerate (1D) and at the four-fold degenerate (4D) sites of coding genes, and the ratio of the two\n"
+                     "pi_bp -- genome-wide or per gene, per sample or for the samples pooled.  Each block of columns is what\n"
+                     "`snp_diversity.py --locus_type CDS --site_type 1D` (or 4D) writes; both come from one pass over the matrices.\n"
+                     "--rand_reads / --replace_reads are not offered: the two separate runs draw the random stream over\n"
+                     "different sets of sites, so no single pass gives what both give.  Run `merge_midas.py snps` first.",
+                     "examples:\n"
+                     "  snp_pnps.py OUT/species_1 --sample_type pooled-samples --genomic_type per-gene --out pnps.txt\n"
+                     "  snp_pnps.py OUT/species_1 --site_prev 0.9 --site_depth 5 --out pnps.txt\n\n"
+                     "output: per chain depth (per-sample), sites, snps, pi, snps_kb, pi_bp with the suffix _1D, the same with _4D,\n"
+                     "and pnps = pi_bp_1D / pi_bp_4D (NA where either is NA or pi_bp_4D is 0.0)",
+                     [("pN/pS options", keep(DIVERSITY_OPTIONS + SEED_OPTIONS)), ("Sample filters", SAMPLE_OPTIONS), ("Site filters", keep(SITE_OPTIONS)),
+                      ("Device", DEVICE_OPTIONS)])
+    return vars(parser.parse_args(argv))
+
+
 def consensus_arguments(argv=None):
     parser = _parser('call_consensus.py',
                      "One consensus sequence per sample over the retained sites of a species, as a multi-FASTA (for trees).\n"
@@ -103,18 +132,23 @@ def consensus_arguments(argv=None):
 
 
 def print_args(args, script):
-    """The reference's argument block, line for line (its last but one line prints locus_type under the name site_type)."""
+    """The reference's argument block, line for line (its last but one line prints locus_type under the name site_type).
+    snp_pnps.py is not the reference's: the same block with the options it has."""
     rows = [("Command: %s" % ' '.join(sys.argv)), "Script: %s" % script, "Input directory: %s" % args['indir'], "Output file: %s" % args['out']]
     blocks = []
     if script == 'snp_diversity.py':
         blocks.append(("Diversity options:", ['genomic_type', 'sample_type', 'weight_by_depth', 'rand_reads', 'replace_reads', 'rand_samples',
                                               'rand_sites', 'snp_maf', 'consensus']))
+    if script == 'snp_pnps.py':
+        blocks.append(("pN/pS options:", ['genomic_type', 'sample_type', 'weight_by_depth', 'rand_samples', 'rand_sites', 'snp_maf', 'consensus']))
     blocks.append(("Sample filters:", ['sample_depth', 'fract_cov', 'max_samples', 'keep_samples', 'exclude_samples']))
     blocks.append(("Site filters:", ['site_list', 'site_depth', 'site_prev', 'site_maf', 'site_ratio', 'allele_support', 'locus_type', 'site_type',
                                      'max_sites']))
     for title, names in blocks:
         rows.append(title)
         for name in names:
+            if script == 'snp_pnps.py' and name in ('locus_type', 'site_type'):
+                continue
             rows.append("  %s: %s" % (name, args['locus_type' if name == 'site_type' else name]))
     sys.stdout.write('\n'.join(rows) + '\n')
 
@@ -162,6 +196,17 @@ def check_diversity_args(args, resampling=False):
         _exit("--locus_type must be CDS if --genomic_type is per-gene")
     if args['locus_type'] != 'CDS' and args['site_type'] is not None:
         _exit("--locus_type must be CDS if --site_type is specified")
+
+
+def check_pnps_args(args):
+    """check_diversity_args' checks that still apply: the classes are CDS sites, and nothing is resampled."""
+    if not os.path.isdir(args['indir']):
+        _exit("Specified input directory '%s' does not exist" % args['indir'])
+    if args['site_depth'] < 2:
+        _exit("--site_depth must be >=2 to calculate nucleotide variation")
+    _common_checks(args)
+    if args['rand_sites'] and (args['rand_sites'] < 0 or args['rand_sites'] > 1):
+        _exit("--rand_sites must be between 0 and 1")
 
 
 def check_consensus_args(args):

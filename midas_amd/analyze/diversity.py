@@ -16,11 +16,12 @@ from midas_amd import abi
 from midas_amd.analyze import sites as S
 
 
-def site_mask(tables, args):
-    """-> (mask [n] bool, rows the reference reads).  --site_list: a listed id that is absent or out of order blocks every id
-    after it, and the loop ends at the first row after the list is used up.  --rand_sites: one draw per site past the list."""
+def restrict_mask(tables, args, mask):
+    """mask [n] bool (what the info table decides) with --site_list and --rand_sites applied -> (mask, rows the reference reads).
+    --site_list: a listed id that is absent or out of order blocks every id after it, and the loop ends at the first row after
+    the list is used up.  --rand_sites: one draw per site past the list, whatever the mask holds there (snp_pnps.py and the two
+    snp_diversity.py runs it stands for drop the same sites under one seed)."""
     n = tables.n_sites
-    mask = S.info_mask(tables, args['locus_type'], args['site_type'])
     if args['site_list']:
         listed = S.read_site_list(args['site_list'])
         ids = tables.strings('site_id')
@@ -39,6 +40,11 @@ def site_mask(tables, args):
         drop = [i for i in candidates if random.uniform(0, 1) > args['rand_sites']]
         mask[np.array(drop, np.int64)] = False
     return mask, n
+
+
+def site_mask(tables, args):
+    """-> (mask [n] bool, rows the reference reads): --locus_type / --site_type, then restrict_mask."""
+    return restrict_mask(tables, args, S.info_mask(tables, args['locus_type'], args['site_type']))
 
 
 def compute(args, tables, samples, ctx):
@@ -60,34 +66,51 @@ def compute(args, tables, samples, ctx):
     return res
 
 
-def write_pi(args, tables, samples, res):
-    """write_pi: one row per chain, every number as str() prints it.  pi is the int 0 until a float is added to it: it prints
-    '0' for a chain without a site, and for every per-sample chain under --consensus, whose terms are all the int 0."""
-    pooled, per_gene = args['sample_type'] == 'pooled-samples', args['genomic_type'] == 'per-gene'
-    sites, snps = res['sites'].ravel(), res['snps'].ravel()
+def chain_cells(args, pi, snps, sites, depth=None):
+    """The cells of write_pi's columns for every chain of one block of sums (arrays of one shape, read flat), every number as
+    str() prints it -> dict of str arrays: sites, snps, pi, snps_kb, pi_bp and (per-sample) depth; and pi_bp_value, the doubles
+    whose repr pi_bp holds (nan where it is NA).  pi is the int 0 until a float is added to it: it prints '0' for a chain
+    without a site, and for every per-sample chain under --consensus, whose terms are all the int 0."""
+    pooled = args['sample_type'] == 'pooled-samples'
+    pi, sites, snps = pi.ravel(), sites.ravel(), snps.ravel()
     some = sites > 0
     div = np.where(some, sites, 1).astype(np.float64)
     fmt = lambda v: np.array(abi.format_repr_f64(v), object)
     saw_float = some & (pooled or not args['consensus'])
-    pi = np.where(saw_float, fmt(res['pi'].ravel()), '0')
-    snps_kb = np.where(some, fmt((1000 * snps).astype(np.float64) / div), 'NA')
-    pi_bp = np.where(some, fmt(np.where(saw_float, res['pi'].ravel(), 0.0) / div), 'NA')
+    pi_bp_value = np.where(saw_float, pi, 0.0) / div
+    cells = dict(sites=np.array([str(x) for x in sites], object), snps=np.array([str(x) for x in snps], object),
+                 pi=np.where(saw_float, fmt(pi), '0'), snps_kb=np.where(some, fmt((1000 * snps).astype(np.float64) / div), 'NA'),
+                 pi_bp=np.where(some, fmt(pi_bp_value), 'NA'), pi_bp_value=np.where(some, pi_bp_value, np.nan))
+    if not pooled:
+        cells['depth'] = np.array([str(x) for x in depth.ravel()], object)
+    return cells
+
+
+BLOCK_COLUMNS = ['sites', 'snps', 'pi', 'snps_kb', 'pi_bp']
+
+
+def write_chains(args, tables, samples, blocks, extra=None):
+    """One row per chain: the sample id (per-sample), the gene id (per-gene), the pool's sample count (pooled), then per block
+    (suffix, chain_cells) its columns -- depth first for per-sample chains -- and then the extra (name, cells) column."""
+    pooled, per_gene = args['sample_type'] == 'pooled-samples', args['genomic_type'] == 'per-gene'
     genes = tables.strings('gene_id') if per_gene else [None]
     G = len(genes)
-    lines = []
-    if pooled:
-        lines.append((['gene_id'] if per_gene else []) + ['samples', 'sites', 'snps', 'pi', 'snps_kb', 'pi_bp'])
+    names = ([] if pooled else ['depth']) + BLOCK_COLUMNS
+    header = (['gene_id'] if per_gene else []) + (['samples'] if pooled else []) + [n + suffix for suffix, _ in blocks for n in names] + \
+        ([extra[0]] if extra else [])
+    lines = [header if pooled else ['sample_id'] + header]
+    for k, s in enumerate([None] if pooled else samples.values()):
         for g in range(G):
-            lines.append(([genes[g]] if per_gene else []) + [str(len(samples)), str(sites[g]), str(snps[g]), pi[g], snps_kb[g], pi_bp[g]])
-    else:
-        depth = res['depth'].ravel()
-        lines.append(['sample_id'] + (['gene_id'] if per_gene else []) + ['depth', 'sites', 'snps', 'pi', 'snps_kb', 'pi_bp'])
-        for k, s in enumerate(samples.values()):
-            for g in range(G):
-                c = k * G + g
-                lines.append([s.id] + ([genes[g]] if per_gene else []) + [str(depth[c]), str(sites[c]), str(snps[c]), pi[c], snps_kb[c], pi_bp[c]])
+            c = k * G + g
+            lines.append(([] if pooled else [s.id]) + ([genes[g]] if per_gene else []) + ([str(len(samples))] if pooled else []) +
+                         [cells[n][c] for _, cells in blocks for n in names] + ([extra[1][c]] if extra else []))
     with open(args['out'], 'w') as out:
         out.write(''.join('\t'.join(r) + '\n' for r in lines))
+
+
+def write_pi(args, tables, samples, res):
+    """write_pi: one row per chain, every number as str() prints it."""
+    write_chains(args, tables, samples, [('', chain_cells(args, res['pi'], res['snps'], res['sites'], res.get('depth')))])
 
 
 def run_pipeline(args, make_context=S.device_context):

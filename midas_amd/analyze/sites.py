@@ -75,16 +75,20 @@ def read_site_list(path):
         return [line.rstrip() for line in f]
 
 
-def scan(ctx, tables, samples, mask, n_sites, args, flags, **kw):
+def scan(ctx, tables, samples, mask, n_sites, args, flags, classes=None, **kw):
     """Context.sites_scan over the first n_sites rows for the selected samples; a malformed row ends the command with the
-    file and the line (the reference dies in float() / int() there)."""
+    file and the line (the reference dies in float() / int() there).  classes = (site_class [n], n_classes):
+    Context.sites_scan_classes, the sums once per class."""
     order = list(samples.values())
+    call, lead = ctx.sites_scan, ()
+    if classes is not None:
+        call, lead = ctx.sites_scan_classes, (np.ascontiguousarray(classes[0][:n_sites], np.uint8), int(classes[1]))
     try:
-        return ctx.sites_scan(tables.freq_text, tables.depth_text, np.ascontiguousarray(mask[:n_sites], np.uint8),
-                              [s.index for s in order], [s.mean_depth for s in order], int(args['site_depth']), float(args['site_ratio']),
-                              float(args['allele_support']), float(args['site_prev']), float(args['site_maf']),
-                              max_sites=-1 if args['max_sites'] == float('inf') else int(args['max_sites']), flags=flags,
-                              group_rows=int(args.get('group_rows', 0) or 0), chunk_bytes=int(args.get('chunk_bytes', 0) or 0), **kw)
+        return call(tables.freq_text, tables.depth_text, np.ascontiguousarray(mask[:n_sites], np.uint8), *lead,
+                    [s.index for s in order], [s.mean_depth for s in order], int(args['site_depth']), float(args['site_ratio']),
+                    float(args['allele_support']), float(args['site_prev']), float(args['site_maf']),
+                    max_sites=-1 if args['max_sites'] == float('inf') else int(args['max_sites']), flags=flags,
+                    group_rows=int(args.get('group_rows', 0) or 0), chunk_bytes=int(args.get('chunk_bytes', 0) or 0), **kw)
     except abi.MidasSnpsError as e:
         exit_bad_row(tables, order, e)
 

@@ -8,6 +8,8 @@
 //   sums     one wave a chain (a sample, or the pool): 64 rows loaded coalesced, then folded in lane order -- the fp64 sum
 //            is the sequential one, bit for bit; per-gene chains switch accumulators where the gene index changes.
 //            Accumulators live in device memory and carry from group to group
+//   classes  midas_sites_scan_classes: the sums once per site class in one pass, one wave a (chain, class); only pi is folded
+//            in lane order, the integer sums come from ballots and per-lane partial sums (ss_sums_classes_kernel)
 //   seq      call_consensus.py: one byte per (retained site, sample), sample-major
 // strain_tracking.py walks the same rows in sites_strains.hip, snp_trees.py the same rows and site decisions in sites_trees.hip.
 // This file is compiled with -ffp-contract=off (build.py): 2*f*(1-f) and d*f round as the interpreter rounds them.
@@ -92,6 +94,114 @@ __global__ __launch_bounds__(64) void ss_sums_kernel(SumP p) {
   if (cur >= 0 && lane == 0) { p.pi[base + cur] = pi; p.snps[base + cur] = snps; p.sites[base + cur] = sites; p.depth[base + cur] = depth; }
 }
 
+// ---- the sums per site class (midas_sites_scan_classes) ------------------------------------------------------------------------
+struct ClassSumP {
+  SumP s;                      // pi / snps / sites / depth are [classes][chains][n_genes]
+  const uint8_t* site_class;   // [g], or nullptr: every row is class 0
+};
+
+// what one lane reads of one row, before anything is decided from it
+struct ClassRow {
+  double f;
+  long long d;
+  int gi;
+  uint8_t keep, cls, cell;
+};
+
+// r < p.g.  Every load is unconditional, so that a step's loads can all be in flight while the step before it is folded
+__device__ __forceinline__ ClassRow class_row_load(const ClassSumP& q, int chain, long long r) {
+  const SumP& p = q.s;
+  ClassRow w;
+  const long long at = (long long)chain * p.stride + r;
+  w.keep = p.final_keep[r];
+  w.cls = q.site_class ? q.site_class[r] : (uint8_t)0;
+  w.cell = p.pooled ? (uint8_t)1 : p.cell[at];
+  w.f = p.pooled ? p.fv[r] : p.fv[at];
+  w.d = p.pooled ? 0 : p.dv[at];
+  w.gi = p.per_gene ? p.gene[r] : 0;
+  return w;
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One wave per (chain, class): blockIdx.x the chain, blockIdx.y the class.  The chains of the classes share no accumulator, so
+// they fold side by side.  Of a step's 64 rows the wave's live lanes are its class's alone, cut into runs of one gene (a run ends
+// where the gene index changes; genome-wide a step is one run).  Per run:
+//   pi      folded serially in lane order, two readlanes and one add a lane -- the sequential fp64 sum, bit for bit
+//   sites, snps   popcounts of ballots
+//   depth   a per-lane partial sum, reduced over the wave when the accumulators are written: where the gene changes and at the end
+// Integer addition has no order, so these three need not ride the chain.  The next step's rows are loaded before the current
+// step is folded.  Kept sites without a gene id are counted by chain 0 of class 0, whatever their class.
+__global__ __launch_bounds__(64) void ss_sums_classes_kernel(ClassSumP q) {
+  const SumP& p = q.s;
+  if (p.g <= 0) return;
+  const int chain = blockIdx.x, cls = blockIdx.y, lane = threadIdx.x;
+  const long long base = ((long long)cls * gridDim.x + chain) * p.n_genes;
+  const bool count_lost = p.per_gene && chain == 0 && cls == 0;
+  long long cur = p.per_gene ? -1 : 0;
+  double pi = 0.0;
+  long long snps = 0, sites = 0, depth = 0, dpart = 0;
+  unsigned long long lost = 0;
+  if (!p.per_gene) { pi = p.pi[base]; snps = p.snps[base]; sites = p.sites[base]; depth = p.depth[base]; }
+  const long long last = p.g - 1;
+  ClassRow nx = class_row_load(q, chain, lane < last ? lane : last);
+  for (long long r0 = 0; r0 < p.g; r0 += 64) {
+    const ClassRow w = nx;
+    if (r0 + 64 < p.g) {
+      const long long rn = r0 + 64 + lane;
+      nx = class_row_load(q, chain, rn < last ? rn : last);
+    }
+    const bool in = r0 + lane < p.g, kept = in && w.keep != 0;
+    if (count_lost) lost += (unsigned long long)__popcll((long long)__ballot(kept && w.gi < 0));
+    const bool on = kept && w.cls == cls && (w.cell & 1) != 0 && w.gi >= 0;
+    double f = w.f;
+    if (!p.pooled && p.round_freq) f = rint(f) + 0.0;
+    const double term = (2.0 * f) * (1.0 - f);
+    double m = f;                               // min(f, 1 - f) as Python's min
+    if (1.0 - f < m) m = 1.0 - f;
+    const long long d = on ? w.d : 0;
+    unsigned long long live = __ballot(on);
+    const unsigned long long snp_b = __ballot(on && m >= p.snp_maf);
+    const int tlo = __double2loint(term), thi = __double2hiint(term);
+    while (live) {
+      // the run: the live lanes in front of the first live lane with another gene
+      const int k0 = __ffsll((long long)live) - 1;
+      const long long gk = __builtin_amdgcn_readlane(w.gi, k0);
+      const unsigned long long other = live & ~__ballot(on && w.gi == (int)gk);
+      unsigned long long run = other ? live & ((1ull << (__ffsll((long long)other) - 1)) - 1ull) : live;
+      live &= ~run;
+      if (gk != cur) {
+        if (cur >= 0) {
+          depth += wave_sum_i64(dpart);
+          dpart = 0;
+          if (lane == 0) { p.pi[base + cur] = pi; p.snps[base + cur] = snps; p.sites[base + cur] = sites; p.depth[base + cur] = depth; }
+        }
+        cur = gk;
+        pi = p.pi[base + cur]; snps = p.snps[base + cur]; sites = p.sites[base + cur]; depth = p.depth[base + cur];
+        // vmcnt(0) here, where the gene changes: loads return in order, so a wait for these four in the fold below would be a wait
+        // for the next step's rows in every step, with or without a change
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+      }
+      sites += __popcll((long long)run);
+      snps += __popcll((long long)(run & snp_b));
+      if ((run >> lane) & 1ull) dpart += d;
+      while (run) {
+        const int k = __ffsll((long long)run) - 1;
+        run &= run - 1;
+        pi += __hiloint2double(__builtin_amdgcn_readlane(thi, k), __builtin_amdgcn_readlane(tlo, k));
+      }
+    }
+  }
+  if (cur >= 0) {
+    depth += wave_sum_i64(dpart);
+    if (lane == 0) { p.pi[base + cur] = pi; p.snps[base + cur] = snps; p.sites[base + cur] = sites; p.depth[base + cur] = depth; }
+  }
+  if (count_lost && lane == 0 && lost) atomicAdd(p.no_gene, lost);
+}
+
 // fetch_consensus for the retained sites of the group: seq[s][rank] (rank among the group's retained sites)
 __global__ __launch_bounds__(256) void ss_seq_kernel(const double* fv, const long long* dv, const uint8_t* cell, const uint8_t* final_keep,
                                                      const uint32_t* rank, const char* minor, const char* major, long long g, long long stride,
@@ -119,13 +229,15 @@ struct ResampleArgs {
   double* out_draw8;
 };
 
-// the two entry points' common body
+// the entry points' common body.  site_class / n_classes: the class of every row and their number (nullptr, 1: one class);
+// classed: the sums are midas_sites_scan_classes' -- [n_classes][chains][n_genes], by ss_sums_classes_kernel
 int32_t sites_scan_body(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
                         int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
                         const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
                         const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
                         int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
-                        uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8, const ResampleArgs* ra) {
+                        uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8, const ResampleArgs* ra,
+                        const uint8_t* site_class, int32_t n_classes, bool classed) {
   if (!mean_depth || !fparams5 || !iparams8 || (n_sites_max > 0 && !site_mask)) return MIDAS_SNPS_ERR_INVALID_ARG;
   const long long site_depth = iparams8[0], max_sites = iparams8[1], flags = iparams8[2], seq_cap = iparams8[6];
   const long long n_genes_in = iparams8[3];
@@ -140,6 +252,10 @@ int32_t sites_scan_body(midas_snps_ctx* ctx, const char* freq, int64_t freq_byte
   if (per_gene)
     for (int64_t i = 0; i < n_sites_max; ++i)
       if (site_gene[i] >= n_genes_in) return MIDAS_SNPS_ERR_INVALID_ARG;
+  if (n_classes < 1 || n_classes > MIDAS_SITES_MAX_CLASSES || (n_classes > 1 && !site_class) || (classed && want_seq)) return MIDAS_SNPS_ERR_INVALID_ARG;
+  if (site_class)
+    for (int64_t i = 0; i < n_sites_max; ++i)
+      if (site_mask[i] && site_class[i] >= n_classes) return MIDAS_SNPS_ERR_INVALID_ARG;
   std::vector<int32_t> col_slot;
   {
     const int32_t rc = sites_begin(ctx, freq, freq_bytes, depth, depth_bytes, n_sites_max, S, sample_col, out_stats16, out_ms8, &col_slot);
@@ -147,13 +263,13 @@ int32_t sites_scan_body(midas_snps_ctx* ctx, const char* freq, int64_t freq_byte
   }
   const long long n_genes = per_gene ? n_genes_in : 1;
   const long long chains = pooled ? 1 : S;
-  const size_t n_acc = (size_t)(chains * n_genes);
+  const size_t n_acc = (size_t)(chains * n_genes) * (size_t)n_classes;
   if (want_sums)
     for (size_t k = 0; k < n_acc; ++k) { out_pi[k] = 0.0; out_snps[k] = 0; out_sites[k] = 0; out_depth[k] = 0; }
   if (n_sites_max == 0) return MIDAS_SNPS_OK;
   SS_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  const long long per_row = (long long)S * (8 + 8 + 1 + 2 * (long long)sizeof(SideCell) + (want_seq ? 1 : 0)) + 4 + 4 + 4 + 8 + 1 + 8 + 8 +
+  const long long per_row = (long long)S * (8 + 8 + 1 + 2 * (long long)sizeof(SideCell) + (want_seq ? 1 : 0)) + 4 + 4 + 4 + 8 + 1 + 8 + 8 + (site_class ? 1 : 0) +
                             (ra ? ResampleStep::per_row(S) : 0);
   SsBufs dev;
   SsEvents ev;
@@ -181,11 +297,13 @@ int32_t sites_scan_body(midas_snps_ctx* ctx, const char* freq, int64_t freq_byte
   long long *d_dv = rg.d_dv, *d_snps = nullptr, *d_sites = nullptr, *d_depth = nullptr;
   uint8_t* d_seq = nullptr;
   int32_t* d_gene = nullptr;
+  uint8_t* d_class = nullptr;
   char *d_minor = nullptr, *d_major = nullptr;
   unsigned long long* d_no_gene = nullptr;
   SS_TRY(dev.get(&d_no_gene, 8));
   SS_TRY(hipMemsetAsync(d_no_gene, 0, 8, st));
   if (per_gene) SS_TRY(dev.get(&d_gene, (size_t)G * 4));
+  if (site_class) SS_TRY(dev.get(&d_class, (size_t)G));
   if (want_seq) {
     SS_TRY(dev.get(&d_seq, rg.cells));
     SS_TRY(dev.get(&d_minor, (size_t)G));
@@ -212,6 +330,7 @@ int32_t sites_scan_body(midas_snps_ctx* ctx, const char* freq, int64_t freq_byte
     const long long base = rg.base;
     // ---- site kernel, order, sums, sequences ---------------------------------------------------------------------------
     if (per_gene) SS_TRY(hipMemcpyAsync(d_gene, site_gene + base, (size_t)g * 4, hipMemcpyHostToDevice, st));
+    if (site_class) SS_TRY(hipMemcpyAsync(d_class, site_class + base, (size_t)g, hipMemcpyHostToDevice, st));
     if (want_seq) {
       SS_TRY(hipMemcpyAsync(d_minor, minor + base, (size_t)g, hipMemcpyHostToDevice, st));
       SS_TRY(hipMemcpyAsync(d_major, major + base, (size_t)g, hipMemcpyHostToDevice, st));
@@ -229,7 +348,13 @@ int32_t sites_scan_body(midas_snps_ctx* ctx, const char* freq, int64_t freq_byte
       q.fv = pooled ? site.d_pooled : d_fv; q.dv = d_dv; q.cell = site.d_cell; q.final_keep = site.d_final; q.gene = d_gene; q.g = g;
       q.stride = G; q.pooled = pooled; q.per_gene = per_gene; q.round_freq = round_freq; q.n_genes = n_genes; q.snp_maf = fparams5[4];
       q.pi = d_pi; q.snps = d_snps; q.sites = d_sites; q.depth = d_depth; q.no_gene = d_no_gene;
-      hipLaunchKernelGGL(ss_sums_kernel, dim3((unsigned)chains), dim3(64), 0, st, q);
+      if (classed) {
+        ClassSumP cq;
+        cq.s = q; cq.site_class = d_class;
+        hipLaunchKernelGGL(ss_sums_classes_kernel, dim3((unsigned)chains, (unsigned)n_classes), dim3(64), 0, st, cq);
+      } else {
+        hipLaunchKernelGGL(ss_sums_kernel, dim3((unsigned)chains), dim3(64), 0, st, q);
+      }
       SS_TRY(hipGetLastError());
     }
     SS_TRY(hipEventRecord(ev.e[6], st));
@@ -309,7 +434,7 @@ extern "C" int32_t midas_sites_scan(midas_snps_ctx* ctx, const char* freq, int64
                                     uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8) {
   return sites_scan_body(ctx, freq, freq_bytes, depth, depth_bytes, n_sites_max, site_mask, site_gene, minor, major, n_samples, sample_col,
                          mean_depth, fparams5, iparams8, out_pi, out_snps, out_sites, out_depth, out_seq, dump_freq, dump_depth, dump_keep,
-                         dump_pooled, out_stats16, out_ms8, nullptr);
+                         dump_pooled, out_stats16, out_ms8, nullptr, nullptr, 1, false);
 }
 
 extern "C" int32_t midas_sites_scan_resampled(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
@@ -330,5 +455,17 @@ extern "C" int32_t midas_sites_scan_resampled(midas_snps_ctx* ctx, const char* f
   const ResampleArgs ra{rand_reads, replace, mt_key, mt_pos, mt_key_out, mt_pos_out, out_draw8};
   return sites_scan_body(ctx, freq, freq_bytes, depth, depth_bytes, n_sites_max, site_mask, site_gene, minor, major, n_samples, sample_col,
                          mean_depth, fparams5, iparams8, out_pi, out_snps, out_sites, out_depth, out_seq, dump_freq, dump_depth, dump_keep,
-                         dump_pooled, out_stats16, out_ms8, &ra);
+                         dump_pooled, out_stats16, out_ms8, &ra, nullptr, 1, false);
+}
+
+extern "C" int32_t midas_sites_scan_classes(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                            int64_t n_sites_max, const uint8_t* site_mask, const int32_t* site_gene, const char* minor,
+                                            const char* major, int32_t n_samples, const int32_t* sample_col, const double* mean_depth,
+                                            const double* fparams5, const int64_t* iparams8, double* out_pi, int64_t* out_snps,
+                                            int64_t* out_sites, int64_t* out_depth, uint8_t* out_seq, double* dump_freq, int64_t* dump_depth,
+                                            uint8_t* dump_keep, double* dump_pooled, int64_t* out_stats16, float* out_ms8,
+                                            const uint8_t* site_class, int32_t n_classes) {
+  return sites_scan_body(ctx, freq, freq_bytes, depth, depth_bytes, n_sites_max, site_mask, site_gene, minor, major, n_samples, sample_col,
+                         mean_depth, fparams5, iparams8, out_pi, out_snps, out_sites, out_depth, out_seq, dump_freq, dump_depth, dump_keep,
+                         dump_pooled, out_stats16, out_ms8, nullptr, site_class, n_classes, true);
 }
