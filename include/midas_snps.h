@@ -1134,6 +1134,34 @@ int32_t midas_sites_consensus_pairs(midas_snps_ctx* ctx, const char* freq, int64
 int32_t midas_nj_tree(midas_snps_ctx* ctx, int32_t n, const double* dist, int32_t* out_join, double* out_len, int32_t* out_last,
                       double* out_last_len, int64_t* out_stats16, float* out_ms8);
 
+/* ---- snp_pairs.py: pooled diversity, dxy and Fst of every pair of samples in one pass -------------------------------------------
+ * Replaces scripts/snp_diversity.py:243-311 and midas/analyze/parse_snps.py:92-151, run once per pair with `--sample_type
+ * pooled-samples --keep_samples a,b`.  midas_sites_pair_diversity walks the two matrices as midas_sites_scan does (same text,
+ * masks, cell parsers, row groups, place of a bad row in out_stats16[4..6]); n_samples >= 2; fparams5 as there; iparams8 =
+ * site_depth, max_sites (-1: all), flags (MIDAS_SITES_WEIGHT and MIDAS_SITES_ROUND are looked at; with MIDAS_SITES_WEIGHT
+ * site_depth must be at least 1, so that no pool divides by 0), 0, group_rows, chunk_bytes, pair_form (0 or 1: one pair a
+ * lane, tiles of 16 x 16 pairs; 2: a 4 x 4 patch a lane, tiles of 64 x 64; more is MIDAS_SNPS_ERR_INVALID_ARG), 0.  Every
+ * (site, sample) cell is kept or not as flag_samples decides (site_depth, site_ratio, allele_support).  Then per pair i < j, over
+ * the rows with site_mask set, in file order, a = f_i and b = f_j (rounded half to even under MIDAS_SITES_ROUND):
+ *   count = kept cells of the two; pooled = 0.0 (count 0), else sum / count with sum = ((0.0 + a) + b) over the kept ones, or
+ *   under MIDAS_SITES_WEIGHT ((0.0 + d_i a) + d_j b) / (d_i + d_j) over the kept ones; the site is retained unless site_prev != 0
+ *   and count / 2 < max(1e-6, site_prev), or site_maf != 0 and pooled < site_maf, or the pair has retained max_sites sites;
+ *   retained: sites += 1, pi += (2 pooled)(1 - pooled), snps += 1 where min(pooled, 1 - pooled) >= snp_maf (Python's min);
+ *   retained and count 2: shared += 1, w1 += (2 a)(1 - a), w2 += (2 b)(1 - b), x += (a (1 - b)) + (b (1 - a)).
+ * Every sum starts from +0.0 and takes one rounded fp64 operation per term, in site order: the results depend on neither
+ * group_rows, chunk_bytes nor pair_form.  The seven outputs are [n_samples][n_samples], filled for i < j, 0 elsewhere.  Under
+ * MIDAS_SITES_ROUND a frequency of a selected sample that is not finite, in any row, is MIDAS_SNPS_ERR_BAD_LAYOUT with
+ * out_stats16[4] = 3; a malformed cell in any row is reported as midas_sites_scan reports it, whatever max_sites is.
+ * out_stats16: [0] sites read, [1] rows with site_mask set, [2] / [3] cells converted by the host, [7] row groups, [8] pairs x
+ * rows, [9] group_rows, [10] chunk_bytes, [11] pairs a lane a side (1 or 4), [12] tiles, [13] the most samples whose seven
+ * matrices fit a quarter of the free device memory (more is MIDAS_SNPS_ERR_OUT_OF_MEMORY).  out_ms8 (nullable): upload + index
+ * (host clock), index, parse, site, order, pairs, -, download (device events).                                                  */
+int32_t midas_sites_pair_diversity(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                                   int64_t n_sites_max, const uint8_t* site_mask, int32_t n_samples, const int32_t* sample_col,
+                                   const double* mean_depth, const double* fparams5, const int64_t* iparams8, int64_t* out_sites,
+                                   int64_t* out_snps, int64_t* out_shared, double* out_pi, double* out_w1, double* out_w2,
+                                   double* out_x, int64_t* out_stats16, float* out_ms8);
+
 /* ---- compare_genes.py: gene-content distances between all pairs of samples of one `merge_midas.py genes` directory ----------
  * midas_genes_matrix_*: one genes_<kind>.txt mapped and left as text.  counts: out4 = sample columns of the header, data rows
  *   (lines after the header; a last line without '\n' counts), bytes of those rows, bytes of the sample ids.  columns: out4 =

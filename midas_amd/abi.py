@@ -386,6 +386,7 @@ def load_library(build_if_missing: bool = True):
         'midas_sites_track_markers': (i32, [vp, vp, i64, vp, i64, i64, i64, vp, i32] + [vp] * 6),
         'midas_sites_consensus_pairs': (i32, [vp, vp, i64, vp, i64, i64, vp, i32] + [vp] * 8),
         'midas_nj_tree': (i32, [vp, i32] + [vp] * 7),
+        'midas_sites_pair_diversity': (i32, [vp, vp, i64, vp, i64, i64, vp, i32] + [vp] * 13),
         'midas_sites_write_markers': (i32, [C.c_char_p, vp, i64, vp, C.c_char_p]),
         'midas_sites_write_pairs': (i32, [C.c_char_p, vp, i32, vp, vp, C.c_char_p]),
         'midas_genes_matrix_open': (i32, [C.c_char_p, C.POINTER(vp), C.c_char_p]),
@@ -456,7 +457,7 @@ EXPORTED_SYMBOLS = [
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
                  'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_scan_resampled', 'midas_sites_scan_classes', 'midas_sites_id_markers', 'midas_sites_track_markers',
-                 'midas_sites_write_markers', 'midas_sites_write_pairs', 'midas_sites_consensus_pairs']
+                 'midas_sites_write_markers', 'midas_sites_write_pairs', 'midas_sites_consensus_pairs', 'midas_sites_pair_diversity']
 # snp_trees.py (neighbour joining over the consensus distances): bound above like the rest, listed by itself
 TREE_SYMBOLS = ['midas_nj_tree']
 
@@ -2081,6 +2082,41 @@ class Context:
         return dict(both=both, diff=diff, n_sites=int(stats[0]), n_kept=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]),
                     groups=int(stats[7]), word_pairs=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]),
                     pair_runs=int(stats[11]), pair_steps=int(stats[12]), sample_limit=int(stats[13]), ms=ms.tolist())
+
+    def sites_pair_diversity(self, freq_text, depth_text, site_mask, sample_col, mean_depth, site_depth: int, site_ratio: float,
+                             allele_support: float, site_prev: float, site_maf: float, snp_maf: float = 0.01, max_sites: int = -1,
+                             flags: int = 0, group_rows: int = 0, chunk_bytes: int = 0, pair_form: int = 0):
+        """midas_sites_pair_diversity(): for every pair i < j of the samples what sites_scan gives under SITES_SUMS | SITES_POOLED
+        with those two alone, and the sums over the sites both are kept at (sites_scan's arguments; of flags SITES_WEIGHT and
+        SITES_ROUND count; max_sites is every pair's own).  -> dict(sites / snps / shared int64 [S, S], pi / w1 / w2 / x f64
+        [S, S], filled above the diagonal; n_sites, n_masked, side_freq, side_depth, groups, pair_sites, pair_form (1 | 4 pairs a
+        lane a side), tiles, sample_limit, ms [8]).  Errors as sites_consensus_pairs: .bad for a row, .limit for too many samples.
+        pair_form 2 runs the 4 x 4 kernel (0, 1: one pair a lane, the faster one on an MI355X): the output does not depend on it."""
+        ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
+        dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
+        mask = np.ascontiguousarray(site_mask, dtype=np.uint8)
+        cols = np.ascontiguousarray(sample_col, dtype=np.int32)
+        mean = np.ascontiguousarray(mean_depth, dtype=np.float64)
+        S = int(cols.shape[0])
+        assert mean.shape[0] == S
+        fp = np.array([site_ratio, allele_support, site_prev, site_maf, snp_maf], np.float64)
+        ip = np.array([site_depth, max_sites, flags & (SITES_WEIGHT | SITES_ROUND), 0, group_rows, chunk_bytes, pair_form, 0], np.int64)
+        out = {k: np.zeros((S, S), np.int64) for k in ('sites', 'snps', 'shared')}
+        out.update({k: np.zeros((S, S), np.float64) for k in ('pi', 'w1', 'w2', 'x')})
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_sites_pair_diversity(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], int(mask.shape[0]), p(mask), S, p(cols),
+                                                  p(mean), p(fp), p(ip), *[p(out[k]) for k in ('sites', 'snps', 'shared', 'pi', 'w1', 'w2', 'x')],
+                                                  p(stats), p(ms))
+        try:
+            self._check_bad(st, stats)
+        except MidasSnpsError as e:
+            e.limit = int(stats[13]) if st == ERR_OUT_OF_MEMORY and stats[13] < S else None
+            raise
+        out.update(n_sites=int(stats[0]), n_masked=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]), groups=int(stats[7]),
+                   pair_sites=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), pair_form=int(stats[11]),
+                   tiles=int(stats[12]), sample_limit=int(stats[13]), ms=ms.tolist())
+        return out
 
     def nj_tree(self, dist):
         """midas_nj_tree(): neighbour joining over a symmetric matrix of finite doubles [n, n], n >= 3, on the device; the

@@ -1,4 +1,4 @@
-"""The command lines of snp_diversity.py, snp_pnps.py, call_consensus.py, strain_tracking.py and compare_genes.py: the reference's option
+"""The command lines of snp_diversity.py, snp_pnps.py, snp_pairs.py, call_consensus.py, strain_tracking.py and compare_genes.py: the reference's option
 names, defaults, check_args messages and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146,
 scripts/strain_tracking.py:10-137, scripts/compare_genes.py:10-65), shared where they agree."""
 import argparse
@@ -119,6 +119,41 @@ def pnps_arguments(argv=None):
     return vars(parser.parse_args(argv))
 
 
+PAIRS_LEFT_OUT = ('--genomic_type', '--sample_type', '--rand_reads', '--replace_reads')
+PAIRS_OPTIONS = [
+    (['--tree'], dict(metavar='PATH', type=str, help="also write a neighbour-joining tree over da (dxy minus the mean within-sample pi_bp)\nhere, in Newick format; needs at least 3 samples")),
+]
+PAIRS_DEVICE_OPTIONS = DEVICE_OPTIONS + [(['--chunk_bytes'], dict(type=int, default=0, help=argparse.SUPPRESS)),
+                                         (['--pair_form'], dict(type=int, default=0, choices=[0, 1, 2], help=argparse.SUPPRESS))]
+
+
+def pairs_arguments(argv=None):
+    """snp_pairs.py: snp_diversity.py's sample, site and diversity options under their names and defaults, without --genomic_type /
+    --sample_type (always genome-wide over pooled pairs) and without --rand_reads / --replace_reads; --tree; the hidden
+    --chunk_bytes and --pair_form."""
+    helps = {'--max_sites': "every pair stops after this many retained sites of its own (all)",
+             '--weight_by_depth': "weight each of the two samples by its depth at the site",
+             '--seed': "seed numpy's and Python's global random streams with INT first: --rand_samples and\n--rand_sites then give the same result every run"}
+    keep = lambda options: [(f, dict(kw, help=helps[f[0]]) if f[0] in helps else kw) for f, kw in options if f[0] not in PAIRS_LEFT_OUT]
+    parser = _parser('snp_pairs.py',
+                     "Between-sample heterogeneity of one species for every pair of samples, from its merged SNP tables: what\n"
+                     "`snp_diversity.py --sample_type pooled-samples --keep_samples a,b` writes for the pair (a, b), and beside it,\n"
+                     "over the sites both samples are kept at, the pi_bp within each sample, the pi_bp between them (dxy),\n"
+                     "Hudson's Fst and da.  All pairs come from one pass over the matrices.  Run `merge_midas.py snps` first.\n"
+                     "--genomic_type / --sample_type are not offered: the command is always genome-wide over pooled pairs.\n"
+                     "--rand_reads / --replace_reads are not offered: each separate run draws the random stream from its own\n"
+                     "start over its own sites, so no single pass gives what they give.",
+                     "examples:\n"
+                     "  snp_pairs.py OUT/species_1 --out pairs.txt\n"
+                     "  snp_pairs.py OUT/species_1 --out pairs.txt --tree da.nwk --site_depth 5 --site_prev 1.0 --sample_depth 10\n\n"
+                     "output: sample1, sample2, then samples (2), sites, snps, pi, snps_kb, pi_bp of the pooled pair, then shared_sites,\n"
+                     "pi_bp_1, pi_bp_2, dxy, fst = 1 - ((pi_bp_1 + pi_bp_2) / 2) / dxy and da = dxy - (pi_bp_1 + pi_bp_2) / 2\n"
+                     "(NA without a shared site; fst also where dxy is 0.0)",
+                     [("Pair options", PAIRS_OPTIONS + keep(DIVERSITY_OPTIONS + SEED_OPTIONS)), ("Sample filters", SAMPLE_OPTIONS),
+                      ("Site filters", keep(SITE_OPTIONS)), ("Device", PAIRS_DEVICE_OPTIONS)])
+    return vars(parser.parse_args(argv))
+
+
 def consensus_arguments(argv=None):
     parser = _parser('call_consensus.py',
                      "One consensus sequence per sample over the retained sites of a species, as a multi-FASTA (for trees).\n"
@@ -133,7 +168,8 @@ def consensus_arguments(argv=None):
 
 def print_args(args, script):
     """The reference's argument block, line for line (its last but one line prints locus_type under the name site_type).
-    snp_pnps.py is not the reference's: the same block with the options it has."""
+    snp_pnps.py and snp_pairs.py are not the reference's: the same block with the options they have (snp_pairs.py prints
+    site_type under its own name)."""
     rows = [("Command: %s" % ' '.join(sys.argv)), "Script: %s" % script, "Input directory: %s" % args['indir'], "Output file: %s" % args['out']]
     blocks = []
     if script == 'snp_diversity.py':
@@ -141,6 +177,8 @@ def print_args(args, script):
                                               'rand_sites', 'snp_maf', 'consensus']))
     if script == 'snp_pnps.py':
         blocks.append(("pN/pS options:", ['genomic_type', 'sample_type', 'weight_by_depth', 'rand_samples', 'rand_sites', 'snp_maf', 'consensus']))
+    if script == 'snp_pairs.py':
+        blocks.append(("Pair options:", ['tree', 'weight_by_depth', 'rand_samples', 'rand_sites', 'snp_maf', 'consensus']))
     blocks.append(("Sample filters:", ['sample_depth', 'fract_cov', 'max_samples', 'keep_samples', 'exclude_samples']))
     blocks.append(("Site filters:", ['site_list', 'site_depth', 'site_prev', 'site_maf', 'site_ratio', 'allele_support', 'locus_type', 'site_type',
                                      'max_sites']))
@@ -149,7 +187,7 @@ def print_args(args, script):
         for name in names:
             if script == 'snp_pnps.py' and name in ('locus_type', 'site_type'):
                 continue
-            rows.append("  %s: %s" % (name, args['locus_type' if name == 'site_type' else name]))
+            rows.append("  %s: %s" % (name, args['locus_type' if name == 'site_type' and script != 'snp_pairs.py' else name]))
     sys.stdout.write('\n'.join(rows) + '\n')
 
 
@@ -207,6 +245,13 @@ def check_pnps_args(args):
     _common_checks(args)
     if args['rand_sites'] and (args['rand_sites'] < 0 or args['rand_sites'] > 1):
         _exit("--rand_sites must be between 0 and 1")
+
+
+def check_pairs_args(args):
+    """check_diversity_args' checks that still apply: nothing is resampled and nothing is per gene."""
+    check_pnps_args(args)
+    if args['locus_type'] != 'CDS' and args['site_type'] is not None:
+        _exit("--locus_type must be CDS if --site_type is specified")
 
 
 def check_consensus_args(args):
