@@ -975,11 +975,17 @@ int32_t midas_genes_merge_format_f64(int64_t n, const double* v, char* out, int6
  *   fraction_covered (f64), the sites' gene index (int32, -1: no gene id), the freq rows, the depth rows (char).  They belong
  *   to the handle.  A file that cannot be read, or a row that lacks a field in use, is an error naming file and line.
  * midas_sites_parse_cell: float() (kind 0, out8 is a double) or int() (kind 1, an int64) of one cell by the host's exact
- *   parser -- the one the scan uses for the cells its device parser passes on.                                             */
+ *   parser -- the one the scan uses for the cells its device parser passes on.
+ * midas_sites_tables_positions: the ref_id and ref_pos columns of the directory's snps_info.txt, read on the first call (the
+ *   columns are found by the header's names; the rows are those of midas_sites_tables_columns).  out4 = the rows' contig index
+ *   (int32, in order of first appearance of the ref_id), their ref_pos (int64, int() of the field), the contig names back to
+ *   back (char) and their offsets (int64, n + 1); sizes2 = contigs, bytes of the names.  They belong to the handle.  A header
+ *   without one of the two columns, a row without the field or a ref_pos that is no integer is an error naming file and line. */
 typedef struct midas_sites_tables midas_sites_tables;
 int32_t midas_sites_tables_open(const char* dir, midas_sites_tables** out, char* err1024);
 int32_t midas_sites_tables_counts(const midas_sites_tables* t, int64_t* out8);
 int32_t midas_sites_tables_columns(const midas_sites_tables* t, const void** out25, int64_t* sizes10);
+int32_t midas_sites_tables_positions(midas_sites_tables* t, const void** out4, int64_t* sizes2, char* err1024);
 void midas_sites_tables_close(midas_sites_tables* t);
 int32_t midas_sites_parse_cell(int32_t kind, const char* text, int64_t n, void* out8);
 
@@ -1161,6 +1167,40 @@ int32_t midas_sites_pair_diversity(midas_snps_ctx* ctx, const char* freq, int64_
                                    const double* mean_depth, const double* fparams5, const int64_t* iparams8, int64_t* out_sites,
                                    int64_t* out_snps, int64_t* out_shared, double* out_pi, double* out_w1, double* out_w2,
                                    double* out_x, int64_t* out_stats16, float* out_ms8);
+
+/* ---- snp_ld.py: linkage disequilibrium between pairs of sites, by distance ---------------------------------
+ * midas_sites_ld walks the two matrices as midas_sites_consensus_pairs does (same text, masks, cell parsers, row groups, site
+ * decisions under MIDAS_SITES_SEQ, --max_sites rule and place of a bad row in out_stats16[4..6]); fparams5 as there; iparams8 =
+ * site_depth, max_sites (-1: all), flags (MIDAS_SITES_MASK_ONLY and MIDAS_SITES_LD_SAME_GENE are looked at), min_samples,
+ * group_rows, chunk_bytes, anchor_chunk (0: what 256 MiB of per-anchor sums hold, at most 2^20), 0.  site_key [n_sites_max]: the
+ * row's position, contig index * 2^40 + ref_pos, >= 0 and strictly ascending over the rows with site_mask set (else
+ * MIDAS_SNPS_ERR_INVALID_ARG with the row in out_stats16[5]); site_gene [n_sites_max] (nullable without
+ * MIDAS_SITES_LD_SAME_GENE): the row's gene index, -1 none.  1 <= max_dist < 2^39, bin_width >= 1, n_bins = ceil(max_dist /
+ * bin_width) <= 4096.  For a retained site k and a sample s, `called` = the cell is kept and its depth is not 0, `minor` =
+ * called and freq >= 0.5: the letters of call_consensus.py, held site-major [retained site][64 samples a word] on the device
+ * for the whole call.
+ * A pair is (a, b) of retained sites, a before b, with 1 <= key_b - key_a <= max_dist and, under MIDAS_SITES_LD_SAME_GENE, equal
+ * gene indices >= 0; its bin is (key_b - key_a - 1) / bin_width.  With C the called and M the minor words, all int64:
+ *   n = popc(C_a & C_b), na = popc(C_a & C_b & M_a), nb = popc(C_a & C_b & M_b), nab = popc(C_a & C_b & M_a & M_b)
+ * window[bin] += 1 for every pair.  The pair is informative when n >= min_samples, 0 < na < n and 0 < nb < n; then pairs[bin] += 1
+ * and, every line one rounded fp64 operation as written, without contraction:
+ *   Dn = n*nab - na*nb, ha = na*(n - na), hb = nb*(n - nb)   (int64)
+ *   num = (double)Dn * (double)Dn;  den = (double)ha * (double)hb;  r2 = num / den
+ *   n2 = (double)(n*n);  n4 = n2 * n2;  d2 = num / n4;  het = den / n4
+ * The sums have two serial levels: p_x[a][bin] (x = r2, d2, het) starts at +0.0 and takes one add per informative partner b of
+ * that bin in ascending b; sum_x[bin] starts at +0.0 and takes one add of p_x[a][bin] per retained site a in ascending a.  So
+ * the results depend on neither group_rows, chunk_bytes nor anchor_chunk.  out_window / out_pairs (int64) and out_sum_r2 /
+ * out_sum_d2 / out_sum_het (double) are [n_bins].  out_stats16: [0] sites read, [1] sites retained, [2] / [3] cells converted by
+ * the host, [7] row groups, [8] pairs visited, [9] group_rows, [10] chunk_bytes, [11] anchor chunks, [12] anchor_chunk, [13] the
+ * most retained sites whose planes, keys and genes fit a quarter of the free device memory (more rows that CAN be retained --
+ * rows with site_mask set, at most max_sites -- is MIDAS_SNPS_ERR_OUT_OF_MEMORY).  out_ms8 (nullable): upload + index (host
+ * clock), index, parse, site, planes, LD kernel, fold, download (device events).                                                */
+#define MIDAS_SITES_LD_SAME_GENE 128
+int32_t midas_sites_ld(midas_snps_ctx* ctx, const char* freq, int64_t freq_bytes, const char* depth, int64_t depth_bytes,
+                       int64_t n_sites_max, const uint8_t* site_mask, int32_t n_samples, const int32_t* sample_col,
+                       const double* mean_depth, const double* fparams5, const int64_t* iparams8, const int64_t* site_key,
+                       const int32_t* site_gene, int64_t max_dist, int64_t bin_width, int64_t* out_window, int64_t* out_pairs,
+                       double* out_sum_r2, double* out_sum_d2, double* out_sum_het, int64_t* out_stats16, float* out_ms8);
 
 /* ---- compare_genes.py: gene-content distances between all pairs of samples of one `merge_midas.py genes` directory ----------
  * midas_genes_matrix_*: one genes_<kind>.txt mapped and left as text.  counts: out4 = sample columns of the header, data rows

@@ -377,6 +377,8 @@ def load_library(build_if_missing: bool = True):
         'midas_sites_tables_counts': (i32, [vp, vp]),
         'midas_sites_tables_columns': (i32, [vp, vp, vp]),
         'midas_sites_tables_close': (None, [vp]),
+        'midas_sites_tables_positions': (i32, [vp, vp, vp, C.c_char_p]),
+        'midas_sites_ld': (i32, [vp, vp, i64, vp, i64, i64, vp, i32] + [vp] * 6 + [i64, i64] + [vp] * 7),
         'midas_sites_parse_cell': (i32, [i32, C.c_char_p, i64, vp]),
         'midas_sites_scan': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15),
         'midas_sites_scan_resampled': (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i32] + [vp] * 15 + [i64, i32, vp, i32, vp, vp, vp]),
@@ -457,7 +459,8 @@ EXPORTED_SYMBOLS = [
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
                  'midas_sites_parse_cell', 'midas_sites_scan', 'midas_sites_scan_resampled', 'midas_sites_scan_classes', 'midas_sites_id_markers', 'midas_sites_track_markers',
-                 'midas_sites_write_markers', 'midas_sites_write_pairs', 'midas_sites_consensus_pairs', 'midas_sites_pair_diversity']
+                 'midas_sites_write_markers', 'midas_sites_write_pairs', 'midas_sites_consensus_pairs', 'midas_sites_pair_diversity',
+                 'midas_sites_tables_positions', 'midas_sites_ld']
 # snp_trees.py (neighbour joining over the consensus distances): bound above like the rest, listed by itself
 TREE_SYMBOLS = ['midas_nj_tree']
 
@@ -1096,6 +1099,8 @@ def format_repr_f64(values) -> list:
 
 
 SITES_WEIGHT, SITES_ROUND, SITES_POOLED, SITES_PER_GENE, SITES_MASK_ONLY, SITES_SEQ, SITES_SUMS = 1, 2, 4, 8, 16, 32, 64
+SITES_LD_SAME_GENE = 128     # MIDAS_SITES_LD_SAME_GENE
+SITES_LD_MAX_BINS = 4096     # the most distance bins of midas_sites_ld
 SITES_MAX_CLASSES = 4        # MIDAS_SITES_MAX_CLASSES
 SITES_PAIR_TILE = 64         # MIDAS_SITES_PAIR_TILE: samples a side of the pair kernel's tile
 ALLELE_LETTERS = 'ATCG'      # the order of the allele codes and of the count columns of strain_tracking.py id_markers
@@ -1135,6 +1140,38 @@ class SitesTables:
         self.gene = col(20, self.n_sites, np.int32)
         self.freq_text = col(21, int(counts[4]), np.uint8)
         self.depth_text = col(22, int(counts[5]), np.uint8)
+        self._positions = None
+
+    def _read_positions(self):
+        """midas_sites_tables_positions, on the first use of .contig / .ref_pos / .contig_names: a directory without the two
+        columns opens as before, and only the command that wants positions hears of it (MidasSnpsError, file and line)."""
+        if self._positions is None:
+            ptrs, sizes = (C.c_void_p * 4)(), (C.c_int64 * 2)()
+            err = C.create_string_buffer(1024)
+            st = self._owner._lib.midas_sites_tables_positions(self._owner._h, ptrs, sizes, err)
+            if st != 0:
+                raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_sites_tables_positions failed")
+            col = lambda k, n, dt: np.asarray(_Column(self._owner, ptrs[k] or 0, n, dt))
+            pool, off = col(2, int(sizes[1]), np.uint8), col(3, int(sizes[0]) + 1, np.int64)
+            raw = pool.tobytes()
+            names = [raw[int(off[k]):int(off[k + 1])].decode('utf-8', errors='surrogateescape') for k in range(int(sizes[0]))]
+            self._positions = (col(0, self.n_sites, np.int32), col(1, self.n_sites, np.int64), names)
+        return self._positions
+
+    @property
+    def contig(self):
+        """Per row of snps_info.txt: the index of its ref_id among .contig_names (int32)."""
+        return self._read_positions()[0]
+
+    @property
+    def ref_pos(self):
+        """Per row of snps_info.txt: int(ref_pos) (int64)."""
+        return self._read_positions()[1]
+
+    @property
+    def contig_names(self):
+        """The ref_ids in order of first appearance."""
+        return self._read_positions()[2]
 
     def column(self, name: str):
         """(pool uint8, offsets int64) of a string column."""
@@ -2116,6 +2153,47 @@ class Context:
         out.update(n_sites=int(stats[0]), n_masked=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]), groups=int(stats[7]),
                    pair_sites=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), pair_form=int(stats[11]),
                    tiles=int(stats[12]), sample_limit=int(stats[13]), ms=ms.tolist())
+        return out
+
+    def sites_ld(self, freq_text, depth_text, site_mask, sample_col, mean_depth, site_key, site_gene, site_depth: int, site_ratio: float,
+                 allele_support: float, site_prev: float, site_maf: float, max_dist: int = 1000, bin_width: int = 10, min_samples: int = 4,
+                 max_sites: int = -1, flags: int = 0, group_rows: int = 0, chunk_bytes: int = 0, anchor_chunk: int = 0):
+        """midas_sites_ld(): linkage disequilibrium between the sites call_consensus.py retains (sites_consensus_pairs' arguments;
+        of flags SITES_MASK_ONLY and SITES_LD_SAME_GENE count), by distance bin.  site_key int64 [n]: contig index * 2^40 +
+        ref_pos, strictly ascending over the rows of the mask; site_gene int32 [n] or None.  -> dict(window / pairs int64
+        [n_bins] = pairs of sites / informative ones, sum_r2 / sum_d2 / sum_het f64 [n_bins]; n_sites, n_kept, side_freq,
+        side_depth, groups, pairs_visited, group_rows, chunk_bytes, anchor_chunks, anchor_chunk, site_limit, ms [8]).  The
+        arithmetic is the contract in include/midas_snps.h: the output depends on neither group_rows, chunk_bytes nor
+        anchor_chunk.  A malformed row raises MidasSnpsError with .bad as sites_scan; more rows in the mask than the planes fit
+        the free device memory for raises it with .limit = that number."""
+        ft = np.ascontiguousarray(freq_text, dtype=np.uint8)
+        dt = np.ascontiguousarray(depth_text, dtype=np.uint8)
+        mask = np.ascontiguousarray(site_mask, dtype=np.uint8)
+        cols = np.ascontiguousarray(sample_col, dtype=np.int32)
+        mean = np.ascontiguousarray(mean_depth, dtype=np.float64)
+        key = np.ascontiguousarray(site_key, dtype=np.int64)
+        gene = None if site_gene is None else np.ascontiguousarray(site_gene, dtype=np.int32)
+        S, n = int(cols.shape[0]), int(mask.shape[0])
+        assert mean.shape[0] == S and S >= 1 and key.shape[0] == n and (gene is None or gene.shape[0] == n)
+        n_bins = -(-int(max_dist) // int(bin_width)) if max_dist >= 1 and bin_width >= 1 else 1
+        fp = np.array([site_ratio, allele_support, site_prev, site_maf, 0.0], np.float64)
+        ip = np.array([site_depth, max_sites, flags & (SITES_MASK_ONLY | SITES_LD_SAME_GENE), min_samples, group_rows, chunk_bytes, anchor_chunk, 0],
+                      np.int64)
+        out = {k: np.zeros(n_bins, np.int64) for k in ('window', 'pairs')}
+        out.update({k: np.zeros(n_bins, np.float64) for k in ('sum_r2', 'sum_d2', 'sum_het')})
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_sites_ld(self._h, p(ft), ft.shape[0], p(dt), dt.shape[0], n, p(mask), S, p(cols), p(mean), p(fp), p(ip), p(key),
+                                      p(gene), int(max_dist), int(bin_width), *[p(out[k]) for k in ('window', 'pairs', 'sum_r2', 'sum_d2', 'sum_het')],
+                                      p(stats), p(ms))
+        try:
+            self._check_bad(st, stats)
+        except MidasSnpsError as e:
+            e.limit = int(stats[13]) if st == ERR_OUT_OF_MEMORY and stats[13] > 0 else None
+            raise
+        out.update(n_sites=int(stats[0]), n_kept=int(stats[1]), side_freq=int(stats[2]), side_depth=int(stats[3]), groups=int(stats[7]),
+                   pairs_visited=int(stats[8]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), anchor_chunks=int(stats[11]),
+                   anchor_chunk=int(stats[12]), site_limit=int(stats[13]), ms=ms.tolist())
         return out
 
     def nj_tree(self, dist):

@@ -1,4 +1,4 @@
-"""The command lines of snp_diversity.py, snp_pnps.py, snp_pairs.py, call_consensus.py, strain_tracking.py and compare_genes.py: the reference's option
+"""The command lines of snp_diversity.py, snp_pnps.py, snp_pairs.py, snp_trees.py, snp_ld.py, call_consensus.py, strain_tracking.py and compare_genes.py: the reference's option
 names, defaults, check_args messages and printed argument block (scripts/snp_diversity.py:12-180, scripts/call_consensus.py:13-146,
 scripts/strain_tracking.py:10-137, scripts/compare_genes.py:10-65), shared where they agree."""
 import argparse
@@ -306,6 +306,65 @@ def print_trees_args(args):
     rows = ["Command: %s" % ' '.join(sys.argv), "Script: snp_trees.py", "Input directory: %s" % args['indir'], "Output file: %s" % args['out'],
             "Distance table: %s" % args['dist']]
     for title, names in (("Sample filters:", ['sample_depth', 'fract_cov', 'max_samples', 'keep_samples', 'exclude_samples']),
+                         ("Site filters:", ['site_list', 'site_depth', 'site_prev', 'site_maf', 'site_ratio', 'allele_support', 'locus_type',
+                                            'site_type', 'max_sites'])):
+        rows.append(title)
+        rows.extend("  %s: %s" % (name, args[name]) for name in names)
+    sys.stdout.write('\n'.join(rows) + '\n')
+
+
+LD_MAX_BINS = 4096          # abi.SITES_LD_MAX_BINS
+LD_MAX_DIST = 2 ** 39       # the site keys keep 2^40 positions a contig
+LD_OPTIONS = [
+    (['--max_dist'], dict(type=int, default=1000, metavar='INT', help="the largest distance in bases between the two sites of a pair (1000)")),
+    (['--bin_width'], dict(type=int, default=10, metavar='INT',
+                           help="bases a distance bin: bin k holds the distances k x B + 1 ... (k + 1) x B (10); at most %d bins" % LD_MAX_BINS)),
+    (['--min_samples'], dict(type=int, default=4, metavar='INT', help="a pair of sites counts only with this many samples called at both (4)")),
+    (['--within'], dict(choices=['contig', 'gene'], default='contig',
+                        help="pair two sites of one contig, or only two sites of one gene (contig)")),
+]
+LD_DEVICE_OPTIONS = HIDDEN_DEVICE_OPTIONS + [(['--chunk_bytes'], dict(type=int, default=0, help=argparse.SUPPRESS)),
+                                             (['--anchor_chunk'], dict(type=int, default=0, help=argparse.SUPPRESS))]
+
+
+def ld_arguments(argv=None):
+    """snp_ld.py: the sample and site options of snp_trees.py under their names and defaults, the four options of its own, the
+    hidden --group_rows, --chunk_bytes and --anchor_chunk."""
+    parser = _parser('snp_ld.py',
+                     "Linkage disequilibrium between the sites of one species, by distance: the consensus allele of every sample\n"
+                     "at the retained sites (as call_consensus.py calls it), and for every pair of sites at most --max_dist bases\n"
+                     "apart r2 and the terms of sigma2_d over the samples called at both, averaged per distance bin.  LD that\n"
+                     "decays with distance tells a recombining population from a clonal one.  Run `merge_midas.py snps` first.",
+                     "examples:\n"
+                     "  snp_ld.py OUT/species_1 --out ld.txt --site_depth 5 --site_prev 0.90 --sample_depth 10\n"
+                     "  snp_ld.py OUT/species_1 --out ld.txt --max_dist 3000 --bin_width 50 --within gene --locus_type CDS\n\n"
+                     "output: bin_start, bin_end (distances in bases), site_pairs (pairs of retained sites in the bin), ld_pairs (those\n"
+                     "with --min_samples samples called at both sites and both alleles seen at each), r2 = their mean r2, and\n"
+                     "sigma2_d = sum of D2 / sum of the heterozygosity products (NA without an ld_pair)",
+                     [("LD options", LD_OPTIONS), ("Sample filters", SAMPLE_OPTIONS), ("Site filters", SITE_OPTIONS), ("Device", LD_DEVICE_OPTIONS)])
+    return vars(parser.parse_args(argv))
+
+
+def check_ld_args(args):
+    check_trees_args(args)
+    if args['max_dist'] < 1:
+        _exit("--max_dist must be >= 1")
+    if args['max_dist'] >= LD_MAX_DIST:
+        _exit("--max_dist must be below 2^39")
+    if args['bin_width'] < 1:
+        _exit("--bin_width must be >= 1")
+    if -(-args['max_dist'] // args['bin_width']) > LD_MAX_BINS:
+        _exit("--max_dist / --bin_width gives more than %d distance bins: raise --bin_width" % LD_MAX_BINS)
+    if args['min_samples'] < 1:
+        _exit("--min_samples must be >= 1")
+    if args['group_rows'] < 0 or args['chunk_bytes'] < 0 or args['anchor_chunk'] < 0:
+        _exit("--group_rows, --chunk_bytes and --anchor_chunk cannot be negative")
+
+
+def print_ld_args(args):
+    rows = ["Command: %s" % ' '.join(sys.argv), "Script: snp_ld.py", "Input directory: %s" % args['indir'], "Output file: %s" % args['out']]
+    for title, names in (("LD options:", ['max_dist', 'bin_width', 'min_samples', 'within']),
+                         ("Sample filters:", ['sample_depth', 'fract_cov', 'max_samples', 'keep_samples', 'exclude_samples']),
                          ("Site filters:", ['site_list', 'site_depth', 'site_prev', 'site_maf', 'site_ratio', 'allele_support', 'locus_type',
                                             'site_type', 'max_sites'])):
         rows.append(title)

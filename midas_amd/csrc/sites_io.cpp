@@ -140,6 +140,11 @@ struct midas_sites_tables {
   std::vector<int32_t> gene;
   int64_t freq_columns = 0;
   Mapped freq, depth;
+  std::string dir;
+  bool have_positions = false;      // midas_sites_tables_positions has read these
+  std::vector<int32_t> contig;
+  std::vector<int64_t> ref_pos;
+  StrCol contig_names;
 };
 
 namespace {
@@ -213,6 +218,43 @@ int32_t read_info(const std::string& path, midas_sites_tables* t, char* err) {
   return MIDAS_SNPS_OK;
 }
 
+// ref_id -> contig index in order of first appearance, ref_pos -> int(): the rows read_info keeps (it skips empty lines)
+int32_t read_positions(const std::string& path, midas_sites_tables* t, char* err) {
+  Mapped m;
+  if (!m.open(path.c_str())) { fail(err, path, 0, "cannot be read"); return MIDAS_SNPS_ERR_INVALID_ARG; }
+  size_t p = 0;
+  std::string_view line;
+  std::vector<std::string_view> header, f;
+  if (!next_line(m.base, m.size, &p, &line)) { fail(err, path, 0, "is empty"); return MIDAS_SNPS_ERR_BAD_LAYOUT; }
+  split_tabs(line, &header);
+  const int c_id = last_column(header, "ref_id"), c_pos = last_column(header, "ref_pos");
+  if (c_id < 0 || c_pos < 0) {
+    fail(err, path, 1, c_id < 0 ? "the header lacks the column ref_id" : "the header lacks the column ref_pos");
+    return MIDAS_SNPS_ERR_BAD_LAYOUT;
+  }
+  std::vector<int32_t> contig;
+  std::vector<int64_t> ref_pos;
+  StrCol names;
+  std::unordered_map<std::string, int32_t> index;
+  for (long long ln = 2; next_line(m.base, m.size, &p, &line); ++ln) {
+    if (line.empty()) continue;
+    split_tabs(line, &f);
+    if ((int)f.size() <= std::max(c_id, c_pos)) { fail(err, path, ln, "the row lacks ref_id or ref_pos"); return MIDAS_SNPS_ERR_BAD_LAYOUT; }
+    int64_t pos = 0;
+    if (!midas::parse_i64_py(f[(size_t)c_pos], &pos)) { fail(err, path, ln, "ref_pos is not an integer"); return MIDAS_SNPS_ERR_BAD_LAYOUT; }
+    const std::string_view id = f[(size_t)c_id];
+    const auto it = index.emplace(std::string(id), (int32_t)index.size());
+    if (it.second) names.push(id);
+    contig.push_back(it.first->second);
+    ref_pos.push_back(pos);
+  }
+  t->contig.swap(contig);
+  t->ref_pos.swap(ref_pos);
+  t->contig_names = std::move(names);
+  t->have_positions = true;
+  return MIDAS_SNPS_OK;
+}
+
 int32_t map_matrix(const std::string& path, Mapped* m, std::vector<std::string_view>* header, char* err) {
   if (!m->open(path.c_str())) { fail(err, path, 0, "cannot be read"); return MIDAS_SNPS_ERR_INVALID_ARG; }
   size_t p = 0;
@@ -239,6 +281,7 @@ int32_t midas_sites_tables_open(const char* dir, midas_sites_tables** out, char*
   if (st == MIDAS_SNPS_OK) st = map_matrix(d + "/snps_freq.txt", &t->freq, &hf, err1024);
   if (st == MIDAS_SNPS_OK) st = map_matrix(d + "/snps_depth.txt", &t->depth, &hd, err1024);
   if (st != MIDAS_SNPS_OK) { delete t; return st; }
+  t->dir = d;
   t->freq_columns = (int64_t)hf.size() - 1;
   for (size_t k = 1; k < hd.size(); ++k) t->matrix_ids.push(hd[k]);
   *out = t;
@@ -275,6 +318,22 @@ int32_t midas_sites_tables_columns(const midas_sites_tables* t, const void** out
   out25[22] = t->depth.base ? t->depth.base + t->depth.body : nullptr;
   out25[23] = nullptr;
   out25[24] = nullptr;
+  return MIDAS_SNPS_OK;
+}
+
+int32_t midas_sites_tables_positions(midas_sites_tables* t, const void** out4, int64_t* sizes2, char* err1024) {
+  if (!t || !out4 || !sizes2) return MIDAS_SNPS_ERR_INVALID_ARG;
+  if (err1024) err1024[0] = 0;
+  if (!t->have_positions) {
+    const int32_t st = read_positions(t->dir + "/snps_info.txt", t, err1024);
+    if (st != MIDAS_SNPS_OK) return st;
+  }
+  out4[0] = t->contig.data();
+  out4[1] = t->ref_pos.data();
+  out4[2] = t->contig_names.pool.data();
+  out4[3] = t->contig_names.off.data();
+  sizes2[0] = (int64_t)t->contig_names.off.size() - 1;
+  sizes2[1] = (int64_t)t->contig_names.pool.size();
   return MIDAS_SNPS_OK;
 }
 
