@@ -167,13 +167,9 @@ def test_record_walk_is_not_fooled_by_bytes_that_look_like_records(tmp_path):
     n_pieces = min(nt * 4, span >> 20)
     assert n_pieces >= 8
     per = span // n_pieces
-    fake = bytearray()
-    for k in range(8):
-        rec = bytearray(33)
-        rec[0:4] = np.int32(0).tobytes(); rec[4:8] = np.int32(5 + k).tobytes()       # refID 0, pos
-        rec[8] = 1; rec[9] = 30                                                      # l_read_name 1 (just the NUL), mapq
-        rec[20:24] = np.int32(-1).tobytes(); rec[24:28] = np.int32(-1).tobytes()     # next refID, next pos
-        fake += np.int32(len(rec)).tobytes() + rec
+    from tests.bam_walk_model import decoy_records
+    fake = decoy_records(8)        # refID 0, pos 5 + k, l_read_name 1 (just the NUL), mapq 30, next refID / next pos -1
+    assert len(fake) == 8 * 37
     placed = 0
     qual = reads.qual.copy()
     for k in range(1, n_pieces):
