@@ -36,7 +36,7 @@ def _decimal(field, top):
 
 def parse_header(lines):
     """-> (names, lens, first record line index).  '@' lines come first; @SQ gives the references from SN: and LN:."""
-    names, lens, k = [], [], 0
+    names, lens, k, seen = [], [], 0, set()
     while k < len(lines) and lines[k].startswith(b"@"):
         f = lines[k].split(b"\t")
         if f[0] == b"@SQ":
@@ -46,8 +46,9 @@ def parse_header(lines):
             if not sn or not sn[0] or length is None:
                 raise SamError(k + 1, "@SQ without SN or LN")
             name = sn[0].decode("latin-1")
-            if name in set(names):
+            if name in seen:
                 raise SamError(k + 1, "duplicate SN")
+            seen.add(name)
             names.append(name)
             lens.append(length)
         k += 1
