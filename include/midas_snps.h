@@ -1248,6 +1248,39 @@ int32_t midas_genes_compare_write_pairs(const char* path, const midas_genes_matr
                                         int64_t n_rows, const int64_t* count, const double* both, const double* either, const double* dist,
                                         char* err1024);
 
+/* ---- gene_linkage.py: co-occurring pairs of genes and the groups they form -----------------------------
+ * midas_genes_linkage reads the rows of genes_copynum.txt as midas_genes_compare does (same text, widths, cell converter, row
+ *   groups, place of a bad row in out_stats16[4..6]).  Gene g is present in sample s when its value > cutoff; c_g counts the
+ *   n_samples used samples in which it is.  g is kept when c_g >= min_present and n_samples - c_g >= min_absent; the kept genes get
+ *   slots 0 .. K-1 in file order.  For slots a < b: both = popc(P_a & P_b) over the presence words (64 samples a word, pad bits
+ *   0), either = c_a + c_b - both; the pair is linked when both >= need[either].  need [n_samples + 1] (int32) is the caller's:
+ *   need[u] = the smallest n in [0, u] with (double)n / (double)u >= T, so the device holds no threshold and divides nothing.
+ *   iparams8 = group_rows, chunk_bytes (0: from the free device memory), min_present (>= 1), min_absent (>= 0), pair_form (0: a
+ *   partner's words in registers up to 16 words, 1: the form for any width), 0, 0, 0.
+ *   out_count / out_row_of_slot / out_label [n_rows_max] (int32): the first K entries are c, the 0-based data row and the label of
+ *   every slot; label[k] = the smallest slot of k's connected component in the graph of linked pairs (a singleton: k).
+ *   out_a / out_b / out_both [max_pairs] (int32): the linked pairs, ascending a, then ascending b, with their `both`.  More than
+ *   max_pairs (<= 2^31 - 1) linked pairs is MIDAS_SNPS_ERR_OUT_OF_MEMORY: out_stats16[11] holds the exact total and no output array
+ *   is written.  Nothing depends on group_rows, chunk_bytes or pair_form.
+ *   out_stats16: [0] rows read, [1] K, [4..6] a bad row, [7] row groups, [8] pairs visited K (K - 1) / 2, [9] group_rows and
+ *   [10] chunk_bytes in use, [11] linked pairs, [12] label rounds that changed a label, [13] words a lane keeps in registers (0:
+ *   the form for any width), [14] strips of 64 anchors.  out_ms8 (nullable): upload + index (host clock), index, parse, planes,
+ *   count pass, write pass (with the scan of the row starts), labels, download (device events).
+ * midas_genes_linkage_write_pairs: gene1, gene2, count1, count2, count_both, count_either, jaccard (repr of (double)both /
+ *   (double)either) for the pairs in their order.  midas_genes_linkage_write_groups: group_id, group_size, gene_id, count for
+ *   the slots of components of at least min_group slots; ids count from 1 in the order of the components' first genes, rows go
+ *   by group, then by slot; *out_n_groups (nullable) = the groups written.                                                     */
+int32_t midas_genes_linkage(midas_snps_ctx* ctx, const char* text, int64_t text_bytes, int64_t n_rows_max, int32_t n_samples,
+                            int32_t n_columns, double cutoff, const int64_t* iparams8, const int32_t* need, int64_t max_pairs,
+                            int32_t* out_count, int32_t* out_row_of_slot, int32_t* out_label, int32_t* out_a, int32_t* out_b,
+                            int32_t* out_both, int64_t* out_stats16, float* out_ms8);
+int32_t midas_genes_linkage_write_pairs(const char* path, const midas_genes_matrix* m, int64_t n_slots, const int32_t* count,
+                                        const int32_t* row_of_slot, int64_t n_pairs, const int32_t* pair_a, const int32_t* pair_b,
+                                        const int32_t* pair_both, char* err1024);
+int32_t midas_genes_linkage_write_groups(const char* path, const midas_genes_matrix* m, int64_t n_slots, const int32_t* count,
+                                         const int32_t* row_of_slot, const int32_t* label, int64_t min_group, int64_t* out_n_groups,
+                                         char* err1024);
+
 /* ---- run_species.py: the aligner's m8 lines classified (midas/run/species.py:51-119) -----------------------------------------
  * midas_species_classify: `text` (host memory) is the whole alignments.m8; it goes to the device chunk_bytes at a time and stays
  *   there.  A line's fields are its runs of non-blanks; query, target, pid (float), aln (int), score (float, field 12) are used and

@@ -398,6 +398,9 @@ def load_library(build_if_missing: bool = True):
         'midas_genes_compare_parse_cell': (i32, [C.c_char_p, i64, C.POINTER(C.c_double), C.POINTER(i32)]),
         'midas_genes_compare': (i32, [vp, vp, i64, i64, i32, i32, i32, i32, C.c_double] + [vp] * 9),
         'midas_genes_compare_write_pairs': (i32, [C.c_char_p, vp, i32, i32, i32, i64, vp, vp, vp, vp, C.c_char_p]),
+        'midas_genes_linkage': (i32, [vp, vp, i64, i64, i32, i32, C.c_double, vp, vp, i64] + [vp] * 8),
+        'midas_genes_linkage_write_pairs': (i32, [C.c_char_p, vp, i64, vp, vp, i64, vp, vp, vp, C.c_char_p]),
+        'midas_genes_linkage_write_groups': (i32, [C.c_char_p, vp, i64, vp, vp, vp, i64, C.POINTER(i64), C.c_char_p]),
         'midas_species_classify': (i32, [vp, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp, C.POINTER(vp)]),
         'midas_species_result_columns': (i32, [vp, vp, vp, vp]),
         'midas_species_result_lines': (i32, [vp] * 8),
@@ -455,6 +458,7 @@ EXPORTED_SYMBOLS = [
     'midas_genes_merge_format_f64',
     'midas_genes_matrix_open', 'midas_genes_matrix_counts', 'midas_genes_matrix_columns', 'midas_genes_matrix_close',
     'midas_genes_compare_parse_cell', 'midas_genes_compare', 'midas_genes_compare_write_pairs',
+    'midas_genes_linkage', 'midas_genes_linkage_write_pairs', 'midas_genes_linkage_write_groups',
 ]
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
@@ -1268,6 +1272,29 @@ class GenesMatrix:
                                                               p(either), p(dist), err)
         if st != 0:
             raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_compare_write_pairs failed")
+
+    def write_linkage(self, path: str, res: dict):
+        """The pair table of gene_linkage.py (midas_genes_linkage_write_pairs) from what Context.genes_linkage returned."""
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        arr = lambda k: np.ascontiguousarray(res[k], dtype=np.int32)
+        count, row, a, b, both = arr('count'), arr('row_of_slot'), arr('pair_a'), arr('pair_b'), arr('pair_both')
+        err = C.create_string_buffer(1024)
+        st = self._owner._lib.midas_genes_linkage_write_pairs(path.encode(), self._owner._h, count.shape[0], p(count), p(row), a.shape[0],
+                                                              p(a), p(b), p(both), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_linkage_write_pairs failed")
+
+    def write_groups(self, path: str, res: dict, min_group: int = 2) -> int:
+        """The group table of gene_linkage.py (midas_genes_linkage_write_groups) -> the groups written."""
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        arr = lambda k: np.ascontiguousarray(res[k], dtype=np.int32)
+        count, row, label = arr('count'), arr('row_of_slot'), arr('label')
+        err, n = C.create_string_buffer(1024), C.c_int64(0)
+        st = self._owner._lib.midas_genes_linkage_write_groups(path.encode(), self._owner._h, count.shape[0], p(count), p(row), p(label),
+                                                               int(min_group), C.byref(n), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_linkage_write_groups failed")
+        return int(n.value)
 
 
 def pandas_cell(text: bytes):
@@ -2248,6 +2275,38 @@ class Context:
         if dump:
             out['cells'] = cells[:, :n]
         return out
+
+    def genes_linkage(self, text, n_rows: int, n_samples: int, n_columns: int, need, cutoff: float = 0.35, min_present: int = 2,
+                      min_absent: int = 2, max_pairs: int = 1 << 26, group_rows: int = 0, chunk_bytes: int = 0, pair_form: int = 0,
+                      pair_out=None):
+        """midas_genes_linkage(): gene_linkage.py over the text rows of genes_copynum.txt, the first n_samples of n_columns sample
+        columns, rows [0, n_rows).  need: int32 [n_samples + 1], the fewest shared samples that link a pair at every size of the
+        union.  -> dict(n_rows read, n_samples, n_kept K, count, row_of_slot, label int32 [K], pair_a, pair_b, pair_both int32
+        [linked], visited, linked, label_rounds, groups, group_rows, chunk_bytes, form, strips, ms [8]).  More than max_pairs
+        linked pairs raises MidasSnpsError (ERR_OUT_OF_MEMORY) with .linked = the exact total; a malformed row raises it with
+        .bad as genes_compare.  pair_out (tests): three int32 arrays of max_pairs entries to receive the pairs."""
+        tx = np.ascontiguousarray(text, dtype=np.uint8)
+        S, N, cap = int(n_samples), int(n_rows), int(max_pairs)
+        nd = np.ascontiguousarray(need, dtype=np.int32)
+        if nd.shape != (S + 1,):
+            raise MidasSnpsError(ERR_INVALID_ARG, "need must hold n_samples + 1 entries")
+        count, row, label = np.zeros(N, np.int32), np.zeros(N, np.int32), np.zeros(N, np.int32)
+        pa, pb, pc = pair_out if pair_out is not None else (np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int32))
+        ip = np.array([group_rows, chunk_bytes, min_present, min_absent, pair_form, 0, 0, 0], np.int64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_genes_linkage(self._h, p(tx), tx.shape[0], N, S, int(n_columns), float(cutoff), p(ip), p(nd), cap, p(count),
+                                           p(row), p(label), p(pa), p(pb), p(pc), p(stats), p(ms))
+        try:
+            self._check_bad(st, stats)
+        except MidasSnpsError as e:
+            e.linked = int(stats[11]) if st == ERR_OUT_OF_MEMORY and stats[11] > cap else None
+            raise
+        K, n = int(stats[1]), int(stats[11])
+        return dict(n_rows=int(stats[0]), n_samples=S, n_kept=K, count=count[:K], row_of_slot=row[:K], label=label[:K],
+                    pair_a=pa[:n].copy(), pair_b=pb[:n].copy(), pair_both=pc[:n].copy(), visited=int(stats[8]), linked=n,
+                    label_rounds=int(stats[12]), groups=int(stats[7]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]),
+                    form=int(stats[13]), strips=int(stats[14]), ms=ms.tolist())
 
     def species_classify(self, text, gene_names, gene_species, gene_marker, n_species: int, marker_cutoff, aln_cov: float,
                          chunk_bytes: int = 0, hash_bits: int = 0, dump: bool = False):

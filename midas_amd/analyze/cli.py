@@ -487,6 +487,61 @@ def compare_genes_arguments(argv=None):
     return args
 
 
+def gene_linkage_arguments(argv=None):
+    """gene_linkage.py: the screen layout and the input rules of compare_genes.py; the linkage options are checked here, each
+    broken rule ends with the Error exit.  --group_rows and --chunk_bytes are hidden."""
+    parser = argparse.ArgumentParser(
+        prog='gene_linkage.py', formatter_class=argparse.RawTextHelpFormatter, usage=argparse.SUPPRESS,
+        description="Description:\nPairs of genes of one species that are present in the same samples, and the groups those pairs form,\n"
+                    "on the device.  Run `merge_midas.py genes` first.\n\nUsage: gene_linkage.py indir [options]\n",
+        epilog="Examples:\n"
+               "1) defaults (presence above copy number 0.35, pairs at a Jaccard index of 0.9 and above):\n"
+               "gene_linkage.py OUT/species_1 --out pairs.txt --groups groups.txt\n\n"
+               "2) identical profiles only, among genes found in at least 5 samples and missing from at least 5:\n"
+               "gene_linkage.py OUT/species_1 --out pairs.txt --min_jaccard 1.0 --min_present 5 --min_absent 5\n\n"
+               "3) looser links, groups of three genes and more:\n"
+               "gene_linkage.py OUT/species_1 --out pairs.txt --groups groups.txt --min_jaccard 0.75 --min_group 3\n")
+    parser.add_argument('indir', metavar='PATH', type=str,
+                        help="one species directory written by `merge_midas.py genes` (holds genes_presabs.txt,\n"
+                             "genes_copynum.txt, genes_depth.txt)")
+    parser.add_argument('--out', metavar='PATH', type=str, default='/dev/stdout', help="the table of linked pairs (/dev/stdout)")
+    parser.add_argument('--groups', metavar='PATH', type=str, help="the table of linkage groups (not written)")
+    parser.add_argument('--max_genes', metavar='INT', type=int, help="read this many genes (rows) only (all)")
+    parser.add_argument('--max_samples', metavar='INT', type=int, help="use the first INT samples (columns) only (all)")
+    parser.add_argument('--cutoff', metavar='FLOAT', type=float, default=0.35, help="a gene is present above this copy number (0.35)")
+    parser.add_argument('--min_present', metavar='INT', type=int, default=2, help="keep genes present in at least INT samples (2)")
+    parser.add_argument('--min_absent', metavar='INT', type=int, default=2, help="keep genes absent from at least INT samples (2)")
+    parser.add_argument('--min_jaccard', metavar='FLOAT', type=float, default=0.9,
+                        help="link two genes when samples with both / samples with either >= FLOAT (0.9)")
+    parser.add_argument('--min_group', metavar='INT', type=int, default=2, help="write groups of at least INT genes (2)")
+    parser.add_argument('--max_pairs', metavar='INT', type=int, default=1 << 26, help="stop when more pairs than this are linked (67108864)")
+    parser.add_argument('--group_rows', type=int, default=0, help=argparse.SUPPRESS)
+    parser.add_argument('--chunk_bytes', type=int, default=0, help=argparse.SUPPRESS)
+    args = vars(parser.parse_args(argv))
+    for ext in ['presabs', 'depth', 'copynum']:
+        inpath = '%s/genes_%s.txt' % (args['indir'], ext)
+        if not os.path.isfile(inpath):
+            sys.exit("\nError: Input file does not exist: %s\n" % inpath)
+        args[ext] = inpath
+    if args['cutoff'] != args['cutoff'] or args['cutoff'] in (float('inf'), float('-inf')):
+        _exit("--cutoff must be a finite number")
+    if args['min_present'] < 1:
+        _exit("--min_present must be >= 1: a gene found in no sample has no partner")
+    if args['min_absent'] < 0:
+        _exit("--min_absent cannot be a negative number")
+    if not 0 < args['min_jaccard'] <= 1:
+        _exit("--min_jaccard must be above 0 and at most 1")
+    if args['min_group'] < 2:
+        _exit("--min_group must be >= 2: a group is two linked genes or more")
+    if not 0 <= args['max_pairs'] < 1 << 31:
+        _exit("--max_pairs must be between 0 and 2147483647")
+    if args['group_rows'] < 0:
+        _exit("--group_rows cannot be a negative number")
+    if args['chunk_bytes'] < 0:
+        _exit("--chunk_bytes cannot be a negative number")
+    return args
+
+
 COPYRIGHT = ["", "MIDAS: Metagenomic Intra-species Diversity Analysis System", "analysis commands on AMD Instinct MI355X (midas_amd %s)",
              "after github.com/snayfach/MIDAS, Copyright (C) 2015-2016 Stephen Nayfach",
              "Freely distributed under the GNU General Public License (GPLv3)", ""]

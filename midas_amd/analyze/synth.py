@@ -147,3 +147,41 @@ def write_genes_dir(path, n_genes, n_samples, seed=0, block=100000, palette_size
             idx = np.where(rng.random((rows, n_samples)) < absent, 0, rng.integers(1, len(palette), (rows, n_samples)))
             f.write(_matrix_bytes(r0, idx, palette).tobytes())
     return dict(sample_ids=sample_ids)
+
+
+def write_linked_genes_dir(path, n_genes, n_samples, seed=0, groups=None, block=10000, flip=0.01):
+    """-> dict(sample_ids, group_of int32 [n_genes]: the planted group of every row, -1 none).  One species directory in the
+    shape `merge_midas.py genes` writes, for gene_linkage.py.  Most genes are independent of one another at mixed prevalence
+    (0.02 + 0.83 x a beta(0.6, 0.6) draw each: many rare, many common, none so near to core that chance alone links them).  groups: the sizes of the planted groups (default: one group for
+    every 400 genes, 5 to 50 genes each); the members of a group stand at rows drawn without order and copy one presence
+    profile with a share `flip` of their cells flipped, so the linked pairs are neither none nor a flood.  A present cell is a
+    short decimal above 0.4, an absent one 0.0 or, one in ten, 0.21."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    sample_ids = ['sample_%03d' % k for k in range(n_samples)]
+    if groups is None:
+        groups = [int(x) for x in rng.integers(5, 51, max(1, n_genes // 400))]
+    groups = [int(x) for x in groups]
+    if sum(groups) > n_genes:
+        raise ValueError("the planted groups hold %d genes, the matrix %d" % (sum(groups), n_genes))
+    group_of = np.full(n_genes, -1, np.int32)
+    rows = rng.permutation(n_genes)[:sum(groups)]
+    group_of[rows] = np.repeat(np.arange(len(groups), dtype=np.int32), groups)
+    profiles = rng.random((len(groups), n_samples)) < rng.uniform(0.15, 0.85, (len(groups), 1))
+    palette = ['0.0', '0.21'] + ['%.3f' % v for v in 0.4 + rng.gamma(2.0, 0.6, 62)]
+    header = ('\t'.join(['gene_id'] + sample_ids) + '\n').encode()
+    for kind in ('presabs', 'depth'):
+        with open(os.path.join(path, 'genes_%s.txt' % kind), 'wb') as f:
+            f.write(header)
+    with open(os.path.join(path, 'genes_copynum.txt'), 'wb') as f:
+        f.write(header)
+        for r0 in range(0, n_genes, block):
+            n = min(block, n_genes - r0)
+            present = rng.random((n, n_samples)) < 0.02 + 0.83 * rng.beta(0.6, 0.6, (n, 1))
+            g = group_of[r0:r0 + n]
+            planted = g >= 0
+            if planted.any():
+                present[planted] = profiles[g[planted]] ^ (rng.random((int(planted.sum()), n_samples)) < flip)
+            idx = np.where(present, rng.integers(2, len(palette), (n, n_samples)), (rng.random((n, n_samples)) < 0.1).astype(np.int64))
+            f.write(_matrix_bytes(r0, idx, palette).tobytes())
+    return dict(sample_ids=sample_ids, group_of=group_of)

@@ -4,7 +4,7 @@
 //   chunks   a run of bytes is uploaded; its complete rows are the group's candidates        (text_rows.h, as sites_rows.h)
 //   index    newlines counted per 16 bytes, exclusive scan, newline k's position -> ends[k]   (text_rows.h)
 //   parse    one thread a row walks its fields; the cells of the first S sample columns are converted as pandas' C reader
-//            converts them (pandas_f64.h: NOT float()), sample-major [sample][G].  A row of another width or a cell that is
+//            converts them (genes_rows.h, pandas_f64.h: NOT float()), sample-major [sample][G].  A row of another width or a cell that is
 //            no finite decimal literal is reported by (row, column), the earliest in file order
 //   bits     --dtype presabs: one wave a (sample, 64 genes): value > cutoff, the ballot is a word of the bit matrix; the pair
 //            counts are ss_pairs_kernel's popcounts (text_rows.h), integers held on the device across groups
@@ -33,6 +33,7 @@
 
 #include "../../include/midas_snps.h"
 #include "ctx_internal.h"
+#include "genes_rows.h"
 #include "kernels.h"
 #include "pandas_f64.h"
 #include "text_rows.h"
@@ -41,41 +42,6 @@ namespace midas {
 namespace {
 
 constexpr int kGeneRun = 32;        // genes of every sample of a strip staged at a time: 2 x 32 x 65 doubles = 33 KB of LDS
-
-struct GcParseP {
-  const char* text;            // the chunk
-  const uint32_t* ends;        // newline offsets of its rows
-  long long g, stride;         // rows to parse; row stride of a sample's values
-  int S, n_cols;               // sample columns converted (the first S); sample columns a row must have
-  double* val;                 // [S][stride]
-  uint32_t* col_float;         // [S] set when a cell of the column has '.' or an exponent
-  unsigned long long* bad;     // min over (row << 32 | column + 1); column + 1 == 0: the row has another width
-};
-
-__global__ __launch_bounds__(256) void gc_parse_kernel(GcParseP p) {
-  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (r >= p.g) return;
-  const uint32_t b = r == 0 ? 0u : p.ends[r - 1] + 1u;
-  uint32_t e = p.ends[r];
-  const char* t = p.text;
-  if (e > b && t[e - 1] == '\r') --e;
-  uint32_t q = b;
-  while (q < e && t[q] != '\t') ++q;         // the gene id
-  int c = 0;
-  while (q < e) {                            // t[q] is the tab in front of sample column c
-    const uint32_t fs = ++q;
-    while (q < e && t[q] != '\t') ++q;
-    if (c < p.S) {
-      double v = 0.0;
-      bool plain_int = true;
-      if (!pandas_f64(t + fs, (int)(q - fs), &v, &plain_int)) atomicMin(p.bad, ((unsigned long long)r << 32) | (unsigned long long)(c + 1));
-      else if (!plain_int) p.col_float[c] = 1u;
-      p.val[(long long)c * p.stride + r] = v;
-    }
-    ++c;
-  }
-  if (c != p.n_cols) atomicMin(p.bad, (unsigned long long)r << 32);
-}
 
 // presabs: bits[s][w] bit k = val[s][64 w + k] > cutoff
 __global__ __launch_bounds__(256) void gc_bits_kernel(const double* val, long long g, long long stride, int S, double cutoff,
@@ -157,26 +123,8 @@ __global__ __launch_bounds__(256) void gc_ordered_pairs_kernel(const double* val
     }
 }
 
-// ---- the host side of the matrix file ------------------------------------------------------------------------------------------
-void gm_fail(char* err1024, const std::string& path, long long line, const char* what) {
-  if (!err1024) return;
-  if (line > 0) snprintf(err1024, 1024, "%s, line %lld: %s", path.c_str(), line, what);
-  else snprintf(err1024, 1024, "%s: %s", path.c_str(), what);
-}
-
 }  // namespace
 }  // namespace midas
-
-struct midas_genes_matrix {
-  std::string path;
-  const char* base = nullptr;
-  size_t size = 0, body = 0;          // the mapping; offset of the first byte after the header line
-  std::vector<char> id_pool;          // the header's fields after the first, back to back
-  std::vector<int64_t> id_off{0};
-  std::string first_field;
-  int64_t n_rows = 0;
-  ~midas_genes_matrix() { if (base && size) munmap(const_cast<char*>(base), size); }
-};
 
 using namespace midas;
 
