@@ -50,6 +50,17 @@ def select(matrix, max_genes, max_samples):
     return n_rows, n_samples
 
 
+def exit_bad_row(matrix, e):
+    """Leaves with the message of a device call's error: its own, or the place of the row or cell that cannot be read."""
+    bad = getattr(e, 'bad', None)
+    if not bad:
+        _exit(e.message)
+    if bad[0] == 1:
+        _exit("%s, line %d: the row does not have %d sample columns" % (matrix.path, bad[1] + 2, matrix.n_columns))
+    _exit("%s, line %d, column %d (sample %s): the cell is not a finite decimal number"
+          % (matrix.path, bad[1] + 2, bad[2] + 2, matrix.sample_ids[bad[2]]))
+
+
 def compare(args, make_context=S.device_context):
     """The command.  make_context: tests substitute a CPU double of the device."""
     print("Reading gene copy-number matrix\n")
@@ -61,13 +72,7 @@ def compare(args, make_context=S.device_context):
                                 cutoff=float(args['cutoff']), group_rows=int(args.get('group_rows', 0) or 0),
                                 chunk_bytes=int(args.get('chunk_bytes', 0) or 0))
     except abi.MidasSnpsError as e:
-        bad = getattr(e, 'bad', None)
-        if not bad:
-            _exit(e.message)
-        if bad[0] == 1:
-            _exit("%s, line %d: the row does not have %d sample columns" % (matrix.path, bad[1] + 2, matrix.n_columns))
-        _exit("%s, line %d, column %d (sample %s): the cell is not a finite decimal number"
-              % (matrix.path, bad[1] + 2, bad[2] + 2, matrix.sample_ids[bad[2]]))
+        exit_bad_row(matrix, e)
     finally:
         ctx.close()
     if args['dtype'] == 'presabs':

@@ -48,16 +48,10 @@ def link(args, make_context=S.device_context):
                                 min_present=int(args['min_present']), min_absent=int(args['min_absent']), max_pairs=int(args['max_pairs']),
                                 group_rows=int(args.get('group_rows', 0) or 0), chunk_bytes=int(args.get('chunk_bytes', 0) or 0))
     except abi.MidasSnpsError as e:
-        bad = getattr(e, 'bad', None)
         if getattr(e, 'linked', None) is not None:
             _exit("%d pairs of genes are linked, more than --max_pairs %d: raise --min_jaccard or --max_pairs"
                   % (e.linked, args['max_pairs']))
-        if not bad:
-            _exit(e.message)
-        if bad[0] == 1:
-            _exit("%s, line %d: the row does not have %d sample columns" % (matrix.path, bad[1] + 2, matrix.n_columns))
-        _exit("%s, line %d, column %d (sample %s): the cell is not a finite decimal number"
-              % (matrix.path, bad[1] + 2, bad[2] + 2, matrix.sample_ids[bad[2]]))
+        genes_compare.exit_bad_row(matrix, e)
     finally:
         ctx.close()
     print("Rows read: %d" % res['n_rows'])

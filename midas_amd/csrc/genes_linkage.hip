@@ -16,9 +16,10 @@
 //              a singleton has its own slot
 //
 // The steps.
-//   parse      per row group, gc_parse_kernel (genes_rows.h): the cells sample-major [sample][row]
-//   planes     a workgroup takes 64 rows x 64 samples: a wave ballots a sample's 64 rows (the reads run along the rows, as the
-//              cells lie), the 64 x 64 bit block is turned in LDS and written gene-major [row][W]; then c_g and the keep flag a
+//   parse      per row group, GeneRows (genes_rows.h): the walk, the line index and gc_parse_kernel; the cells sample-major
+//              [sample][row]
+//   planes     planes_by_row_kernel over PresentCell (bit_planes.h): a workgroup takes 64 rows x 64 samples: a wave ballots a
+//              sample's 64 rows, the 64 x 64 bit block is turned in LDS and written gene-major [row][W]; then c_g and the keep flag a
 //              row, the library's exclusive scan of the flags, and a gather into the resident packed [K][W], count[K] and
 //              row_of_slot[K], appended behind the groups before
 //   pairs      a 256-thread workgroup owns a strip of 64 anchor slots, their words and counts in LDS, need[] beside them.  It
@@ -36,8 +37,6 @@
 //              slot: it is the component's smallest slot, whatever order the atomics took
 // No fp arithmetic beyond the cell parse, which pandas_f64.h spells with __dmul_rn / __ddiv_rn.
 #include <algorithm>
-#include <charconv>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -57,28 +56,6 @@ constexpr int kStrip = 64;          // anchor slots a workgroup
 constexpr int kStep = 256;          // partner slots a step: one a lane
 constexpr int kRegWords = 16;       // the most words of a partner a lane keeps in registers
 constexpr int kNeedLds = 4096;      // need[] lies in LDS while S + 1 <= this
-
-// planes[k][w] bit j = val[64 w + j][k] > cutoff for the group's rows k: blockIdx.x = 64 rows, blockIdx.y = the word.  Wave v
-// ballots the samples 16 v .. 16 v + 15 of the word, a lane a row; then thread t < 64 gathers bit t of the 64 sample words.
-__global__ __launch_bounds__(256) void gl_planes_kernel(const double* val, long long g, long long stride, int S, int W, double cutoff,
-                                                        unsigned long long* planes) {
-  __shared__ unsigned long long t[64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = blockIdx.y;
-  const long long k = (long long)blockIdx.x * 64 + lane;
-  for (int i = 0; i < 16; ++i) {
-    const int j = wave * 16 + i, s = w * 64 + j;
-    const bool present = k < g && s < S && val[(long long)s * stride + k] > cutoff;
-    const unsigned long long word = __ballot(present);
-    if (lane == 0) t[j] = word;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64 && k < g) {
-    unsigned long long c = 0;
-#pragma unroll 8
-    for (int j = 0; j < 64; ++j) c |= ((t[j] >> lane) & 1ull) << j;
-    planes[k * W + w] = c;
-  }
-}
 
 // c[r] = samples in which row r is present; flag[r] = the row is kept
 __global__ __launch_bounds__(256) void gl_keep_kernel(const unsigned long long* planes, long long g, int W, int S, int min_present,
@@ -287,36 +264,6 @@ std::string_view gl_gene_id(const midas_genes_matrix* m, const std::vector<size_
   return std::string_view(s, n);
 }
 
-struct GlWriter {
-  FILE* f = nullptr;
-  std::string buf;
-  bool ok = true;
-  explicit GlWriter(const char* path) : f(fopen(path, "w")) { buf.reserve(1 << 20); }
-  void i64(int64_t v) {
-    char tmp[24];
-    buf.append(tmp, (size_t)(std::to_chars(tmp, tmp + sizeof tmp, v).ptr - tmp));
-  }
-  void f64(double v) {
-    char tmp[40];
-    int64_t n = 0;
-    midas_genes_merge_format_f64(1, &v, tmp, sizeof tmp, &n);
-    buf.append(tmp, (size_t)(n > 0 ? n - 1 : 0));      // (without the formatter's '\n')
-  }
-  void row_done() {
-    buf.push_back('\n');
-    if (buf.size() > (1u << 20) - 4096) {
-      ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size() && ok;
-      buf.clear();
-    }
-  }
-  bool close() {
-    ok = (buf.empty() || fwrite(buf.data(), 1, buf.size(), f) == buf.size()) && ok;
-    ok = fclose(f) == 0 && ok;
-    f = nullptr;
-    return ok;
-  }
-};
-
 }  // namespace
 }  // namespace midas
 
@@ -328,19 +275,16 @@ int32_t midas_genes_linkage(midas_snps_ctx* ctx, const char* text, int64_t text_
                             int32_t n_columns, double cutoff, const int64_t* iparams8, const int32_t* need, int64_t max_pairs,
                             int32_t* out_count, int32_t* out_row_of_slot, int32_t* out_label, int32_t* out_a, int32_t* out_b,
                             int32_t* out_both, int64_t* out_stats16, float* out_ms8) {
-  if (!ctx || text_bytes < 0 || (text_bytes > 0 && !text) || n_rows_max < 0 || n_rows_max > 0x7FFFFFFFll || n_samples < 1 ||
-      n_samples > 65535 * 64 || n_columns < n_samples || !iparams8 || !out_stats16 || !need || iparams8[0] < 0 || iparams8[1] < 0 ||
-      iparams8[2] < 1 || iparams8[3] < 0 || iparams8[4] < 0 || iparams8[4] > 1 || max_pairs < 0 || max_pairs > 0x7FFFFFFFll ||
-      (n_rows_max > 0 && (!out_count || !out_row_of_slot || !out_label)) || (max_pairs > 0 && (!out_a || !out_b || !out_both)))
+  if (n_rows_max > 0x7FFFFFFFll || n_samples > 65535 * 64 || !iparams8 || !need || iparams8[2] < 1 || iparams8[3] < 0 || iparams8[4] < 0 ||
+      iparams8[4] > 1 || max_pairs < 0 || max_pairs > 0x7FFFFFFFll || (n_rows_max > 0 && (!out_count || !out_row_of_slot || !out_label)) ||
+      (max_pairs > 0 && (!out_a || !out_b || !out_both)))
     return MIDAS_SNPS_ERR_INVALID_ARG;
+  {
+    const int32_t rc = genes_begin(ctx, text, text_bytes, n_rows_max, n_samples, n_columns, iparams8, out_stats16, out_ms8);
+    if (rc != MIDAS_SNPS_OK) return rc;
+  }
   const int S = n_samples, W = (S + 63) / 64;
   const int min_present = (int)std::min<int64_t>(iparams8[2], (int64_t)S + 1), min_absent = (int)std::min<int64_t>(iparams8[3], (int64_t)S + 1);
-  ctx->clear_error();
-  ctx->err_read = -1;
-  for (int k = 0; k < 16; ++k) out_stats16[k] = 0;
-  out_stats16[5] = -1;
-  out_stats16[6] = -1;
-  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = 0.f;
   if (n_rows_max == 0 || text_bytes == 0) return MIDAS_SNPS_OK;
   SS_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -359,114 +303,53 @@ int32_t midas_genes_linkage(midas_snps_ctx* ctx, const char* text, int64_t text_
   SS_TRY(dev.get(&d_total, 8));
   SS_TRY(dev.get(&d_changed, 4));
   SS_TRY(hipMemcpyAsync(d_need, need, ((size_t)S + 1) * 4, hipMemcpyHostToDevice, st));
-  // ---- sizes: rows a group and bytes a chunk, from the caller or from a quarter of the free device memory --------------------
-  constexpr long long kChunkMax = 1ll << 30;    // newline offsets are 32-bit
-  long long G = iparams8[0], chunk_bytes = iparams8[1];
-  const long long per_row = (long long)S * 8 + (long long)W * 8 + 4 + 4 + 4 + 4;
-  if (G == 0 || chunk_bytes == 0) {
-    size_t free_b = 0, total_b = 0;
-    SS_TRY(hipMemGetInfo(&free_b, &total_b));
-    const long long budget = (long long)(free_b / 4);
-    if (chunk_bytes == 0) chunk_bytes = std::min<long long>(kChunkMax, std::max<long long>(1 << 20, budget / 4));
-    if (G == 0) G = std::max<long long>(1, (budget - std::min(budget / 2, 5 * chunk_bytes / 4)) / per_row);
-  }
-  chunk_bytes = std::min(std::max<long long>(chunk_bytes, 64), kChunkMax);
-  chunk_bytes = std::min(chunk_bytes, std::max<long long>(64, (long long)text_bytes + 1));
-  G = std::max<long long>(1, std::min<long long>(std::min<long long>(G, n_rows_max), chunk_bytes));
-  const size_t cells = (size_t)G * (size_t)S;
-  if (cells > 0xFFFFFFF0ull) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a row group beyond 2^32 cells: lower group_rows");
-  for (auto& x : ev.e) SS_TRY(hipEventCreate(&x));
-  Chunk ck;
-  ck.host = text;
-  ck.bytes = text_bytes;
+  // ---- the walk: the group's planes, its kept rows, their slots (the free memory is read behind the resident side) -------------
+  GeneRows rows(ctx, dev, ev, ms, out_stats16);
   {
-    const int32_t rc = chunk_alloc(ctx, dev, ck, chunk_bytes);
+    const int32_t rc = rows.init(text, text_bytes, n_rows_max, S, n_columns, iparams8[0], iparams8[1],
+                                 (long long)S * 8 + (long long)W * 8 + 4 + 4 + 4 + 4, n_rows_max);
     if (rc != MIDAS_SNPS_OK) return rc;
   }
-  uint32_t *d_scratch = nullptr, *d_col_float = nullptr, *d_flag = nullptr, *d_rank = nullptr;
-  double* d_val = nullptr;
+  const long long G = rows.G;
+  uint32_t *d_scratch = rows.d_scratch, *d_flag = nullptr, *d_rank = nullptr;
   unsigned long long* d_planes = nullptr;
   int32_t* d_c = nullptr;
-  SS_TRY(dev.get(&ck.d_ends, ((size_t)G + 1) * 4));
-  SS_TRY(dev.get(&ck.d_bad, 8));
-  SS_TRY(dev.get(&d_scratch, scan_scratch_words(std::max<long long>((kChunkMax + 16) / 16, n_rows_max)) * 4));
-  SS_TRY(dev.get(&d_val, cells * 8));
-  SS_TRY(dev.get(&d_col_float, (size_t)S * 4));
   SS_TRY(dev.get(&d_planes, (size_t)G * (size_t)W * 8));
   SS_TRY(dev.get(&d_c, (size_t)G * 4));
   SS_TRY(dev.get(&d_flag, (size_t)G * 4));
   SS_TRY(dev.get(&d_rank, (size_t)G * 4));
-  SS_TRY(hipMemsetAsync(d_col_float, 0, (size_t)S * 4, st));
-  long long base = 0, groups = 0, K = 0;
-  while (base < n_rows_max) {
-    const auto t_load = std::chrono::steady_clock::now();
+  long long K = 0;
+  for (;;) {
+    long long g = 0;
     {
-      const int32_t rc = chunk_load(ctx, st, ev, ck, chunk_bytes, G, d_scratch, &ms[1]);
+      const int32_t rc = rows.next(&g);
       if (rc != MIDAS_SNPS_OK) return rc;
     }
-    ms[0] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_load).count();
-    const long long g = std::min(ck.lines, std::min(G, n_rows_max - base));
-    if (g == 0) {
-      if (ck.at_eof) break;
-      if (chunk_bytes >= kChunkMax) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a matrix row longer than 1 GiB");
-      chunk_bytes = std::min(kChunkMax, chunk_bytes * 2);
-      const int32_t rc = chunk_alloc(ctx, dev, ck, chunk_bytes);
-      if (rc != MIDAS_SNPS_OK) return rc;
-      continue;
-    }
-    ++groups;
-    // ---- parse -------------------------------------------------------------------------------------------------------------
-    SS_TRY(hipMemsetAsync(ck.d_bad, 0xFF, 8, st));
-    SS_TRY(hipEventRecord(ev.e[2], st));
-    GcParseP pp;
-    pp.text = ck.d_text; pp.ends = ck.d_ends; pp.g = g; pp.stride = G; pp.S = S; pp.n_cols = n_columns; pp.val = d_val;
-    pp.col_float = d_col_float; pp.bad = ck.d_bad;
-    hipLaunchKernelGGL(gc_parse_kernel, dim3(nblocks(g, 256)), dim3(256), 0, st, pp);
-    SS_TRY(hipGetLastError());
-    SS_TRY(hipEventRecord(ev.e[3], st));
-    // ---- planes, kept rows, their slots ---------------------------------------------------------------------------------------
-    hipLaunchKernelGGL(gl_planes_kernel, dim3(nblocks(g, 64), (unsigned)W), dim3(256), 0, st, d_val, g, G, S, W, cutoff, d_planes);
+    if (g == 0) break;
+    hipLaunchKernelGGL((planes_by_row_kernel<1, PresentCell>), dim3(nblocks(g, 64), (unsigned)W), dim3(256), 0, st, PresentCell{rows.d_val, G, cutoff},
+                       g, S, W, d_planes, (unsigned long long*)nullptr);
     SS_TRY(hipGetLastError());
     hipLaunchKernelGGL(gl_keep_kernel, dim3(nblocks(g, 256)), dim3(256), 0, st, d_planes, g, W, S, min_present, min_absent, d_c, d_flag);
     SS_TRY(hipGetLastError());
     SS_TRY(launch_scan_u32(d_flag, d_rank, g, d_scratch, st));
-    hipLaunchKernelGGL(gl_gather_kernel, dim3(nblocks(g * W, 256)), dim3(256), 0, st, d_planes, d_c, d_flag, d_rank, g, W, base, K,
+    hipLaunchKernelGGL(gl_gather_kernel, dim3(nblocks(g * W, 256)), dim3(256), 0, st, d_planes, d_c, d_flag, d_rank, g, W, rows.base, K,
                        (long long)rows_cap, d_packed, d_count, d_row_of_slot);
     SS_TRY(hipGetLastError());
     SS_TRY(hipEventRecord(ev.e[4], st));
-    unsigned long long bad = kNoBad;
-    uint32_t end_at = 0, last_flag = 0, last_rank = 0;
-    SS_TRY(hipMemcpyAsync(&bad, ck.d_bad, 8, hipMemcpyDeviceToHost, st));
-    SS_TRY(hipMemcpyAsync(&end_at, ck.d_ends + g - 1, 4, hipMemcpyDeviceToHost, st));
+    uint32_t last_flag = 0, last_rank = 0;
     SS_TRY(hipMemcpyAsync(&last_flag, d_flag + g - 1, 4, hipMemcpyDeviceToHost, st));
     SS_TRY(hipMemcpyAsync(&last_rank, d_rank + g - 1, 4, hipMemcpyDeviceToHost, st));
-    SS_TRY(hipStreamSynchronize(st));
-    float t = 0.f;
-    SS_TRY(hipEventElapsedTime(&t, ev.e[2], ev.e[3]));
-    ms[2] += t;
-    SS_TRY(hipEventElapsedTime(&t, ev.e[3], ev.e[4]));
-    ms[3] += t;
-    if (bad != kNoBad) {          // the groups come in file order and a group reports its earliest: the file's earliest
-      const long long row = base + (long long)(bad >> 32), col = (long long)(bad & 0xFFFFFFFFull) - 1;
-      out_stats16[0] = base;
-      out_stats16[4] = col < 0 ? 1 : 2;
-      out_stats16[5] = row;
-      out_stats16[6] = col;
-      char buf[160];
-      if (col < 0) snprintf(buf, sizeof buf, "data row %lld: not %d sample columns wide", row, n_columns);
-      else snprintf(buf, sizeof buf, "data row %lld, sample column %lld: not a finite decimal number", row, col);
-      return ss_fail(ctx, MIDAS_SNPS_ERR_BAD_LAYOUT, buf);
+    {
+      const int32_t rc = rows.check(g);
+      if (rc != MIDAS_SNPS_OK) return rc;
     }
+    SS_TRY(rows.lap(3, 4, 3));
     K += (long long)last_flag + last_rank;
-    base += g;
-    ck.at = std::min(ck.bytes, ck.at + (long long)end_at + 1);
+    rows.advance(g);
   }
-  out_stats16[0] = base;
+  rows.end(nullptr);              // (the walk's statistics now: more pairs than max_pairs is an error that reports them)
   out_stats16[1] = K;
-  out_stats16[7] = groups;
   out_stats16[8] = K * (K - 1) / 2;
-  out_stats16[9] = G;
-  out_stats16[10] = chunk_bytes;
   // ---- the pairs: count pass, row starts, write pass ---------------------------------------------------------------------------
   int form = 0;
   if (iparams8[4] == 0 && W <= kRegWords) for (form = 1; form < W; form *= 2) {}
@@ -495,15 +378,13 @@ int32_t midas_genes_linkage(midas_snps_ctx* ctx, const char* text, int64_t text_
     SS_TRY(hipEventRecord(ev.e[1], st));
     SS_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st));
     SS_TRY(hipStreamSynchronize(st));
-    float t = 0.f;
-    SS_TRY(hipEventElapsedTime(&t, ev.e[0], ev.e[1]));
-    ms[4] += t;
+    SS_TRY(rows.lap(0, 1, 4));
   }
   out_stats16[11] = (int64_t)total;
   if (total > (unsigned long long)max_pairs) {
     char buf[200];
     snprintf(buf, sizeof buf, "%llu linked pairs of genes, but max_pairs is %lld", total, (long long)max_pairs);
-    if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = ms[k];
+    rows.end(out_ms8);
     return ss_fail(ctx, MIDAS_SNPS_ERR_OUT_OF_MEMORY, buf);
   }
   SS_TRY(dev.get(&d_label, (size_t)std::max<long long>(K, 1) * 4));
@@ -538,11 +419,8 @@ int32_t midas_genes_linkage(midas_snps_ctx* ctx, const char* text, int64_t text_
     }
     SS_TRY(hipEventRecord(ev.e[3], st));
     SS_TRY(hipStreamSynchronize(st));
-    float t = 0.f;
-    SS_TRY(hipEventElapsedTime(&t, ev.e[0], ev.e[1]));
-    ms[5] += t;
-    SS_TRY(hipEventElapsedTime(&t, ev.e[2], ev.e[3]));
-    ms[6] += t;
+    SS_TRY(rows.lap(0, 1, 5));
+    SS_TRY(rows.lap(2, 3, 6));
   }
   out_stats16[12] = rounds;
   // ---- download ----------------------------------------------------------------------------------------------------------------
@@ -559,10 +437,8 @@ int32_t midas_genes_linkage(midas_snps_ctx* ctx, const char* text, int64_t text_
   }
   SS_TRY(hipEventRecord(ev.e[1], st));
   SS_TRY(hipStreamSynchronize(st));
-  float t = 0.f;
-  SS_TRY(hipEventElapsedTime(&t, ev.e[0], ev.e[1]));
-  ms[7] += t;
-  if (out_ms8) for (int k = 0; k < 8; ++k) out_ms8[k] = ms[k];
+  SS_TRY(rows.lap(0, 1, 7));
+  rows.end(out_ms8);
   return MIDAS_SNPS_OK;
 }
 
@@ -578,7 +454,7 @@ int32_t midas_genes_linkage_write_pairs(const char* path, const midas_genes_matr
   for (int64_t e = 0; e < n_pairs; ++e)
     if (pair_a[e] < 0 || pair_a[e] >= n_slots || pair_b[e] < 0 || pair_b[e] >= n_slots) return MIDAS_SNPS_ERR_INVALID_ARG;
   const std::vector<size_t> at = gl_row_starts(m);
-  GlWriter w(path);
+  TableWriter w(path);
   if (!w.f) { gm_fail(err1024, path, 0, "cannot be written"); return MIDAS_SNPS_ERR_INVALID_ARG; }
   w.buf += "gene1\tgene2\tcount1\tcount2\tcount_both\tcount_either\tjaccard\n";
   for (int64_t e = 0; e < n_pairs; ++e) {
@@ -615,7 +491,7 @@ int32_t midas_genes_linkage_write_groups(const char* path, const midas_genes_mat
   std::vector<int32_t> member((size_t)n_slots);
   for (int64_t k = 0; k < n_slots; ++k) member[(size_t)fill[(size_t)label[k]]++] = (int32_t)k;
   const std::vector<size_t> at = gl_row_starts(m);
-  GlWriter w(path);
+  TableWriter w(path);
   if (!w.f) { gm_fail(err1024, path, 0, "cannot be written"); return MIDAS_SNPS_ERR_INVALID_ARG; }
   w.buf += "group_id\tgroup_size\tgene_id\tcount\n";
   int64_t id = 0;

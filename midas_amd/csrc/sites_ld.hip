@@ -4,12 +4,14 @@
 //   planes   the consensus calls of a group's retained sites, appended SITE-major to two resident bit matrices [retained site]
 //            [64 samples a word], `called` and `minor`, with the site's key and gene beside them: the window of an anchor never
 //            sees a group border.  A workgroup takes 64 retained sites x 64 samples: a wave ballots a sample's 64 sites (the cell
-//            reads run along the sites, as the cells lie), the 64 x 64 bit block is turned in LDS
+//            reads run along the sites, as the cells lie), the 64 x 64 bit block is turned in LDS (planes_by_row_kernel over
+//            ConsensusCell, bit_planes.h)
 //   ld       one wave an anchor; lanes take 64 consecutive partners a step, four popcount sums over the words each; the terms go
 //            through LDS, and one lane a quantity adds them in lane order.  The bin of a partner never falls along the walk, so a
 //            lane carries ONE running sum and stores it when the bin changes: p[anchor][bin] without bins in LDS
 //   fold     one lane a (bin, quantity) chain over the chunk's anchors in order, from the carried total
 // This file is compiled with -ffp-contract=off (build.py), as every file that parses the cells and calls the sites.
+#include "bit_planes.h"
 #include "sites_call.h"
 
 namespace midas {
@@ -29,41 +31,6 @@ __global__ __launch_bounds__(256) void ld_keep_list_kernel(const uint8_t* final_
   list[k] = (uint32_t)r;
   key[k] = gkey[r];
   gene[k] = ggene ? ggene[r] : 0;
-}
-
-// The planes of the group's m retained sites, [site][W words]: blockIdx.x = 64 sites, blockIdx.y = the word (64 samples).  Wave v
-// ballots the samples 16 v .. 16 v + 15 of the word, a lane a site; then thread t < 64 gathers bit t of the 64 sample words.
-__global__ __launch_bounds__(256) void ld_planes_kernel(const double* fv, const long long* dv, const uint8_t* cell, const uint32_t* list,
-                                                        long long m, long long stride, int S, int W, unsigned long long* called,
-                                                        unsigned long long* minor) {
-  __shared__ unsigned long long tc[64], tm[64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, w = blockIdx.y;
-  const long long k = (long long)blockIdx.x * 64 + lane;
-  const long long row = k < m ? (long long)list[k] : 0;
-  for (int i = 0; i < 16; ++i) {
-    const int j = wave * 16 + i, s = w * 64 + j;
-    bool is_called = false, is_minor = false;
-    if (k < m && s < S) {
-      const long long at = (long long)s * stride + row;
-      if ((cell[at] & 1) && dv[at] != 0) {
-        is_called = true;
-        is_minor = fv[at] >= 0.5;
-      }
-    }
-    const unsigned long long wc = __ballot(is_called), wm = __ballot(is_minor);
-    if (lane == 0) { tc[j] = wc; tm[j] = wm; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 64 && k < m) {
-    unsigned long long c = 0, mn = 0;
-#pragma unroll 8
-    for (int j = 0; j < 64; ++j) {
-      c |= ((tc[j] >> lane) & 1ull) << j;
-      mn |= ((tm[j] >> lane) & 1ull) << j;
-    }
-    called[k * W + w] = c;
-    minor[k * W + w] = mn;
-  }
 }
 
 struct LdP {
@@ -298,8 +265,8 @@ extern "C" int32_t midas_sites_ld(midas_snps_ctx* ctx, const char* freq, int64_t
     const long long kept_g = site.kept_g();
     if (m0 + kept_g > m_cap) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "more sites retained than the mask holds");
     if (kept_g > 0) {
-      hipLaunchKernelGGL(ld_planes_kernel, dim3(nblocks(kept_g, 64), (unsigned)W), dim3(256), 0, st, rg.d_fv, rg.d_dv, site.d_cell, d_list,
-                         kept_g, G, S, W, d_called + m0 * W, d_minor + m0 * W);
+      hipLaunchKernelGGL((planes_by_row_kernel<2, ConsensusCell>), dim3(nblocks(kept_g, 64), (unsigned)W), dim3(256), 0, st,
+                         ConsensusCell{rg.d_fv, rg.d_dv, site.d_cell, d_list, G}, kept_g, S, W, d_called + m0 * W, d_minor + m0 * W);
       SS_TRY(hipGetLastError());
     }
     SS_TRY(hipEventRecord(ev.e[5], st));        // (the list and the planes count as the order's phase)

@@ -39,9 +39,8 @@ __global__ __launch_bounds__(256) void sp_pairs_kernel(PairDivP p) {
   __shared__ double sf[2][kSpRun][PAD];
   __shared__ long long sd[W ? 2 : 1][W ? kSpRun : 1][W ? PAD : 1];
   __shared__ uint8_t sk[2][kSpRun][T];
-  int ti = 0, left = blockIdx.x;
-  while (left >= p.tiles_side - ti) { left -= p.tiles_side - ti; ++ti; }
-  const int tj = ti + left;
+  const PairTile tile = pair_tile(blockIdx.x, p.tiles_side);
+  const int ti = tile.ti, tj = tile.tj;
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const int base_s[2] = {ti * T, tj * T};
 
@@ -267,11 +266,10 @@ extern "C" int32_t midas_sites_pair_diversity(midas_snps_ctx* ctx, const char* f
   // one pair a lane (tiles of 16 x 16) unless the caller forces the 4 x 4 patch: on an MI355X the first form was the faster one at
   // every sample count measured, 50 to 1 500 (profiles/snp_pairs.txt) -- the fold is bound by its instructions, not by the loads
   const int patch = iparams8[6] == 2 ? 4 : 1;
-  const int tile = 16 * patch, tiles_side = (S + tile - 1) / tile;
-  const long long n_tiles = (long long)tiles_side * (tiles_side + 1) / 2;
-  if (n_tiles > 0x7FFFFFFFll) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "more pair tiles than a grid holds");
+  const PairTiles tiles = pair_tiles(S, 16 * patch);
+  if (tiles.n > 0x7FFFFFFFll) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "more pair tiles than a grid holds");
   PairDivP q;
-  q.fv = rg.d_fv; q.dv = rg.d_dv; q.cell = site.d_cell; q.row_keep = site.d_final; q.stride = rg.G; q.S = S; q.tiles_side = tiles_side;
+  q.fv = rg.d_fv; q.dv = rg.d_dv; q.cell = site.d_cell; q.row_keep = site.d_final; q.stride = rg.G; q.S = S; q.tiles_side = tiles.side;
   q.round_freq = round_freq; q.max_sites = max_sites; q.site_maf = fparams5[3]; q.snp_maf = fparams5[4];
   {
     // GenomicSite.filter's prevalence test, count / 2 against max(1e-6, site_prev), once for the three counts there are
@@ -300,8 +298,8 @@ extern "C" int32_t midas_sites_pair_diversity(midas_snps_ctx* ctx, const char* f
       if (rc != MIDAS_SNPS_OK) return rc;
     }
     q.g = g;
-    if (patch == 1) sp_launch<1>(q, weight != 0, n_tiles, st);
-    else sp_launch<4>(q, weight != 0, n_tiles, st);
+    if (patch == 1) sp_launch<1>(q, weight != 0, tiles.n, st);
+    else sp_launch<4>(q, weight != 0, tiles.n, st);
     SS_TRY(hipGetLastError());
     pair_sites += n_pairs * g;
     SS_TRY(hipEventRecord(ev.e[6], st));
@@ -327,7 +325,7 @@ extern "C" int32_t midas_sites_pair_diversity(midas_snps_ctx* ctx, const char* f
   out_stats16[1] = site.kept;
   out_stats16[8] = pair_sites;
   out_stats16[11] = patch;
-  out_stats16[12] = n_tiles;
+  out_stats16[12] = tiles.n;
   sites_end(rg, out_ms8);
   return MIDAS_SNPS_OK;
 }

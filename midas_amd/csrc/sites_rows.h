@@ -9,7 +9,8 @@
 //            int -> fp64 conversion, one IEEE multiply or divide: correctly rounded), or [+-]digits up to 18 of them for
 //            the depth; every other cell goes to a side list, which the host converts with its exact parser and patches
 //            in before the caller's kernels run.  Values land sample-major, [sample][row]
-// (chunks, the line index and the pair kernel live in text_rows.h, shared with genes_compare.hip)
+// (chunks, the line index, the pair tiles and the popcount pair kernel live in text_rows.h, shared with genes_rows.h; the sizes of
+// a walk are row_group_plan.h's, the kernels that turn calls into bit planes bit_planes.h's)
 // Also here: what the entry points check and set up alike before the walk (sites_begin), and the statistics they all close
 // with (sites_end).  Everything has internal linkage: each of the files compiles its own copy, with -ffp-contract=off
 // (build.py): fast_f64's one multiply or divide must stay one.
@@ -27,6 +28,7 @@
 #include "../../include/midas_snps.h"
 #include "ctx_internal.h"
 #include "kernels.h"
+#include "row_group_plan.h"
 #include "text_numbers.h"
 #include "text_rows.h"
 
@@ -210,8 +212,6 @@ struct RowGroups {
   uint32_t end_at[2] = {0, 0};
   unsigned long long bad[2] = {kNoBad, kNoBad};
 
-  static constexpr long long kChunkMax = (1ll << 30);       // newline offsets are 32-bit
-
   RowGroups(midas_snps_ctx* c, SsBufs& d, SsEvents& e, float* ms8, int64_t* stats16) : ctx(c), st(c->stream), dev(d), ev(e), ms(ms8), stats(stats16) {}
 
   int32_t alloc_chunk(Chunk& c, long long cb) { return chunk_alloc(ctx, dev, c, cb); }
@@ -223,19 +223,11 @@ struct RowGroups {
     S = n_samples;
     n_cols = (int)col_slot.size();
     n_sites_max = n_max;
-    G = G_in;
-    chunk_bytes = chunk_in;
-    if (G == 0 || chunk_bytes == 0) {
-      size_t free_b = 0, total_b = 0;
-      SS_TRY(hipMemGetInfo(&free_b, &total_b));
-      const long long budget = (long long)(free_b / 4);
-      if (chunk_bytes == 0) chunk_bytes = std::min<long long>(kChunkMax, std::max<long long>(1 << 20, budget / 8));
-      if (G == 0) G = std::max<long long>(1, (budget - std::min(budget / 2, 5 * chunk_bytes / 2)) / per_row);
-    }
-    chunk_bytes = std::min(std::max<long long>(chunk_bytes, 64), kChunkMax);
-    chunk_bytes = std::min(chunk_bytes, std::max<long long>(64, std::max(freq_bytes, depth_bytes) + 1));
-    G = std::min<long long>(std::min<long long>(G, n_sites_max), chunk_bytes);
-    G = std::max<long long>(G, 1);
+    size_t free_b = 0, total_b = 0;
+    if (G_in == 0 || chunk_in == 0) SS_TRY(hipMemGetInfo(&free_b, &total_b));
+    const RowGroupPlan plan = plan_row_groups(free_b, G_in, chunk_in, 2, std::max(freq_bytes, depth_bytes), n_sites_max, per_row);
+    G = plan.G;
+    chunk_bytes = plan.chunk_bytes;
     cells = (size_t)G * (size_t)S;
     if (cells > 0xFFFFFFF0ull) return ss_fail(ctx, MIDAS_SNPS_ERR_UNSUPPORTED, "a row group beyond 2^32 cells: lower group_rows");
     for (auto& x : ev.e) SS_TRY(hipEventCreate(&x));
@@ -258,12 +250,7 @@ struct RowGroups {
     return MIDAS_SNPS_OK;
   }
 
-  hipError_t lap(int a, int b, int slot) {
-    float t = 0.f;
-    const hipError_t e = hipEventElapsedTime(&t, ev.e[a], ev.e[b]);
-    if (e == hipSuccess) ms[slot] += t;
-    return e;
-  }
+  hipError_t lap(int a, int b, int slot) { return ev.lap(a, b, &ms[slot]); }
 
   // upload the next chunk of one matrix and index its lines (text_rows.h)
   int32_t load_chunk(Chunk& c) { return chunk_load(ctx, st, ev, c, chunk_bytes, G, d_scratch, &ms[1]); }

@@ -294,8 +294,7 @@ extern "C" int32_t midas_sites_track_markers(midas_snps_ctx* ctx, const char* fr
   SS_TRY(dev.get(&d_both, n_acc * 8));
   SS_TRY(dev.get(&d_err, 8));
   SS_TRY(hipMemsetAsync(d_both, 0, n_acc * 8, st));
-  const int tiles_side = (S + kPairTile - 1) / kPairTile;
-  const long long n_tiles = (long long)tiles_side * (tiles_side + 1) / 2;
+  const PairTiles tiles = pair_tiles(S, kPairTile);
   const long long pair_blocks = iparams8[5] > 0 ? iparams8[5] : 1024;      // workgroups the pair kernel aims at
   long long matched = 0, word_pairs = 0, max_runs = 0, max_steps = 0;
   for (;;) {
@@ -329,9 +328,9 @@ extern "C" int32_t midas_sites_track_markers(midas_snps_ctx* ctx, const char* fr
                            fparams2[0], (double)iparams8[0], d_bits, wstride, d_err);
         SS_TRY(hipGetLastError());
         SS_TRY(hipEventRecord(ev.e[5], st));
-        const PairRuns pr = pair_runs(n_words, n_tiles, pair_blocks, kPairRun);
-        hipLaunchKernelGGL(ss_pairs_kernel, dim3((unsigned)n_tiles, (unsigned)pr.runs), dim3(256), 0, st, d_bits, wstride, n_words, pr.run_words,
-                           S, tiles_side, d_both);
+        const PairRuns pr = pair_runs(n_words, tiles.n, pair_blocks, kPairRun);
+        hipLaunchKernelGGL(ss_pairs_kernel, dim3((unsigned)tiles.n, (unsigned)pr.runs), dim3(256), 0, st, d_bits, wstride, n_words, pr.run_words,
+                           S, tiles.side, d_both);
         SS_TRY(hipGetLastError());
         SS_TRY(hipEventRecord(ev.e[6], st));
         SS_TRY(hipMemcpyAsync(&err, d_err, 8, hipMemcpyDeviceToHost, st));

@@ -1,8 +1,10 @@
 // snp_trees.py on MI355X (midas_sites_consensus_pairs): the rows of snps_freq.txt / snps_depth.txt walked as midas_sites_scan
 // walks them (RowGroups, sites_rows.h), the site kernel and the order of call_consensus.py (SiteStep, sites_call.h), then
-//   planes   the consensus calls of a group's retained sites as two bit matrices, `called` and `minor`, one wave a word
+//   planes   the consensus calls of a group's retained sites as two bit matrices [sample][64 retained sites a word], `called` and
+//            `minor`, one wave a word (planes_by_sample_kernel over ConsensusCell, bit_planes.h)
 //   pairs    both[i][j] += popcount(C_i & C_j), diff[i][j] += popcount(C_i & C_j & (M_i ^ M_j)), the tiling of the pair kernel
 // This file is compiled with -ffp-contract=off (build.py), as every file that parses the cells and calls the sites.
+#include "bit_planes.h"
 #include "sites_call.h"
 
 namespace midas {
@@ -14,29 +16,6 @@ __global__ __launch_bounds__(256) void ss_keep_list_kernel(const uint8_t* final_
   if (r < g && final_keep[r]) list[rank[r]] = (uint32_t)r;
 }
 
-// The planes [sample][64 retained sites a word], from the parsed cells.  One wave a (sample, 64 retained sites): `called` where
-// ss_seq_kernel writes a letter (the cell is kept and depth != 0), `minor` where that letter is the minor allele (freq >= 0.5).
-__global__ __launch_bounds__(256) void ss_planes_kernel(const double* fv, const long long* dv, const uint8_t* cell, const uint32_t* list,
-                                                        long long m, long long stride, int S, unsigned long long* called,
-                                                        unsigned long long* minor, long long wstride) {
-  const int s = blockIdx.y * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (s >= S) return;                                  // (the whole wave)
-  const long long k = (long long)blockIdx.x * 64 + lane;
-  bool is_called = false, is_minor = false;
-  if (k < m) {
-    const long long at = (long long)s * stride + list[k];
-    if ((cell[at] & 1) && dv[at] != 0) {
-      is_called = true;
-      is_minor = fv[at] >= 0.5;
-    }
-  }
-  const unsigned long long wc = __ballot(is_called), wm = __ballot(is_minor);
-  if (lane == 0) {
-    called[(long long)s * wstride + blockIdx.x] = wc;
-    minor[(long long)s * wstride + blockIdx.x] = wm;
-  }
-}
-
 // both[i][j] += popcount(C_i & C_j), diff[i][j] += popcount(C_i & C_j & (M_i ^ M_j)) for i <= j: ss_pairs_kernel's tiling (a
 // 64 x 64 tile of pairs a workgroup, a 4 x 4 part of it a thread, a run of words along blockIdx.y) over two planes.  Four strips
 // are staged, 16 words at a time: the static LDS of ss_pairs_kernel's two strips of 32.
@@ -45,9 +24,8 @@ __global__ __launch_bounds__(256) void ss_plane_pairs_kernel(const unsigned long
                                                              long long wstride, long long n_words, long long run_words, int S,
                                                              int tiles_side, unsigned long long* both, unsigned long long* diff) {
   __shared__ unsigned long long ca[kPlaneRun][kPairPad], cb[kPlaneRun][kPairPad], ma[kPlaneRun][kPairPad], mb[kPlaneRun][kPairPad];
-  int ti = 0, left = blockIdx.x;
-  while (left >= tiles_side - ti) { left -= tiles_side - ti; ++ti; }
-  const int tj = ti + left;
+  const PairTile tile = pair_tile(blockIdx.x, tiles_side);
+  const int ti = tile.ti, tj = tile.tj;
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const long long w0 = (long long)blockIdx.y * run_words, w1 = w0 + run_words < n_words ? w0 + run_words : n_words;
   uint32_t nb[4][4], nd[4][4];
@@ -164,8 +142,7 @@ extern "C" int32_t midas_sites_consensus_pairs(midas_snps_ctx* ctx, const char* 
   SS_TRY(dev.get(&d_diff, n_acc * 8));
   SS_TRY(hipMemsetAsync(d_both, 0, n_acc * 8, st));
   SS_TRY(hipMemsetAsync(d_diff, 0, n_acc * 8, st));
-  const int tiles_side = (S + kPairTile - 1) / kPairTile;
-  const long long n_tiles = (long long)tiles_side * (tiles_side + 1) / 2;
+  const PairTiles tiles = pair_tiles(S, kPairTile);
   const long long pair_blocks = iparams8[6] > 0 ? iparams8[6] : 1024;      // workgroups the pair kernel aims at
   long long word_pairs = 0, max_runs = 0, max_steps = 0;
   bool stop = false;
@@ -185,15 +162,15 @@ extern "C" int32_t midas_sites_consensus_pairs(midas_snps_ctx* ctx, const char* 
     SS_TRY(hipStreamSynchronize(st));
     const long long kept_g = site.kept_g(), n_words = (kept_g + 63) / 64;
     if (kept_g > 0) {
-      hipLaunchKernelGGL(ss_planes_kernel, dim3((unsigned)n_words, (unsigned)((S + 3) / 4)), dim3(256), 0, st, rg.d_fv, rg.d_dv, site.d_cell,
-                         d_list, kept_g, G, S, d_called, d_minor, wstride);
+      hipLaunchKernelGGL((planes_by_sample_kernel<2, ConsensusCell>), dim3((unsigned)n_words, (unsigned)((S + 3) / 4)), dim3(256), 0, st,
+                         ConsensusCell{rg.d_fv, rg.d_dv, site.d_cell, d_list, G}, kept_g, S, wstride, d_called, d_minor);
       SS_TRY(hipGetLastError());
     }
     SS_TRY(hipEventRecord(ev.e[5], st));        // (again: the list and the planes count as the order's phase)
     if (kept_g > 0) {
-      const PairRuns pr = pair_runs(n_words, n_tiles, pair_blocks, kPlaneRun);
-      hipLaunchKernelGGL(ss_plane_pairs_kernel, dim3((unsigned)n_tiles, (unsigned)pr.runs), dim3(256), 0, st, d_called, d_minor, wstride,
-                         n_words, pr.run_words, S, tiles_side, d_both, d_diff);
+      const PairRuns pr = pair_runs(n_words, tiles.n, pair_blocks, kPlaneRun);
+      hipLaunchKernelGGL(ss_plane_pairs_kernel, dim3((unsigned)tiles.n, (unsigned)pr.runs), dim3(256), 0, st, d_called, d_minor, wstride,
+                         n_words, pr.run_words, S, tiles.side, d_both, d_diff);
       SS_TRY(hipGetLastError());
       word_pairs += (long long)S * (S + 1) / 2 * n_words;
       max_runs = std::max(max_runs, pr.runs);

@@ -1,6 +1,8 @@
-// The text-matrix walker's parts that sites_rows.h and genes_compare.hip share: a run of bytes of a tab-separated matrix
-// uploaded as a chunk, its newline index (newlines counted per 16 bytes, the library's exclusive scan, newline k's position ->
-// ends[k]), the device buffer and event holders, and the popcount pair kernel over a bit matrix [sample][64 rows a word].
+// The text-matrix walkers' parts that sites_rows.h (RowGroups) and genes_rows.h (GeneRows) share: a run of bytes of a
+// tab-separated matrix uploaded as a chunk, its newline index (newlines counted per 16 bytes, the library's exclusive scan,
+// newline k's position -> ends[k]), the device buffer and event holders, the tiles of sample pairs every pair kernel is launched
+// over (pair_tiles, pair_tile), and the popcount pair kernel over a bit matrix [sample][64 rows a word].  The kernels that make
+// such bit matrices are bit_planes.h's; the sizes of a walk are row_group_plan.h's.
 // species_hits.hip and species_merge.hip take the index kernels and the exact one-multiply float() decoder from here too.
 // Everything has internal linkage: each of the files compiles its own copy.
 #pragma once
@@ -134,6 +136,12 @@ struct SsBufs {
 struct SsEvents {
   hipEvent_t e[8] = {};
   ~SsEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  hipError_t lap(int a, int b, float* ms) {      // *ms += the device time from e[a] to e[b]
+    float t = 0.f;
+    const hipError_t err = hipEventElapsedTime(&t, e[a], e[b]);
+    if (err == hipSuccess) *ms += t;
+    return err;
+  }
 };
 
 unsigned nblocks(long long n, long long per) { return (unsigned)((n + per - 1) / per); }
@@ -157,6 +165,19 @@ struct Chunk {
 constexpr int kPairTile = MIDAS_SITES_PAIR_TILE;      // samples a side of a workgroup's tile of pairs
 constexpr int kPairRun = 32;                          // words of every sample staged at a time
 constexpr int kPairPad = kPairTile + 1;               // the staged words lie [word][sample]: 65 keeps the transposing stores apart
+
+// The tiles of `tile` samples a side on or above the diagonal of the S x S pairs, counted row by row: a pair kernel's blockIdx.x
+struct PairTiles { int side; long long n; };
+PairTiles pair_tiles(int S, int tile) {
+  const int side = (S + tile - 1) / tile;
+  return PairTiles{side, (long long)side * (side + 1) / 2};
+}
+struct PairTile { int ti, tj; };                      // ti <= tj
+__device__ __forceinline__ PairTile pair_tile(int block, int tiles_side) {
+  int ti = 0, left = block;
+  while (left >= tiles_side - ti) { left -= tiles_side - ti; ++ti; }
+  return PairTile{ti, ti + left};
+}
 // both[i][j] += sum over words of popcount(B[i][w] & B[j][w]) for i <= j.  A workgroup owns a 64 x 64 tile of pairs on or
 // above the diagonal (blockIdx.x counts those tiles row by row) and a run of words (blockIdx.y); it stages 32 words of its
 // two strips of samples in LDS, [word][sample], and a thread keeps a 4 x 4 part of the tile: rows ty + 16 i, columns
@@ -165,9 +186,8 @@ constexpr int kPairPad = kPairTile + 1;               // the staged words lie [w
 __global__ __launch_bounds__(256) void ss_pairs_kernel(const unsigned long long* bits, long long wstride, long long n_words, long long run_words,
                                                        int S, int tiles_side, unsigned long long* both) {
   __shared__ unsigned long long sa[kPairRun][kPairPad], sb[kPairRun][kPairPad];
-  int ti = 0, left = blockIdx.x;
-  while (left >= tiles_side - ti) { left -= tiles_side - ti; ++ti; }
-  const int tj = ti + left;
+  const PairTile tile = pair_tile(blockIdx.x, tiles_side);
+  const int ti = tile.ti, tj = tile.tj;
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
   const long long w0 = (long long)blockIdx.y * run_words, w1 = w0 + run_words < n_words ? w0 + run_words : n_words;
   uint32_t sum[4][4];
@@ -254,9 +274,7 @@ int32_t chunk_load(midas_snps_ctx* ctx, hipStream_t st, SsEvents& ev, Chunk& c, 
   SS_TRY(hipGetLastError());
   SS_TRY(hipEventRecord(ev.e[2], st));
   SS_TRY(hipStreamSynchronize(st));
-  float t = 0.f;
-  SS_TRY(hipEventElapsedTime(&t, ev.e[1], ev.e[2]));
-  *index_ms += t;
+  SS_TRY(ev.lap(1, 2, index_ms));
   c.lines = (long long)last_count + last_prefix;
   return MIDAS_SNPS_OK;
 }

@@ -116,6 +116,61 @@ def read_cells(text, n_rows, n_samples, n_columns):
     return cells, col_float
 
 
+def walk(text, n_rows, group_rows, chunk_bytes):
+    """The walk of rows [0, n_rows) of a body of less than 1 MiB by row groups, as the statistics report it -> (rows read,
+    groups, group_rows, chunk_bytes).  A chunk is the next chunk_bytes bytes (at least 64, at most the body and one byte; 0:
+    that), a final line without '\\n' gets one; a group is the chunk's complete lines, at most group_rows (0: n_rows) of them;
+    a chunk without a complete line is doubled."""
+    text = text.tobytes() if isinstance(text, np.ndarray) else text
+    n = len(text)
+    cb = min(max(chunk_bytes if chunk_bytes else 1 << 20, 64), max(64, n + 1))
+    G = max(1, min(group_rows if group_rows else n_rows, n_rows, cb))
+    at = base = groups = 0
+    while base < n_rows:
+        chunk = text[at:at + cb]
+        eof = at + len(chunk) == n
+        if eof and chunk and not chunk.endswith(b'\n'):
+            chunk += b'\n'
+        ends = [k for k, c in enumerate(chunk) if c == 10]
+        g = min(len(ends), G, n_rows - base)
+        if g == 0:
+            if eof:
+                break
+            cb *= 2
+            continue
+        groups += 1
+        base += g
+        at = min(n, at + ends[g - 1] + 1)
+    return base, groups, G, cb
+
+
+def walker_cases():
+    """The borders of the walk on 50 rows of 6 samples, row 20 longer than 64 bytes -> [(name, body uint8, n_rows, group_rows,
+    chunk_bytes)]: a chunk that must grow, a last line without '\\n', CRLF, fewer rows asked for than the file has, groups of
+    one row."""
+    rng = np.random.default_rng(3)
+    spell = ('1.5', '0.36', '0.0', '0.35', '12', '7e-1', '0', '3.4e-1')
+    rows = [['g%d' % r] + [spell[k] for k in rng.integers(0, len(spell), 6)] for r in range(50)]
+    rows[20][1:] = ['1.50000000000000000', '0.00000000000000000', '0.36000000000000000', '0.0', '12.0000000000000000', '0.35']
+    assert len('\t'.join(rows[20])) > 64 and max(len('\t'.join(r)) for r in rows[:20] + rows[21:]) < 40
+
+    def body(eol='\n', last=True):
+        t = eol.join('\t'.join(r) for r in rows) + (eol if last else '')
+        return np.frombuffer(t.encode(), np.uint8)
+    return [('grow', body(), 50, 7, 64), ('no last newline', body(last=False), 50, 7, 256), ('no last newline, one group', body(last=False), 50, 0, 0),
+            ('crlf', body('\r\n'), 50, 7, 256), ('crlf, no last newline', body('\r\n', False), 50, 0, 100), ('fewer rows', body(), 33, 10, 200),
+            ('fewer rows, one group', body(), 33, 0, 0), ('one row a group', body(), 50, 1, 0), ('one row a group, grow', body(), 50, 1, 64)]
+
+
+def walker_bad_body():
+    """Row 5 is short and row 15 holds a cell that is no number: with groups of 10 rows the short row is the first group's and
+    must win -> (body, .bad)."""
+    rows = [['g%d' % r, '1.5', '0.0', '0.36', '0', '12', '0.35'] for r in range(30)]
+    rows[5].pop()
+    rows[15][2] = 'NA'
+    return np.frombuffer(('\n'.join('\t'.join(r) for r in rows) + '\n').encode(), np.uint8), (1, 5, -1)
+
+
 def ordered_sum(x):
     """sum() of the rows of x [rows, ...] front to back, one fp64 add each (numpy's cumsum adds sequentially; the host test
     checks that against Python's sum)."""

@@ -143,6 +143,31 @@ def test_the_earliest_bad_cell_is_reported_whatever_the_groups_are(ctx, tmp_path
     assert r.returncode == 1 and "genes_copynum.txt, line 51, column 4 (sample s002): the cell is not a finite decimal number" in r.stderr
 
 
+WALKS = M.walker_cases()
+
+
+@pytest.mark.parametrize("k", range(len(WALKS)), ids=[w[0] for w in WALKS])
+def test_the_walk_of_the_rows_at_its_borders(ctx, k):
+    name, body, n_rows, group_rows, chunk = WALKS[k]
+    walk = M.walk(body, n_rows, group_rows, chunk)
+    assert walk[0] == n_rows and (name != 'grow' or walk[3] == 128) and (group_rows != 1 or walk[1] == n_rows)
+    cells, col_float = M.read_cells(body, n_rows, 6, 6)
+    for dtype, distance in (('presabs', 'jaccard'), ('copynum', 'euclidean')):
+        got = ctx.genes_compare(body, n_rows, 6, 6, dtype=dtype, distance=distance, group_rows=group_rows, chunk_bytes=chunk, dump=True)
+        assert (got['n_rows'], got['groups'], got['group_rows'], got['chunk_bytes']) == walk, name
+        assert _same_bits(got['cells'], cells) and np.array_equal(got['col_float'], col_float.astype(np.uint8)), name
+        _check(got, M.compare(cells, dtype, distance, 0.35), dtype, distance, name)
+
+
+@pytest.mark.parametrize("group_rows,chunk", [(10, 0), (1, 0), (0, 0), (10, 64)])
+def test_a_short_row_in_one_group_wins_over_a_bad_cell_in_the_next(ctx, group_rows, chunk):
+    body, bad = M.walker_bad_body()
+    for dtype in ('presabs', 'copynum'):
+        with pytest.raises(abi.MidasSnpsError) as ei:
+            ctx.genes_compare(body, 30, 6, 6, dtype=dtype, group_rows=group_rows, chunk_bytes=chunk)
+        assert ei.value.status == abi.ERR_BAD_LAYOUT and ei.value.bad == bad
+
+
 def _write_gene_info(db, ds):
     for sp in ds['species_ids']:
         genes = [g for g, s in zip(ds['gene_ids'], ds['gene_species']) if s == sp]

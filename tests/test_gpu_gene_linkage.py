@@ -265,6 +265,28 @@ def test_a_malformed_cell_is_reported_where_compare_genes_reports_it(ctx):
     assert ctx.genes_linkage(body, 50, S, S, need, group_rows=32)['n_rows'] == 50
 
 
+WALKS = CG.walker_cases()
+
+
+@pytest.mark.parametrize("k", range(len(WALKS)), ids=[w[0] for w in WALKS])
+def test_the_walk_of_the_rows_at_its_borders(ctx, k):
+    name, body, n_rows, group_rows, chunk = WALKS[k]
+    need = M.need_linear(6, 0.6)
+    exp = _expect(body, 6, need, n_rows=n_rows)
+    assert exp['n_kept'] > 10 and 0 < exp['linked'] < exp['visited']
+    got = ctx.genes_linkage(body, n_rows, 6, 6, np.array(need, np.int32), group_rows=group_rows, chunk_bytes=chunk)
+    assert (got['n_rows'], got['groups'], got['group_rows'], got['chunk_bytes']) == CG.walk(body, n_rows, group_rows, chunk), name
+    _same(got, exp, name)
+
+
+@pytest.mark.parametrize("group_rows,chunk", [(10, 0), (1, 0), (0, 0), (10, 64)])
+def test_a_short_row_in_one_group_wins_over_a_bad_cell_in_the_next(ctx, group_rows, chunk):
+    body, bad = CG.walker_bad_body()
+    with pytest.raises(abi.MidasSnpsError) as ei:
+        ctx.genes_linkage(body, 30, 6, 6, genes_linkage.need_table(6, 0.9), group_rows=group_rows, chunk_bytes=chunk)
+    assert ei.value.status == abi.ERR_BAD_LAYOUT and ei.value.bad == bad
+
+
 def test_the_script_in_its_own_process_writes_the_models_tables_byte_for_byte(tmp_path):
     d = str(tmp_path / 'species_1')
     synth.write_linked_genes_dir(d, 700, 90, seed=11, groups=[5, 12, 30, 50])
