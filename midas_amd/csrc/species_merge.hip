@@ -39,6 +39,7 @@
 #include <string_view>
 #include <vector>
 
+#include "species_table.h"
 #include "text_numbers.h"
 #include "text_rows.h"
 #include "workers.h"
@@ -64,13 +65,6 @@ enum SmReason : uint32_t {
 };
 
 const char* const kSmColumn[4] = {"species_id", "count_reads", "coverage", "relative_abundance"};
-
-__host__ __device__ inline unsigned long long sm_hash(const char* s, uint32_t n) {   // FNV-1a, then MurmurHash3's finaliser
-  unsigned long long h = 0xCBF29CE484222325ull;
-  for (uint32_t k = 0; k < n; ++k) { h ^= (unsigned char)s[k]; h *= 0x100000001B3ull; }
-  h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
-  return h;
-}
 
 // int(text) for [sign] and up to 18 digits
 __host__ __device__ inline bool sm_i64_fast(const char* s, uint32_t n, long long* out) {
@@ -341,7 +335,8 @@ __global__ __launch_bounds__(256) void sm_stats_kernel(const double* cov, const 
   if (mine) atomicAdd(&prev, mine);
   if (tid == 0 || tid == 64) {                           // two waves, a mean each
     const int m = tid == 0 ? 0 : 2;
-    const double mean = __ddiv_rn(sm_pairwise_sum(m == 0 ? c : a, S), (double)S);
+    // (np.mean starts its reduce from 0.0: a row of eight or more -0.0, whose pairwise sum is -0.0, has the mean 0.0)
+    const double mean = __ddiv_rn(0.0 + sm_pairwise_sum(m == 0 ? c : a, S), (double)S);
     stats[(long long)m * n_species + row] = mean;
     stats[(long long)(m + 4) * n_species + row] = sm_round2(mean);
   }
@@ -604,21 +599,9 @@ extern "C" int32_t midas_species_merge(midas_snps_ctx* ctx, int32_t n_samples, c
   const int64_t id_base = species_id_off[0];
   std::vector<uint32_t> name_off((size_t)R + 1);
   for (long long g = 0; g <= R; ++g) name_off[(size_t)g] = (uint32_t)(species_id_off[g] - id_base);
-  uint32_t table = 16;
-  while (table < 2u * (uint32_t)R + 2u) table <<= 1;
-  std::vector<int32_t> slot(table, 0);
-  for (int32_t g = 0; g < n_species; ++g) {
-    const char* nm = species_ids + species_id_off[g];
-    const uint32_t len = name_off[(size_t)g + 1] - name_off[(size_t)g];
-    uint32_t at = (uint32_t)sm_hash(nm, len) & (table - 1);
-    while (slot[at]) {
-      const int32_t o = slot[at] - 1;
-      if (name_off[(size_t)o + 1] - name_off[(size_t)o] == len && std::memcmp(species_ids + species_id_off[o], nm, len) == 0)
-        return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "a species id is listed twice");
-      at = (at + 1) & (table - 1);
-    }
-    slot[at] = g + 1;
-  }
+  std::vector<int32_t> slot;
+  if (!species_table_build(species_ids, species_id_off, n_species, &slot)) return ss_fail(ctx, MIDAS_SNPS_ERR_INVALID_ARG, "a species id is listed twice");
+  const uint32_t table = (uint32_t)slot.size();
   // ---- the groups of whole files ----------------------------------------------------------------------------------------------------
   std::vector<long long> size((size_t)S);
   for (long long s = 0; s < S; ++s) {

@@ -48,9 +48,9 @@ def same(res, want):
     assert res.prevalence.tolist() == want['prevalence'] and res.order.tolist() == want['order']
 
 
-def files_of(res, out, sample_ids):
+def files_of(res, out, sample_ids, threads=0):
     os.makedirs(str(out), exist_ok=True)
-    res.write(str(out), sample_ids)
+    res.write(str(out), sample_ids, threads)
     return dict((f, open(os.path.join(str(out), f)).read()) for f in M.FILES)
 
 
