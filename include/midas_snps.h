@@ -1281,6 +1281,37 @@ int32_t midas_genes_linkage_write_groups(const char* path, const midas_genes_mat
                                          const int32_t* row_of_slot, const int32_t* label, int64_t min_group, int64_t* out_n_groups,
                                          char* err1024);
 
+/* ---- gene_assoc.py: genes that differ between two groups of samples, with a permutation test ------------
+ * midas_genes_assoc reads the rows of genes_copynum.txt as midas_genes_compare does (same text, widths, cell converter, row groups,
+ *   place of a bad row in out_stats16[4..6]).  use_words / case_words [ceil(n_samples / 64)]: bit s set when column s takes part /
+ *   is a case (a case bit outside use_words is ignored): N used samples, n1 cases.  More than 8 191 used samples is
+ *   MIDAS_SNPS_ERR_UNSUPPORTED.  perm_planes [n_perms][ceil(n_samples / 64)]: bit s of plane b set when sample s is a case under
+ *   relabelling b (the caller sets n1 bits among the used columns); n_perms <= 1 000 000; null only with n_perms 0.
+ *   Presence is value > cutoff; c counts it over the used samples, a over the cases; a gene is kept when c >= min_present and
+ *   N - c >= min_absent and gets the next slot in file order.  kind 0 (presabs): w = a, ties = 0, x(L) = N a(L) - n1 c.  kind 1
+ *   (copynum): r_s = 2 #{t: v_t < v_s} + #{t: v_t == v_s} + 1 over the used samples, w = sum of r_s over the cases, ties = sum of
+ *   (#{t: v_t == v_s}^2 - 1), x(L) = w(L) - n1 (N + 1).  exceed = #{b: |x(M_b)| >= |x(L0)|}.
+ *   iparams8 = group_rows, chunk_bytes (0: from the free device memory), min_present, min_absent, kind, form (1: i8 MFMA; 0: one
+ *   thread a (gene, relabelling), plain adds), 0, 0.
+ *   out_row_of_slot / out_count / out_count_case (int32), out_w / out_ties (int64), out_exceed (uint32) [n_rows_max]: the first K
+ *   entries are the slots'.  out_products (nullable, tests): int32 [min(n_rows_max * n_perms, 2^24)], a(M_b) or w(M_b) at
+ *   slot * n_perms + b; MIDAS_SNPS_ERR_INVALID_ARG once K * n_perms exceeds 2^24.  Relabellings that take more than a quarter of
+ *   the free device memory are MIDAS_SNPS_ERR_OUT_OF_MEMORY.  Nothing depends on group_rows, chunk_bytes or form.
+ *   out_stats16: [0] rows read, [1] K, [4..6] a bad row, [7] row groups, [8] 1: the product kernel keeps a tile's digits in LDS,
+ *   [9] group_rows and [10] chunk_bytes in use, [11] N, [12] n1, [13] form, [14] N rounded up to the K step.  out_ms8 (nullable):
+ *   upload + index (host clock), index, parse, keep + ranks, product, expanding the relabellings, 0, download (device events).
+ * midas_genes_assoc_write: gene_id, count_case, count_control, effect, p_value, q_value and, with n_perms > 0, exceed, p_perm,
+ *   q_perm for the slots in their order (row_of_slot ascending); the doubles are the caller's, written as str() writes them. */
+int32_t midas_genes_assoc(midas_snps_ctx* ctx, const char* text, int64_t text_bytes, int64_t n_rows_max, int32_t n_samples,
+                          int32_t n_columns, const uint64_t* use_words, const uint64_t* case_words, const uint64_t* perm_planes,
+                          int64_t n_perms, double cutoff, const int64_t* iparams8, int32_t* out_row_of_slot, int32_t* out_count,
+                          int32_t* out_count_case, int64_t* out_w, int64_t* out_ties, uint32_t* out_exceed, int32_t* out_products,
+                          int64_t* out_stats16, float* out_ms8);
+int32_t midas_genes_assoc_write(const char* path, const midas_genes_matrix* m, int64_t n_slots, const int32_t* row_of_slot,
+                                const int32_t* count, const int32_t* count_case, const double* effect, const double* p_value,
+                                const double* q_value, int64_t n_perms, const uint32_t* exceed, const double* p_perm, const double* q_perm,
+                                char* err1024);
+
 /* ---- run_species.py: the aligner's m8 lines classified (midas/run/species.py:51-119) -----------------------------------------
  * midas_species_classify: `text` (host memory) is the whole alignments.m8; it goes to the device chunk_bytes at a time and stays
  *   there.  A line's fields are its runs of non-blanks; query, target, pid (float), aln (int), score (float, field 12) are used and

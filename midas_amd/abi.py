@@ -401,6 +401,8 @@ def load_library(build_if_missing: bool = True):
         'midas_genes_linkage': (i32, [vp, vp, i64, i64, i32, i32, C.c_double, vp, vp, i64] + [vp] * 8),
         'midas_genes_linkage_write_pairs': (i32, [C.c_char_p, vp, i64, vp, vp, i64, vp, vp, vp, C.c_char_p]),
         'midas_genes_linkage_write_groups': (i32, [C.c_char_p, vp, i64, vp, vp, vp, i64, C.POINTER(i64), C.c_char_p]),
+        'midas_genes_assoc': (i32, [vp, vp, i64, i64, i32, i32, vp, vp, vp, i64, C.c_double] + [vp] * 10),
+        'midas_genes_assoc_write': (i32, [C.c_char_p, vp, i64] + [vp] * 6 + [i64, vp, vp, vp, C.c_char_p]),
         'midas_species_classify': (i32, [vp, vp, i64, i32, vp, vp, vp, vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp, C.POINTER(vp)]),
         'midas_species_result_columns': (i32, [vp, vp, vp, vp]),
         'midas_species_result_lines': (i32, [vp] * 8),
@@ -459,6 +461,7 @@ EXPORTED_SYMBOLS = [
     'midas_genes_matrix_open', 'midas_genes_matrix_counts', 'midas_genes_matrix_columns', 'midas_genes_matrix_close',
     'midas_genes_compare_parse_cell', 'midas_genes_compare', 'midas_genes_compare_write_pairs',
     'midas_genes_linkage', 'midas_genes_linkage_write_pairs', 'midas_genes_linkage_write_groups',
+    'midas_genes_assoc', 'midas_genes_assoc_write',
 ]
 # the analysis entry points (snp_diversity.py, call_consensus.py, strain_tracking.py): bound above like the rest, listed by themselves
 SITES_SYMBOLS = ['midas_sites_tables_open', 'midas_sites_tables_counts', 'midas_sites_tables_columns', 'midas_sites_tables_close',
@@ -1295,6 +1298,22 @@ class GenesMatrix:
         if st != 0:
             raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_linkage_write_groups failed")
         return int(n.value)
+
+    def write_assoc(self, path: str, res: dict, table: dict):
+        """The table of gene_assoc.py (midas_genes_assoc_write) from what Context.genes_assoc returned and the host's columns:
+        table = dict(effect, p_value, q_value f64 [K] and, with permutations, p_perm, q_perm)."""
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        i32a = lambda k: np.ascontiguousarray(res[k], dtype=np.int32)
+        f64a = lambda k: None if table.get(k) is None else np.ascontiguousarray(table[k], dtype=np.float64)
+        row, count, case = i32a('row_of_slot'), i32a('count'), i32a('count_case')
+        P = int(res['n_perms'])
+        exceed = np.ascontiguousarray(res['exceed'], dtype=np.uint32) if P else None
+        cols = [f64a(k) for k in ('effect', 'p_value', 'q_value', 'p_perm', 'q_perm')]
+        err = C.create_string_buffer(1024)
+        st = self._owner._lib.midas_genes_assoc_write(path.encode(), self._owner._h, row.shape[0], p(row), p(count), p(case), p(cols[0]),
+                                                      p(cols[1]), p(cols[2]), P, p(exceed), p(cols[3]), p(cols[4]), err)
+        if st != 0:
+            raise MidasSnpsError(st, err.value.decode(errors='replace') or "midas_genes_assoc_write failed")
 
 
 def pandas_cell(text: bytes):
@@ -2307,6 +2326,42 @@ class Context:
                     pair_a=pa[:n].copy(), pair_b=pb[:n].copy(), pair_both=pc[:n].copy(), visited=int(stats[8]), linked=n,
                     label_rounds=int(stats[12]), groups=int(stats[7]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]),
                     form=int(stats[13]), strips=int(stats[14]), ms=ms.tolist())
+
+    def genes_assoc(self, text, n_rows: int, n_samples: int, n_columns: int, use, case, planes, cutoff: float = 0.35,
+                    dtype: str = 'presabs', min_present: int = 1, min_absent: int = 0, group_rows: int = 0, chunk_bytes: int = 0,
+                    form: int = 1, products: bool = False):
+        """midas_genes_assoc(): gene_assoc.py over the text rows of genes_copynum.txt, the first n_samples of n_columns sample
+        columns, rows [0, n_rows).  use, case: uint64 [ceil(n_samples / 64)], bit s: column s takes part / is a case; planes:
+        uint64 [P, ceil(n_samples / 64)], the relabellings (P may be 0).  -> dict(n_rows read, n_samples, n_used N, n_case n1,
+        n_perms P, dtype, n_kept K, row_of_slot, count, count_case int32 [K], w, ties int64 [K], exceed uint32 [K], groups,
+        group_rows, chunk_bytes, form, in_lds, ms [8]; with products (tests): products int32 [K, P]).  A malformed row raises
+        MidasSnpsError with .bad as genes_compare."""
+        tx = np.ascontiguousarray(text, dtype=np.uint8)
+        S, N = int(n_samples), int(n_rows)
+        W = (S + 63) // 64
+        us, cs = np.ascontiguousarray(use, dtype=np.uint64), np.ascontiguousarray(case, dtype=np.uint64)
+        pl = np.ascontiguousarray(planes, dtype=np.uint64).reshape(-1, W)
+        if us.shape != (W,) or cs.shape != (W,):
+            raise MidasSnpsError(ERR_INVALID_ARG, "use and case must hold ceil(n_samples / 64) words")
+        P = pl.shape[0]
+        row, count, ccase = np.zeros(N, np.int32), np.zeros(N, np.int32), np.zeros(N, np.int32)
+        w, ties, exceed = np.zeros(N, np.int64), np.zeros(N, np.int64), np.zeros(N, np.uint32)
+        prod = np.zeros(min(N * P, 1 << 24), np.int32) if products else None
+        ip = np.array([group_rows, chunk_bytes, min_present, min_absent, GENES_DTYPES[dtype], form, 0, 0], np.int64)
+        stats, ms = np.zeros(16, np.int64), np.zeros(8, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        st = self._lib.midas_genes_assoc(self._h, p(tx), tx.shape[0], N, S, int(n_columns), us.ctypes.data_as(C.c_void_p),
+                                         cs.ctypes.data_as(C.c_void_p), p(pl), P, float(cutoff), p(ip), p(row), p(count), p(ccase), p(w),
+                                         p(ties), p(exceed), p(prod), p(stats), p(ms))
+        self._check_bad(st, stats)
+        K = int(stats[1])
+        out = dict(n_rows=int(stats[0]), n_samples=S, n_used=int(stats[11]), n_case=int(stats[12]), n_perms=P, dtype=dtype, n_kept=K,
+                   row_of_slot=row[:K], count=count[:K], count_case=ccase[:K], w=w[:K], ties=ties[:K], exceed=exceed[:K],
+                   groups=int(stats[7]), group_rows=int(stats[9]), chunk_bytes=int(stats[10]), form=int(stats[13]), in_lds=int(stats[8]),
+                   ms=ms.tolist())
+        if products:
+            out['products'] = prod[:K * P].reshape(K, P).copy()
+        return out
 
     def species_classify(self, text, gene_names, gene_species, gene_marker, n_species: int, marker_cutoff, aln_cov: float,
                          chunk_bytes: int = 0, hash_bits: int = 0, dump: bool = False):

@@ -542,6 +542,68 @@ def gene_linkage_arguments(argv=None):
     return args
 
 
+def gene_assoc_arguments(argv=None):
+    """gene_assoc.py: the screen layout and the input rules of compare_genes.py; the test's options are checked here, each broken
+    rule ends with the Error exit (the rules of the --groups file are genes_assoc.read_groups').  --group_rows, --chunk_bytes and
+    --form are hidden."""
+    parser = argparse.ArgumentParser(
+        prog='gene_assoc.py', formatter_class=argparse.RawTextHelpFormatter, usage=argparse.SUPPRESS,
+        description="Description:\nGenes of one species whose presence or copy number differs between two groups of samples, with a\n"
+                    "permutation test, on the device.  Run `merge_midas.py genes` first.\n\nUsage: gene_assoc.py indir --groups FILE [options]\n",
+        epilog="Examples:\n"
+               "1) presence / absence at copy number 0.35, Fisher's exact test:\n"
+               "gene_assoc.py OUT/species_1 --groups groups.txt --out assoc.txt\n\n"
+               "2) the same with 10 000 relabellings of the samples:\n"
+               "gene_assoc.py OUT/species_1 --groups groups.txt --out assoc.txt --permutations 10000 --seed 7\n\n"
+               "3) the copy numbers themselves (rank-sum test), genes found in at least 5 samples:\n"
+               "gene_assoc.py OUT/species_1 --groups groups.txt --out assoc.txt --dtype copynum --min_present 5 --permutations 10000\n")
+    parser.add_argument('indir', metavar='PATH', type=str,
+                        help="one species directory written by `merge_midas.py genes` (holds genes_presabs.txt,\n"
+                             "genes_copynum.txt, genes_depth.txt)")
+    parser.add_argument('--groups', metavar='PATH', type=str, help="lines of sample_id<TAB>label with two distinct labels (required)")
+    parser.add_argument('--case', metavar='LABEL', type=str, help="the label of the case group (the greater label in byte order)")
+    parser.add_argument('--out', metavar='PATH', type=str, default='/dev/stdout', help="the table of genes (/dev/stdout)")
+    parser.add_argument('--max_genes', metavar='INT', type=int, help="read this many genes (rows) only (all)")
+    parser.add_argument('--max_samples', metavar='INT', type=int, help="use the first INT samples (columns) only (all)")
+    parser.add_argument('--dtype', choices=['presabs', 'copynum'], default='presabs',
+                        help="test presence / absence (Fisher's exact test) or the copy numbers (rank-sum test) (presabs)")
+    parser.add_argument('--cutoff', metavar='FLOAT', type=float, default=0.35, help="a gene is present above this copy number (0.35)")
+    parser.add_argument('--min_present', metavar='INT', type=int, default=1, help="keep genes present in at least INT used samples (1)")
+    parser.add_argument('--min_absent', metavar='INT', type=int, default=0, help="keep genes absent from at least INT used samples (0)")
+    parser.add_argument('--permutations', metavar='INT', type=int, default=0, help="relabellings of the samples for p_perm (0: none)")
+    parser.add_argument('--seed', metavar='INT', type=int, default=0, help="seed of the relabellings (0)")
+    parser.add_argument('--group_rows', type=int, default=0, help=argparse.SUPPRESS)
+    parser.add_argument('--chunk_bytes', type=int, default=0, help=argparse.SUPPRESS)
+    parser.add_argument('--form', type=int, default=1, help=argparse.SUPPRESS)
+    args = vars(parser.parse_args(argv))
+    for ext in ['presabs', 'depth', 'copynum']:
+        inpath = '%s/genes_%s.txt' % (args['indir'], ext)
+        if not os.path.isfile(inpath):
+            sys.exit("\nError: Input file does not exist: %s\n" % inpath)
+        args[ext] = inpath
+    if args['groups'] is None:
+        _exit("--groups is required")
+    if not os.path.isfile(args['groups']):
+        _exit("Specified input file '%s' does not exist" % args['groups'])
+    if args['cutoff'] != args['cutoff'] or args['cutoff'] in (float('inf'), float('-inf')):
+        _exit("--cutoff must be a finite number")
+    if args['min_present'] < 0:
+        _exit("--min_present cannot be a negative number")
+    if args['min_absent'] < 0:
+        _exit("--min_absent cannot be a negative number")
+    if not 0 <= args['permutations'] <= 1000000:
+        _exit("--permutations must be between 0 and 1000000")
+    if args['seed'] < 0:
+        _exit("--seed cannot be a negative number")
+    if args['group_rows'] < 0:
+        _exit("--group_rows cannot be a negative number")
+    if args['chunk_bytes'] < 0:
+        _exit("--chunk_bytes cannot be a negative number")
+    if args['form'] not in (0, 1):
+        _exit("--form must be 0 or 1")
+    return args
+
+
 COPYRIGHT = ["", "MIDAS: Metagenomic Intra-species Diversity Analysis System", "analysis commands on AMD Instinct MI355X (midas_amd %s)",
              "after github.com/snayfach/MIDAS, Copyright (C) 2015-2016 Stephen Nayfach",
              "Freely distributed under the GNU General Public License (GPLv3)", ""]

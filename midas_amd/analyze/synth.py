@@ -185,3 +185,40 @@ def write_linked_genes_dir(path, n_genes, n_samples, seed=0, groups=None, block=
             idx = np.where(present, rng.integers(2, len(palette), (n, n_samples)), (rng.random((n, n_samples)) < 0.1).astype(np.int64))
             f.write(_matrix_bytes(r0, idx, palette).tobytes())
     return dict(sample_ids=sample_ids, group_of=group_of)
+
+
+def write_assoc_genes_dir(path, n_genes, n_samples, seed=0, associated=0.01, unnamed=0.05, block=10000):
+    """-> dict(sample_ids, groups_path, planted bool [n_genes]).  One species directory in the shape `merge_midas.py genes`
+    writes, for gene_assoc.py, with groups.txt beside the matrices: a share `unnamed` of the samples carries no label, the others
+    are 'case' or 'control' at even odds.  Most genes are independent of the label at mixed prevalence (as in
+    write_linked_genes_dir); a share `associated` of them is planted: present in 70 % of the cases and 25 % of the controls,
+    with copy numbers half as high again in the cases.  A present cell is a short decimal above 0.4, an absent one 0.0 or, one
+    in ten, 0.21: many tied zeros, as in the real matrices."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    sample_ids = ['sample_%03d' % k for k in range(n_samples)]
+    named = rng.random(n_samples) >= unnamed
+    is_case = rng.random(n_samples) < 0.5
+    named[:2], is_case[0], is_case[1] = True, True, False        # (both groups are never empty)
+    groups_path = os.path.join(path, 'groups.txt')
+    with open(groups_path, 'w') as f:
+        f.write('sample_id\tlabel\n' + ''.join('%s\t%s\n' % (sample_ids[k], 'case' if is_case[k] else 'control') for k in range(n_samples) if named[k]))
+    planted = rng.random(n_genes) < associated
+    palette = ['0.0', '0.21'] + ['%.3f' % v for v in np.sort(0.4 + rng.gamma(2.0, 0.6, 62))]
+    header = ('\t'.join(['gene_id'] + sample_ids) + '\n').encode()
+    for kind in ('presabs', 'depth'):
+        with open(os.path.join(path, 'genes_%s.txt' % kind), 'wb') as f:
+            f.write(header)
+    with open(os.path.join(path, 'genes_copynum.txt'), 'wb') as f:
+        f.write(header)
+        for r0 in range(0, n_genes, block):
+            n = min(block, n_genes - r0)
+            prevalence = 0.02 + 0.83 * rng.beta(0.6, 0.6, (n, 1))
+            level = np.where(is_case, 0.70, 0.25)[None, :]
+            p = np.where(planted[r0:r0 + n, None], level, prevalence)
+            present = rng.random((n, n_samples)) < p
+            value = rng.integers(2, 2 + 31, (n, n_samples))                                   # the lower half of the sorted palette
+            value = np.where(planted[r0:r0 + n, None] & is_case[None, :], value + 31, value)    # the upper half for the cases of a planted gene
+            idx = np.where(present, value, (rng.random((n, n_samples)) < 0.1).astype(np.int64))
+            f.write(_matrix_bytes(r0, idx, palette).tobytes())
+    return dict(sample_ids=sample_ids, groups_path=groups_path, planted=planted)
