@@ -1312,6 +1312,35 @@ int32_t midas_genes_assoc_write(const char* path, const midas_genes_matrix* m, i
                                 const double* q_value, int64_t n_perms, const uint32_t* exceed, const double* p_perm, const double* q_perm,
                                 char* err1024);
 
+/* ---- gene_curves.py: pangenome and core-genome accumulation curves over orders of the samples -----------
+ * midas_genes_curves reads the rows of genes_copynum.txt as midas_genes_compare does (same text, widths, cell converter, row groups,
+ *   place of a bad row in out_stats16[4..6]).  orders [n_orders][n_used] (int32): row 0 lists the n_used columns in use, every other
+ *   row is a permutation of them; 1 <= n_orders <= 100 001, 1 <= n_used <= 8 191.  need [n_used + 1] (int32): need[k] = the fewest
+ *   of the first k samples in which a core gene is present, 1 <= need[k] <= k (need[0] is not read).  Before any device work the
+ *   entry point checks that every entry of orders is in [0, n_samples), that row 0 holds distinct entries, that every other row is
+ *   a permutation of row 0's set and that need[] keeps its bounds: MIDAS_SNPS_ERR_INVALID_ARG with a message that names the row,
+ *   and the outputs untouched.
+ *   Presence is value > cutoff; c(g, r, k) = the number of the first k samples of order r in which gene g is present.
+ *   out_pan / out_core / out_single [n_orders][n_used] (int64): at [r][k - 1] the genes with c >= 1, with c >= need[k], with
+ *   c == 1, over every row read.  Orders and accumulators that take more than a quarter of the free device memory are
+ *   MIDAS_SNPS_ERR_OUT_OF_MEMORY.  Nothing depends on group_rows, chunk_bytes or form.
+ *   iparams8 = group_rows, chunk_bytes (0: from the free device memory), form (1: counts kept as bit planes over words of 64
+ *   genes; 0: one thread a (order, gene), a plain count), 0, 0, 0, 0, 0.
+ *   out_stats16: [0] rows read, [4..6] a bad row, [7] row groups, [8] words of 64 genes of the last group, [9] group_rows and
+ *   [10] chunk_bytes in use, [11] n_used, [12] n_orders, [13] form, [14] counter planes a lane keeps (7, 10 or 13; form 0: 0).
+ *   out_ms8 (nullable): upload + index (host clock), index, parse, planes, curves, 0, 0, download (device events).
+ * midas_genes_curves_write: table 0: samples, pan, core, single, new (= pan[k] - pan[k - 1]) of order 0 for k = 1 .. n_used and,
+ *   with n_perms > 0, pan_mean pan_min pan_max core_mean core_min core_max single_mean single_min single_max new_mean from means
+ *   [4][n_used] (pan, core, single, new; written as str() writes them) and minmax [6][n_used] (int64: pan min, max, core min, max,
+ *   single min, max).  table 1: order, samples, sample_id, pan, core, single for every (order, k); orders as above.            */
+int32_t midas_genes_curves(midas_snps_ctx* ctx, const char* text, int64_t text_bytes, int64_t n_rows_max, int32_t n_samples,
+                           int32_t n_columns, const int32_t* orders, int64_t n_orders, int32_t n_used, const int32_t* need, double cutoff,
+                           const int64_t* iparams8, int64_t* out_pan, int64_t* out_core, int64_t* out_single, int64_t* out_stats16,
+                           float* out_ms8);
+int32_t midas_genes_curves_write(const char* path, const midas_genes_matrix* m, int32_t table, int64_t n_orders, int32_t n_used,
+                                 const int64_t* pan, const int64_t* core, const int64_t* single, const int32_t* orders, int64_t n_perms,
+                                 const double* means, const int64_t* minmax, char* err1024);
+
 /* ---- run_species.py: the aligner's m8 lines classified (midas/run/species.py:51-119) -----------------------------------------
  * midas_species_classify: `text` (host memory) is the whole alignments.m8; it goes to the device chunk_bytes at a time and stays
  *   there.  A line's fields are its runs of non-blanks; query, target, pid (float), aln (int), score (float, field 12) are used and

@@ -20,7 +20,7 @@ from .pileup import (DEFAULT_ARGS, INDEX_FACTS, NUM_STATS, PAD_PYSAM, PAD_SPEC, 
 from .merge import (DEFAULT_MERGE_ARGS, ERR_MERGE_ZERO_MEAN_DEPTH, GENES_MATRIX_KINDS, SNP_TYPE_BITS, SNP_TYPE_NAMES, TABLES_READ_PHASES,
                     TABLES_READ_STATS, GeneClusterMap, GeneTables, MergeParams, MergeTables, _Genes, format_repr_f64, write_genes_matrix,
                     write_merge_info, write_merge_matrix, write_merge_matrix_device)
-from .genes import GENES_BAM_PHASES, GENES_BAM_STATS, GENES_DISTANCES, GENES_DTYPES, GenesMatrix, pandas_cell
+from .genes import GENES_BAM_PHASES, GENES_BAM_STATS, GENES_DISTANCES, GENES_DTYPES, GenesMatrix, genes_curves, pandas_cell
 from .sites import (ALLELE_LETTERS, SITES_LD_MAX_BINS, SITES_LD_SAME_GENE, SITES_MASK_ONLY, SITES_MAX_CLASSES, SITES_PAIR_TILE,
                     SITES_PER_GENE, SITES_POOLED, SITES_ROUND, SITES_SEQ, SITES_SUMS, SITES_WEIGHT, SitesTables, parse_cell)
 from .species import (SPECIES_MERGE_PHASES, SPECIES_MERGE_REASONS, SPECIES_MERGE_STATS, SPECIES_PHASES, SPECIES_REASONS, SpeciesMerge,

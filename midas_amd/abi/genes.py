@@ -1,5 +1,5 @@
 """run_midas.py genes (the per-gene counts) and the commands over merged gene matrices: compare_genes.py, gene_linkage.py,
-gene_assoc.py."""
+gene_assoc.py, gene_curves.py."""
 
 from __future__ import annotations
 
@@ -38,6 +38,8 @@ register('exported', {
     'midas_genes_linkage_write_groups': (i32, [cstr, vp, i64, vp, vp, vp, i64, P(i64), cstr]),
     'midas_genes_assoc': (i32, [vp, vp, i64, i64, i32, i32, vp, vp, vp, i64, f64] + [vp] * 10),
     'midas_genes_assoc_write': (i32, [cstr, vp, i64] + [vp] * 6 + [i64, vp, vp, vp, cstr]),
+    'midas_genes_curves': (i32, [vp, vp, i64, i64, i32, i32, vp, i64, i32, vp, f64] + [vp] * 6),
+    'midas_genes_curves_write': (i32, [cstr, vp, i32, i64, i32, vp, vp, vp, vp, i64, vp, vp, cstr]),
 })
 
 
@@ -99,6 +101,34 @@ class GenesMatrix:
         self._write('midas_genes_assoc_write', path, row.shape[0], ptr(row), ptr(count), ptr(case), ptr(cols[0]), ptr(cols[1]),
                     ptr(cols[2]), n_perms, ptr(exceed), ptr(cols[3]), ptr(cols[4]))
 
+    def _write_curves(self, path: str, which: int, res: dict, orders=None, table=None):
+        """Either table of gene_curves.py (midas_genes_curves_write) from what genes_curves returned."""
+        i64a = lambda a: np.ascontiguousarray(a, dtype=np.int64)
+        pan, core, single = i64a(res['pan']), i64a(res['core']), i64a(res['single'])
+        R, N = pan.shape
+        od = None if orders is None else np.ascontiguousarray(orders, dtype=np.int32)
+        if pan.shape != core.shape or pan.shape != single.shape or (od is not None and od.shape != pan.shape):
+            raise MidasSnpsError(ERR_INVALID_ARG, "pan, core, single and orders must be [orders, samples in use] alike")
+        n_perms = R - 1 if table else 0
+        means = minmax = None
+        if n_perms:
+            means = np.ascontiguousarray([table[k] for k in ('pan_mean', 'core_mean', 'single_mean', 'new_mean')], dtype=np.float64)
+            minmax = np.ascontiguousarray([table[k] for k in ('pan_min', 'pan_max', 'core_min', 'core_max', 'single_min', 'single_max')],
+                                          dtype=np.int64)
+            if means.shape != (4, N) or minmax.shape != (6, N):
+                raise MidasSnpsError(ERR_INVALID_ARG, "every statistic column must hold one entry a sample in use")
+        self._write('midas_genes_curves_write', path, which, R, N, ptr(pan), ptr(core), ptr(single), ptr(od), n_perms, ptr(means), ptr(minmax))
+
+    def write_curves(self, path: str, res: dict, table: dict):
+        """The curve table of gene_curves.py from what genes_curves returned and the host's columns: table = dict(pan_mean,
+        core_mean, single_mean, new_mean f64 [N]; pan_min, pan_max, core_min, core_max, single_min, single_max int64 [N]), or an
+        empty dict when there is no random order."""
+        self._write_curves(path, 0, res, table=table)
+
+    def write_curve_orders(self, path: str, res: dict, orders):
+        """The table of every order of gene_curves.py: one row an (order, k) with the id of the sample added at that step."""
+        self._write_curves(path, 1, res, orders=orders)
+
 
 def pandas_cell(text: bytes):
     """A matrix cell as pandas' C reader converts it, by the library's host build of the device converter
@@ -116,6 +146,33 @@ def _matrix_text(text, n_rows, n_samples, n_columns):
     tx = np.ascontiguousarray(text, dtype=np.uint8)
     N, S = int(n_rows), int(n_samples)
     return tx, N, S, (ptr(tx), tx.shape[0], N, S, int(n_columns))
+
+
+def genes_curves(ctx, text, n_rows: int, n_samples: int, n_columns: int, orders, need, cutoff: float = 0.35, form: int = 1,
+                 group_rows: int = 0, chunk_bytes: int = 0, out=None):
+    """midas_genes_curves() on the context ctx: gene_curves.py over the text rows of genes_copynum.txt, the first n_samples of
+    n_columns sample columns, rows [0, n_rows).  orders: int32 [R, N], row 0 the columns in use, every other row a permutation
+    of them; need: int32 [N + 1], 1 <= need[k] <= k.  -> dict(n_rows read, n_samples, n_used N, n_orders R, pan, core, single
+    int64 [R, N], groups, group_rows, chunk_bytes, form, planes, words, ms [8]).  A broken rule of orders or need raises
+    MidasSnpsError (ERR_INVALID_ARG) whose message names the row, a malformed row of the matrix raises it with .bad as
+    Context.genes_compare.  out (tests): three int64 [R, N] arrays to receive pan, core and single."""
+    tx, n, S, head = _matrix_text(text, n_rows, n_samples, n_columns)
+    od = np.ascontiguousarray(orders, dtype=np.int32)
+    nd = np.ascontiguousarray(need, dtype=np.int32)
+    if od.ndim != 2 or od.shape[0] < 1 or od.shape[1] < 1:
+        raise MidasSnpsError(ERR_INVALID_ARG, "orders must be [orders, samples in use], one row at least")
+    R, N = od.shape
+    if nd.shape != (N + 1,):
+        raise MidasSnpsError(ERR_INVALID_ARG, "need must hold one entry more than a row of orders")
+    pan, core, single = out if out is not None else (np.zeros((R, N), np.int64), np.zeros((R, N), np.int64), np.zeros((R, N), np.int64))
+    for a in (pan, core, single):
+        if a.dtype != np.int64 or a.shape != (R, N) or not a.flags.c_contiguous:
+            raise MidasSnpsError(ERR_INVALID_ARG, "out must be three contiguous int64 arrays shaped as orders")
+    ip = np.array([group_rows, chunk_bytes, form, 0, 0, 0, 0, 0], np.int64)
+    stats, ms = ctx._device_call(ctx._lib.midas_genes_curves, *head, ptr(od), R, N, ptr(nd), float(cutoff), ptr(ip), ptr(pan), ptr(core),
+                                 ptr(single))
+    return dict(walk_stats(stats, 'n_rows', side=False), n_samples=S, n_used=N, n_orders=R, pan=pan, core=core, single=single,
+                form=int(stats[13]), planes=int(stats[14]), words=int(stats[8]), ms=ms.tolist())
 
 
 class _GenesCalls:

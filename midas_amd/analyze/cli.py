@@ -604,6 +604,63 @@ def gene_assoc_arguments(argv=None):
     return args
 
 
+def gene_curves_arguments(argv=None):
+    """gene_curves.py: the screen layout and the input rules of compare_genes.py; the curves' options are checked here, each broken
+    rule ends with the Error exit (the rules of the --samples file are genes_curves.read_samples').  --group_rows, --chunk_bytes
+    and --form are hidden."""
+    parser = argparse.ArgumentParser(
+        prog='gene_curves.py', formatter_class=argparse.RawTextHelpFormatter, usage=argparse.SUPPRESS,
+        description="Description:\nHow the pangenome of one species grows and its core genome shrinks as samples are added: accumulation\n"
+                    "curves over the listed and over random orders of the samples, with Heaps' law, on the device.\n"
+                    "Run `merge_midas.py genes` first.\n\nUsage: gene_curves.py indir [options]\n",
+        epilog="Examples:\n"
+               "1) defaults (presence above copy number 0.35, a core gene is in every sample, 100 random orders):\n"
+               "gene_curves.py OUT/species_1 --out curves.txt\n\n"
+               "2) a soft core (95 % of the samples so far), 1 000 orders, every order's curve kept:\n"
+               "gene_curves.py OUT/species_1 --out curves.txt --core_frac 0.95 --permutations 1000 --seed 7 --orders orders.txt\n\n"
+               "3) the listed order alone, over the samples a file names:\n"
+               "gene_curves.py OUT/species_1 --out curves.txt --samples ids.txt --permutations 0\n")
+    parser.add_argument('indir', metavar='PATH', type=str,
+                        help="one species directory written by `merge_midas.py genes` (holds genes_presabs.txt,\n"
+                             "genes_copynum.txt, genes_depth.txt)")
+    parser.add_argument('--out', metavar='PATH', type=str, default='/dev/stdout', help="the table of curves, one row a number of samples (/dev/stdout)")
+    parser.add_argument('--orders', metavar='PATH', type=str, help="the curve of every order, one row an order and sample (not written)")
+    parser.add_argument('--samples', metavar='PATH', type=str, help="use the samples this file lists, one id a line (all)")
+    parser.add_argument('--max_genes', metavar='INT', type=int, help="read this many genes (rows) only (all)")
+    parser.add_argument('--max_samples', metavar='INT', type=int, help="use the first INT samples (columns) only (all)")
+    parser.add_argument('--cutoff', metavar='FLOAT', type=float, default=0.35, help="a gene is present above this copy number (0.35)")
+    parser.add_argument('--core_frac', metavar='FLOAT', type=float, default=1.0,
+                        help="a gene is core while it is present in at least this share of the samples so far (1.0)")
+    parser.add_argument('--permutations', metavar='INT', type=int, default=100, help="random orders of the samples beside the listed one (100)")
+    parser.add_argument('--seed', metavar='INT', type=int, default=0, help="seed of the random orders (0)")
+    parser.add_argument('--group_rows', type=int, default=0, help=argparse.SUPPRESS)
+    parser.add_argument('--chunk_bytes', type=int, default=0, help=argparse.SUPPRESS)
+    parser.add_argument('--form', type=int, default=1, help=argparse.SUPPRESS)
+    args = vars(parser.parse_args(argv))
+    for ext in ['presabs', 'depth', 'copynum']:
+        inpath = '%s/genes_%s.txt' % (args['indir'], ext)
+        if not os.path.isfile(inpath):
+            sys.exit("\nError: Input file does not exist: %s\n" % inpath)
+        args[ext] = inpath
+    if args['samples'] is not None and not os.path.isfile(args['samples']):
+        _exit("Specified input file '%s' does not exist" % args['samples'])
+    if args['cutoff'] != args['cutoff'] or args['cutoff'] in (float('inf'), float('-inf')):
+        _exit("--cutoff must be a finite number")
+    if not 0 < args['core_frac'] <= 1:
+        _exit("--core_frac must be above 0 and at most 1")
+    if not 0 <= args['permutations'] <= 100000:
+        _exit("--permutations must be between 0 and 100000")
+    if args['seed'] < 0:
+        _exit("--seed cannot be a negative number")
+    if args['group_rows'] < 0:
+        _exit("--group_rows cannot be a negative number")
+    if args['chunk_bytes'] < 0:
+        _exit("--chunk_bytes cannot be a negative number")
+    if args['form'] not in (0, 1):
+        _exit("--form must be 0 or 1")
+    return args
+
+
 COPYRIGHT = ["", "MIDAS: Metagenomic Intra-species Diversity Analysis System", "analysis commands on AMD Instinct MI355X (midas_amd %s)",
              "after github.com/snayfach/MIDAS, Copyright (C) 2015-2016 Stephen Nayfach",
              "Freely distributed under the GNU General Public License (GPLv3)", ""]

@@ -222,3 +222,34 @@ def write_assoc_genes_dir(path, n_genes, n_samples, seed=0, associated=0.01, unn
             idx = np.where(present, value, (rng.random((n, n_samples)) < 0.1).astype(np.int64))
             f.write(_matrix_bytes(r0, idx, palette).tobytes())
     return dict(sample_ids=sample_ids, groups_path=groups_path, planted=planted)
+
+
+def write_pangenome_curve_dir(path, n_genes, n_samples, seed=0, block=10000):
+    """-> dict(sample_ids, kind int8 [n_genes]).  One species directory in the shape `merge_midas.py genes` writes, for
+    gene_curves.py: a core that erodes and a pangenome that keeps growing.  Every gene draws one of eight kinds: 0 present in
+    every sample, 1 in all but one, 2 / 3 / 4 / 5 in about 97 %, 70 %, 30 % and 2 % of the samples, 6 in exactly one sample, 7
+    in none (shares 15, 5, 10, 15, 20, 20, 10 and 5 %).  A present cell is a short decimal above 0.4, an absent one 0.0 or, one
+    in ten, 0.21."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    sample_ids = ['sample_%03d' % k for k in range(n_samples)]
+    kind = rng.choice(8, n_genes, p=[0.15, 0.05, 0.10, 0.15, 0.20, 0.20, 0.10, 0.05]).astype(np.int8)
+    level = np.array([1.0, 1.0, 0.97, 0.70, 0.30, 0.02, 0.0, 0.0])
+    palette = ['0.0', '0.21'] + ['%.3f' % v for v in 0.4 + rng.gamma(2.0, 0.6, 62)]
+    header = ('\t'.join(['gene_id'] + sample_ids) + '\n').encode()
+    for name in ('presabs', 'depth'):
+        with open(os.path.join(path, 'genes_%s.txt' % name), 'wb') as f:
+            f.write(header)
+    with open(os.path.join(path, 'genes_copynum.txt'), 'wb') as f:
+        f.write(header)
+        for r0 in range(0, n_genes, block):
+            n = min(block, n_genes - r0)
+            k = kind[r0:r0 + n]
+            present = rng.random((n, n_samples)) < level[k][:, None]
+            lone = rng.integers(0, n_samples, n)                       # the sample a gene of kind 1 misses, one of kind 6 has
+            rows = np.arange(n)
+            present[rows[k == 1], lone[k == 1]] = False
+            present[rows[k == 6], lone[k == 6]] = True
+            idx = np.where(present, rng.integers(2, len(palette), (n, n_samples)), (rng.random((n, n_samples)) < 0.1).astype(np.int64))
+            f.write(_matrix_bytes(r0, idx, palette).tobytes())
+    return dict(sample_ids=sample_ids, kind=kind)

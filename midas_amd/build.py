@@ -17,7 +17,7 @@ OBJ_DIR = os.path.join(LIB_DIR, "obj")
 LIB_NAME = "libmidas_snps_hip.so"
 LIB_PATH = os.path.join(LIB_DIR, LIB_NAME)
 
-SOURCES = ["contigs.cpp", "bgzf_host.cpp", "bam_host.cpp", "bam_shares.cpp", "bam_writer.cpp", "tables_host.cpp", "fasta_host.cpp", "row_deflate.cpp", "comm.cpp", "pack_reads.hip", "index_reads.hip", "pileup_tiles.hip", "index_direct.hip", "pileup_direct.hip", "pileup_long.hip", "rows_deflate.hip", "bgzf_inflate.hip", "bam_walk.hip", "measure.hip", "merge_sites.hip", "merge_rows.hip", "tables_scan.hip", "tables_device.hip", "genes_count.hip", "genes_merge_io.cpp", "genes_merge.hip", "sites_io.cpp", "sites_scan.hip", "sites_strains.hip", "sites_trees.hip", "sites_pairs.hip", "sites_ld.hip", "nj_tree.hip", "genes_compare.hip", "genes_linkage.hip", "genes_assoc.hip", "sam_scan.hip", "species_hits.hip", "species_assign.cpp", "species_merge.hip", "device_sort.hip", "mt19937_stream.hip", "bam_device.hip", "ctx_runtime.hip", "batch.hip", "batch_direct.hip", "batch_packed.hip", "batch_rows.hip"]
+SOURCES = ["contigs.cpp", "bgzf_host.cpp", "bam_host.cpp", "bam_shares.cpp", "bam_writer.cpp", "tables_host.cpp", "fasta_host.cpp", "row_deflate.cpp", "comm.cpp", "pack_reads.hip", "index_reads.hip", "pileup_tiles.hip", "index_direct.hip", "pileup_direct.hip", "pileup_long.hip", "rows_deflate.hip", "bgzf_inflate.hip", "bam_walk.hip", "measure.hip", "merge_sites.hip", "merge_rows.hip", "tables_scan.hip", "tables_device.hip", "genes_count.hip", "genes_merge_io.cpp", "genes_merge.hip", "sites_io.cpp", "sites_scan.hip", "sites_strains.hip", "sites_trees.hip", "sites_pairs.hip", "sites_ld.hip", "nj_tree.hip", "genes_compare.hip", "genes_linkage.hip", "genes_assoc.hip", "genes_curves.hip", "sam_scan.hip", "species_hits.hip", "species_assign.cpp", "species_merge.hip", "device_sort.hip", "mt19937_stream.hip", "bam_device.hip", "ctx_runtime.hip", "batch.hip", "batch_direct.hip", "batch_packed.hip", "batch_rows.hip"]
 HEADERS = ["layout.h", "contigs.h", "kernels.h", "device_common.h", "pileup_common.h", "direct_common.h", "dense_bases.h", "ctx_internal.h", "batch.h", "filter_tables.h", "work_plan.h", "hostio.h", "hostio_internal.h", "bam_parse.h", "bam_record.h", "decode_plan.h", "sam_resident_plan.h", "tables_plan.h", "row_deflate.h", "workers.h", "crc32.h", "text_numbers.h", "text_rows.h", "species_table.h", "bit_planes.h", "assoc_kernels.h", "row_group_plan.h", "genes_rows.h", "sites_rows.h", "sites_call.h", "sites_resample.h", "draw_plan.h", "pandas_f64.h", "merge_fmt.h", "merge_rows.h", os.path.join("..", "..", "include", "midas_snps.h")]
 
 # The atomic optimizer turns a one-lane atomicAdd into mbcnt/readfirstlane and waits for the result at once; the
@@ -27,7 +27,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdg
 # sites_call.h too, the first of sites_resample.h: round(f * N) of --rand_reads) and genes_compare.hip reproduce sums and products the interpreter forms with one rounding per operation: no
 # fused multiply-add there (bit_planes.h and genes_rows.h are compiled both with the flag and, in genes_linkage.hip and genes_assoc.hip, without it: the first holds no
 # fp arithmetic, only comparisons, the second's cell parse spells its operations with __dmul_rn / __ddiv_rn in pandas_f64.h; genes_assoc.hip and
-# assoc_kernels.h compare the parsed doubles and form integers only, so they need no place in this list);
+# assoc_kernels.h compare the parsed doubles and form integers only, so they need no place in this list; genes_curves.hip likewise
+# holds only the comparison value > cutoff and integers: no entry here either);
 # species_hits.hip decodes float() with one multiply or divide and evaluates the reference's filters;
 # species_merge.hip decodes the same way and forms numpy's means and round(x, 2); merge_rows.hip decides '{0:.3g}' ties by the
 # double minor / depth; nj_tree.hip forms every Q value, branch length and joined distance as the contract writes it
